@@ -2,8 +2,14 @@
 """Benchmark of the NPVP Stage-2 predictor training step on MI355X (BASELINE.json metric:
 "predictor train frames/sec at 1/2/4/8 MI355X; MFMA util %").
 
-    python bench.py --gpus 1 --steps K --warmup W
-    python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
+    python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W [--full]
+
+A plain run measures the headline figure only: it builds the primary workload, warms up (and, with --mode auto, times eager
+against replay to pick the step it times), times K steps and prints the result line.  --full adds everything else described
+below - the roofline probes, `replay_check`, the secondary workloads and the CPU baseline - each still switched off by its own
+--no-* option.  --dump-outputs DIR writes what the last timed step returned to its caller (see `step_outputs`) as DIR/<name>.npy;
+the inputs, weights and seeds depend on the arguments only, so two builds can be compared output for output.
 
 A "step" is one optimisation step of the predictor-only flavour of the reference's
 training_step_no_gan: frozen-encoder feature grids in HBM -> predictor fwd (S: context +
@@ -25,7 +31,7 @@ data-parallel configuration for that GPU count (c3 on 4, c4 on 8 and - as a rehe
 run rank 0 alone times that configuration's global batch and its shard on one GPU, so that `scaling_dp` carries both the
 strong ratio (N GPUs / the whole batch on 1) and the shard efficiency (N GPUs / N x one shard on 1).
 
-Prints ONE JSON line (rank 0) with `roofline` (dominant kernel = the GEMM layout - forward or dgrad -
+Prints ONE JSON line (rank 0); with --full it carries `roofline` (dominant kernel = the GEMM layout - forward or dgrad -
 with the largest share of the timed region, timed live with HIP event pairs around every launch on the
 stream it is launched on), `roofline_hbm` (the three kernels that lead the HBM-bound half of the step: algorithmic bytes,
 event-pair time in the step, TB/s against 8 TB/s) and, at N=1, `cpu_baseline` (the CPU oracle restatement of the same step
@@ -66,6 +72,7 @@ WORKLOADS = {   # name -> (config file, variant, per-GPU clips, To, Tp)
 HBM_PEAK_TBS = 8.0            # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec (6.29 TB/s measured by a float4 copy)
 MFMA_PEAK_TFLOPS = 2500.0     # MI355X_MICROARCH.md: dense bf16 MFMA peak (v_mfma_f32_32x32x16_bf16); fp32-input MFMA: 157.3
 LAYOUTS = {(1, 1): "forward", (1, 0): "dgrad", (0, 0): "wgrad"}
+DUMP_PARAM_SAMPLE = 1 << 22   # --dump-outputs: the updated parameters, all of them up to 4 Mi values (16 MB), else that many at fixed positions
 
 
 def forward_macs_per_clip(To, Tp, stochastic):
@@ -154,6 +161,28 @@ def library_hash():
     return hashlib.sha256(open(LIB_PATH, "rb").read()).hexdigest()
 
 
+def step_outputs(out, model):
+    """-> {name: float32 array}: what the caller of a train step receives from it - the step's result (loss, its terms and the
+    clipped gradient norm: 0-d) and the parameters it updated in place, `model.parameters()` flattened in order (`params`; beyond
+    DUMP_PARAM_SAMPLE values, that many at positions drawn once with a fixed seed, in ascending order)"""
+    res = {k: v.detach().float().cpu().numpy() for k, v in out.items() if isinstance(v, torch.Tensor)}
+    with torch.no_grad():
+        flat = torch.cat([p.reshape(-1) for p in model.parameters()])
+        if flat.numel() > DUMP_PARAM_SAMPLE:
+            idx = torch.randperm(flat.numel(), generator=torch.Generator().manual_seed(0))[:DUMP_PARAM_SAMPLE].sort().values
+            flat = flat[idx.to(flat.device)]
+        res["params"] = flat.float().cpu().numpy()
+    return res
+
+
+def write_outputs(outputs, path):
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, a in outputs.items():
+        np.save(os.path.join(path, f"{name}.npy"), a)
+    log(f"outputs of the last timed step: {', '.join(f'{k} {tuple(a.shape)}' for k, a in outputs.items())} -> {path}")
+
+
 def log(msg):
     if int(os.environ.get("RANK", "0")) == 0:
         print(f"[bench {time.strftime('%H:%M:%S')}] {msg}", file=sys.stderr, flush=True)
@@ -167,10 +196,11 @@ def run_workload(key, *a, **kw):
         return _run_workload(key, *a, **kw)
 
 
-def _run_workload(key, steps, warmup, args, rank, world, dev, probe, flavour=None, clips=None, mode="eager", check=False):
+def _run_workload(key, steps, warmup, args, rank, world, dev, probe, flavour=None, clips=None, mode="eager", check=False, dump=False):
     """Build the workload's model / optimiser / synthetic batch, run `warmup` untimed and `steps` timed steps
     (barrier + synchronize on both sides, MAX over ranks), free everything.  -> result dict.  world = 1 inside a multi-rank job =
     a SOLO run of the calling rank (no collectives, no barrier): the one-GPU denominators of `scaling_dp`.
+    dump: the result carries `outputs` = step_outputs() of the last timed step, read before anything else runs a step.
     mode: "eager" (two streams, host enqueues every launch), "graph" (the step captured single-stream into ONE HIP graph and replayed:
     no host in the loop) or "auto" = whichever of the two is faster in a short timed trial after the warm-up - only tried when the eager
     step is plausibly host bound (host enqueue time >= 60 % of the step), single process, predictor flavour.  The record says which."""
@@ -443,6 +473,7 @@ def _run_workload(key, steps, warmup, args, rank, world, dev, probe, flavour=Non
         graph_nodes = {k: v for k, v in gstep.census.items() if k != "memset_bytes"}        # (node census of the replayed step: no "memset")
     fence()
     dt = time.perf_counter() - t0
+    outputs = step_outputs(out, model) if dump else None      # (before the probes' extra steps and replay_check below move the state on)
     if check and replayed and check_state:
         check_state["result"].copy_(opt.flat_p)
     log(f"[{key}] after the timed steps: reserved {torch.cuda.memory_reserved(dev) / 2 ** 30:.1f} GiB, allocator retries "
@@ -586,7 +617,7 @@ def _run_workload(key, steps, warmup, args, rank, world, dev, probe, flavour=Non
     res = {"key": key, "name": name, "B": B, "To": To, "Tp": Tp, "ms": ms, "frames_per_s": frames / (ms * 1e-3), "peak_gb": peak_gb,
            "loss": loss, "host_ms": 1000.0 * t_host / steps, "flops_step": flops_step, "roof": roof, "roof_hbm": roof_hbm, "steps": steps,
            "warmup": warmup, "range_events": events, "launches": launches, "mode": used, "mode_trial": trial_ms, "replay_check": replay_check,
-           "graph_nodes": graph_nodes}
+           "graph_nodes": graph_nodes, "outputs": outputs}
     if gsync is not None:
         # how many ranks REALLY reduce together: the mean over the ranks of (rank + 1), through the very exchange the gradient buckets
         # take (ProcessGroup or the library's npvp_dp_*), must be (world + 1) / 2 - one number the driver can check against --gpus
@@ -657,6 +688,13 @@ def main():
     ap.add_argument("--no-probe", action="store_true")
     ap.add_argument("--probe-all", action="store_true", help="bracket every GEMM launch with events, not only forward / dgrad")
     ap.add_argument("--no-secondary", action="store_true", help="skip the secondary workloads")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: roofline probes in the primary workload's timed steps, replay_check, "
+                         "the secondary workloads and the CPU baseline (--no-probe / --no-secondary / --no-cpu-baseline still drop "
+                         "theirs); without it the run times the primary workload and prints the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned to its caller - loss, PF_L1, KL, grad_norm and the updated "
+                         "parameters (a fixed seeded sample beyond 4 Mi values) - as DIR/<name>.npy in float32")
     args = ap.parse_args()
 
     import npvp_amd
@@ -670,10 +708,13 @@ def main():
     torch.cuda.set_device(local)
     dev = torch.device("cuda", local)
 
-    main_res = run_workload(args.workload, args.steps, args.warmup, args, rank, world, dev, probe=not args.no_probe, mode=args.mode, check=True)
+    main_res = run_workload(args.workload, args.steps, args.warmup, args, rank, world, dev, probe=args.full and not args.no_probe,
+                            mode=args.mode, check=args.full, dump=args.dump_outputs is not None and rank == 0)
+    if main_res["outputs"] is not None:
+        write_outputs(main_res["outputs"], args.dump_outputs)
 
     secondary, detail, scaling_dp, modes, strong = {}, {}, None, {}, None
-    sec_ok = not args.no_secondary and not args.graph and args.flavour == "predictor"
+    sec_ok = args.full and not args.no_secondary and not args.graph and args.flavour == "predictor"
     if sec_ok and (args.workload == "c2" or world > 1):
         sec_steps, sec_warm = max(4, args.steps // 2), min(3, args.warmup) or 1
 
@@ -757,7 +798,7 @@ def main():
                "secondary_mode": modes or None, "scaling_dp": scaling_dp, "strong_scaling": strong, "dp": r.get("dp"),
                "replay_check": r.get("replay_check"), "graph_nodes": r.get("graph_nodes"), "graph_packet_capture": npvp_amd.graph_packet_capture(),
                "host": dict(zip(("cpu", "cores"), host_cpu()))}
-        if world == 1 and not args.no_cpu_baseline and args.flavour == "predictor":
+        if world == 1 and args.full and not args.no_cpu_baseline and args.flavour == "predictor":
             log("timing the CPU oracle on a bounded sample ...")
             res["cpu_baseline"] = cpu_baseline(args.workload)
         print(json.dumps(res), flush=True)

@@ -3,7 +3,7 @@
 for W in c2 c4; do
   for PR in "--no-probe" ""; do
     echo "== $W --graph $PR"
-    python3 bench.py --workload $W --graph --steps 10 --warmup 3 --no-secondary --no-cpu-baseline $PR > /tmp/gp.json 2> /tmp/gp.log
+    python3 bench.py --workload $W --graph --steps 10 --warmup 3 --no-secondary --no-cpu-baseline --full $PR > /tmp/gp.json 2> /tmp/gp.log
     grep -a "timed steps\|probe " /tmp/gp.log | cut -c1-230
     grep -aq "timed steps" /tmp/gp.log || tail -8 /tmp/gp.log
     python3 -c "

@@ -11,7 +11,7 @@ cd /tmp && export TMPDIR=/tmp
 BENCH="python3 $ROOT/bench.py --steps 3 --warmup 2 --no-secondary --no-cpu-baseline --no-probe"
 
 echo "[1] un-profiled bench (the record the kernel stats are read beside)"
-python3 $ROOT/bench.py --steps 10 --warmup 3 --no-secondary --no-cpu-baseline > "$OUT/bench_c2.json" 2> "$OUT/bench_c2.err"
+python3 $ROOT/bench.py --steps 10 --warmup 3 --no-secondary --no-cpu-baseline --full > "$OUT/bench_c2.json" 2> "$OUT/bench_c2.err"
 tail -2 "$OUT/bench_c2.err"
 
 echo "[2] kernel trace"

@@ -12,7 +12,7 @@ QUIET="--no-secondary --no-cpu-baseline --no-probe"
 for STEP in "$@"; do
 case "$STEP" in
 bench)      # the default command, as the driver runs it
-  python3 $ROOT/bench.py --steps 20 --warmup 5 > "$OUT/bench_default.json" 2> "$OUT/bench_default.err" || exit 1
+  python3 $ROOT/bench.py --steps 20 --warmup 5 --full > "$OUT/bench_default.json" 2> "$OUT/bench_default.err" || exit 1
   tail -c 1500 "$OUT/bench_default.json" ;;
 mfma)       # BASELINE's "MFMA util %": one --pmc pass per workload, the bench record beside it for the unprofiled step time
   for W in c2p c2; do

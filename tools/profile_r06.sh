@@ -13,7 +13,7 @@ DP1="env RANK=0 WORLD_SIZE=1 LOCAL_RANK=0 MASTER_ADDR=127.0.0.1 MASTER_PORT=2955
 for STEP in "$@"; do
 case "$STEP" in
 bench)      # the default command, as the driver runs it
-  python3 $ROOT/bench.py --steps 20 --warmup 5 > "$OUT/bench_default.json" 2> "$OUT/bench_default.err" || exit 1
+  python3 $ROOT/bench.py --steps 20 --warmup 5 --full > "$OUT/bench_default.json" 2> "$OUT/bench_default.err" || exit 1
   tail -c 1500 "$OUT/bench_default.json" ;;
 dptrace)    # the data-parallel c4 shard step on ONE RCCL rank: eager (two streams + side stream) and replayed as graph segments
   export RANK=0 WORLD_SIZE=1 LOCAL_RANK=0 MASTER_ADDR=127.0.0.1 MASTER_PORT=29551 NPVP_DP_FORCE=1 NPVP_DIST_BACKEND=nccl
