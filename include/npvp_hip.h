@@ -424,6 +424,45 @@ int npvp_bias_act(const float* x, const float* bias, const float* residual, floa
                   int layout, int act, npvp_stream_t stream);
 int npvp_act_bwd(const float* g, const float* y, float* dx, long long n, int act, npvp_stream_t stream);
 
+/* ---- Stage-1 autoencoder training (csrc/ae_train.hip): LitAE.training_step / shared_step (ref/models/ResNetAutoEncoder.py:13-49)
+ * through ResnetEncoder / ResnetDecoder (ref :51-204) and NonLocalAttenion2D (ref/models/submodules.py:98-176); the convolutions
+ * stay MIOpen's.  Every entry point is deterministic (fixed-order sums, no atomics) and needs no zero-filled buffer.
+ * BatchNorm2d in training mode + ReLU (+ skip-add), replacing `norm_layer(c), nn.ReLU(True)` of ref :76-130 / :168-175 / :239-249
+ * and the `+ x` of ref/models/submodules.py:80-93 / ResNetAutoEncoder.py:259-261:
+ *   layout 0: x [outer = N*H*W][inner = C] (channels-last), C a power of two in [4, 1024]; layout 1: x [outer = N*C][inner = H*W],
+ *   H*W % 4 == 0.  Buffers 16-byte aligned.  workspace >= npvp_bn_workspace_bytes(C).
+ * bn_stats: sums[2][C] (double) = per-channel [sum x, sum x^2]  (a data-parallel caller all-reduces these and n, then applies);
+ * bn_act_apply: mean / rstd from sums over `count` elements per channel (sums == NULL: from running_mean / running_var, eval mode),
+ *   running statistics updated in place as torch does (momentum, unbiased variance; NULL = not tracked), then
+ *   y = act((x - mean) rstd w + b) + residual  (act 0 none, 1 ReLU; residual nullable); mean / rstd [C] are saved for the backward;
+ * bn_act_bwd: g' = g * act'(.) (the ReLU mask recomputed from x with the forward's arithmetic), dw = sum g' xhat, db = sum g',
+ *   dx = w rstd (g' - db/n - xhat dw/n) (train = 1) or w rstd g' (train = 0: running statistics).  The skip-add's gradient is g itself. */
+int npvp_bn_workspace_bytes(int C);
+int npvp_bn_stats(const float* x, long long outer, long long inner, int C, int layout, double* sums, void* workspace, long long ws_bytes,
+                  npvp_stream_t stream);
+int npvp_bn_act_apply(const float* x, const float* w, const float* b, const float* residual, const double* sums, long long count,
+                      float eps, float momentum, float* running_mean, float* running_var, long long outer, long long inner, int C,
+                      int layout, int act, float* y, float* mean, float* rstd, npvp_stream_t stream);
+int npvp_bn_act_bwd(const float* g, const float* x, const float* mean, const float* rstd, const float* w, const float* b, long long outer,
+                    long long inner, int C, int layout, int act, int train, float* dx, float* dw, float* db, void* workspace,
+                    long long ws_bytes, npvp_stream_t stream);
+/* ReflectionPad2d(P) (ref/models/ResNetAutoEncoder.py:72, :187, :234-236): layout 1 x [planes = N*C][H][W] -> y [planes][H+2P][W+2P];
+ * layout 0 x [planes = N][H][W][C] -> y [N][H+2P][W+2P][C].  backward = 1: x is the padded gradient, y the input gradient, each
+ * input pixel the fixed-order sum of the padded pixels that read it (no atomics).  1 <= P < H, W. */
+int npvp_reflect_pad(const float* x, float* y, int planes, int H, int W, int C, int P, int layout, int backward, npvp_stream_t stream);
+/* Non-local attention core of NonLocalAttenion2D.forward (ref/models/submodules.py:150-170): o = softmax(q k^T) v per frame, scores
+ * NOT scaled, k / v = 2x2 max-pool (stride 2) of the projections over the H x W grid; F frames of H*W rows each.  q [F*H*W][ldq],
+ * k [F*H*W][ldk] (first A columns), v [F*H*W][ldv] (first V columns) are the UNPOOLED projections; o [F*H*W][ldo]; lse [F*H*W] is
+ * saved for the backward.  (A, V) in {(8,32), (16,64), (32,128), (64,256)} (C = 64..512, a = C/8, v = C/2), H even, W a power of
+ * two, H*W in {4096, 1024, 256, 64} respectively (the grids of the five AE configs).  The score matrix stays on chip.
+ * bwd: dq, and dk / dv of the unpooled projections: each window's gradient at its arg-max (first maximum in row-major order, as torch),
+ * 0 at the other three positions.  D [2][F*H*W] is scratch (rowsum(go * o) and 1 / rowsum(P), summed in double).  dq / dk / dv may be column slices of one buffer. */
+int npvp_nonlocal_attn_fwd(const float* q, long long ldq, const float* k, long long ldk, const float* v, long long ldv, float* o,
+                           long long ldo, float* lse, int F, int H, int W, int A, int V, npvp_stream_t stream);
+int npvp_nonlocal_attn_bwd(const float* q, long long ldq, const float* k, long long ldk, const float* v, long long ldv, const float* go,
+                           long long ldgo, const float* lse, float* D, float* dq, long long lddq,
+                           float* dk, long long lddk, float* dv, long long lddv, int F, int H, int W, int A, int V, npvp_stream_t stream);
+
 /* ---- the data-parallel exchange: all-reduce(mean) of the parameter gradients, RCCL over xGMI, one process per GPU.
  * Replaces what the reference gets from Lightning's DDP strategy (ref/train_Predictor_lightning.py:40-42: strategy = 'ddp' over
  * `devices` GPUs) for a host without torch.distributed.  Protocol: rank 0 calls npvp_dp_unique_id and carries the 128

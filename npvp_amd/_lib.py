@@ -111,6 +111,14 @@ SIGNATURES = {
     "npvp_u8hwc_to_f32chw": (c_int, [c_p, c_p, c_ll, c_int, c_int, c_int, c_p, c_p, c_p]),
     "npvp_bias_act": (c_int, [c_p, c_p, c_p, c_p, c_ll, c_ll, c_int, c_int, c_int, c_p]),
     "npvp_act_bwd": (c_int, [c_p, c_p, c_p, c_ll, c_int, c_p]),
+    "npvp_bn_workspace_bytes": (c_int, [c_int]),
+    "npvp_bn_stats": (c_int, [c_p, c_ll, c_ll, c_int, c_int, c_p, c_p, c_ll, c_p]),
+    "npvp_bn_act_apply": (c_int, [c_p, c_p, c_p, c_p, c_p, c_ll, c_f, c_f, c_p, c_p, c_ll, c_ll, c_int, c_int, c_int, c_p, c_p, c_p, c_p]),
+    "npvp_bn_act_bwd": (c_int, [c_p, c_p, c_p, c_p, c_p, c_p, c_ll, c_ll, c_int, c_int, c_int, c_int, c_p, c_p, c_p, c_p, c_ll, c_p]),
+    "npvp_reflect_pad": (c_int, [c_p, c_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_p]),
+    "npvp_nonlocal_attn_fwd": (c_int, [c_p, c_ll, c_p, c_ll, c_p, c_ll, c_p, c_ll, c_p, c_int, c_int, c_int, c_int, c_int, c_p]),
+    "npvp_nonlocal_attn_bwd": (c_int, [c_p, c_ll, c_p, c_ll, c_p, c_ll, c_p, c_ll, c_p, c_p, c_p, c_ll, c_p, c_ll, c_p, c_ll, c_int, c_int,
+                                       c_int, c_int, c_int, c_p]),
     "npvp_ssim_per_image": (c_int, [c_p, c_p, c_int, c_int, c_int, c_int, c_p, c_int, c_p, c_p, c_ll, c_p]),
 }
 

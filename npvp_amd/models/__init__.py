@@ -5,3 +5,4 @@ from .VidHRFormer import (VidHRformerDecoderNAR, VidHRFormerEncoder, VidHRFormer
 from .submodules import CoorGenerator, NRMLP, PosFeatFuser, EventEncoder
 from .Predictor import Predictor
 from .ResNetAutoEncoder import ResnetEncoder, ResnetDecoder, ResnetBlock, Factorized3DConvAttn, NonLocalAttenion2D, build_frozen_autoencoder, to_device_layout
+from .ae_train import build_autoencoder, prepare_trainable_autoencoder

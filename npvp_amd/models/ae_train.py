@@ -1,0 +1,147 @@
+"""Trainable Stage-1 autoencoder (LitAE, ref/models/ResNetAutoEncoder.py:13-49): the same ResnetEncoder / ResnetDecoder modules, with
+the same state-dict keys, run through the HIP ops of csrc/ae_train.hip instead of stock torch:
+  [pad] conv [BatchNorm2d [ReLU]] [+ skip]  ->  ops.reflect_pad, the convolution (MIOpen), ops.bn_act_train (statistics + one apply
+                                               pass, skip-add fused)
+  NonLocalAttenion2D                        ->  one GEMM for [Wq | Wk | Wv] (ops.linear), ops.nonlocal_attn_packed (pooling fused, no
+                                               score matrix in HBM), out_proj (ops.linear), ops.bn_act_train + ReLU, x + gamma * h
+`prepare_trainable_autoencoder` binds these forwards to the two module INSTANCES; the classes, their forward methods and the frozen
+Stage-2 path (build_frozen_autoencoder / fuse_frozen_autoencoder) are untouched.
+"""
+import types
+
+import torch
+import torch.nn as nn
+
+from .. import ops
+from .ResNetAutoEncoder import ResnetEncoder, ResnetDecoder, Factorized3DConvAttn, NonLocalAttenion2D, ResnetBlock
+
+
+def build_autoencoder(AE, img_channels):
+    """(encoder, decoder) as LitAE.__init__ builds them (ref/models/ResNetAutoEncoder.py:14-19) from the `AE:` section of a reference
+    YAML: parameters require grad, train mode."""
+    enc = ResnetEncoder(img_channels, ngf=AE['ngf'], n_downsampling=AE['n_downsampling'], num_res_blocks=AE['num_res_blocks'],
+                        norm_layer=nn.BatchNorm2d, norm_layer1d=nn.BatchNorm1d, learn_3d=AE['learn_3d'])
+    dec = ResnetDecoder(img_channels, ngf=AE['ngf'], n_downsampling=AE['n_downsampling'], out_layer=AE['out_layer'],
+                        norm_layer=nn.BatchNorm2d)
+    return enc.train(), dec.train()
+
+
+def _bn(bn, x, act, residual=None):
+    """BatchNorm2d (+ ReLU) (+ residual) with nn.BatchNorm2d's own mode logic (ref: torch.nn.modules.batchnorm._BatchNorm.forward)"""
+    if bn.training and bn.track_running_stats and bn.num_batches_tracked is not None:
+        bn.num_batches_tracked.add_(1)
+    train = bn.training or bn.running_mean is None
+    w = bn.weight if bn.weight is not None else torch.ones(bn.num_features, device=x.device)
+    b = bn.bias if bn.bias is not None else torch.zeros(bn.num_features, device=x.device)
+    return ops.bn_act_train(x, w, b, bn.running_mean, bn.running_var, bn.momentum, bn.eps, act, train, residual)
+
+
+def _pad_size(m):
+    p = m.padding
+    if len(set(p)) != 1:
+        raise NotImplementedError("ReflectionPad2d with unequal sides")
+    return p[0]
+
+
+def _run_seq(seq, x, residual=None):
+    """Sequential of [ReflectionPad2d] conv [BatchNorm2d] [ReLU] groups (and a final Tanh / Sigmoid); `residual` is added to the
+    output of the last module (fused into its BatchNorm pass when it ends in one)"""
+    mods, i = list(seq), 0
+    while i < len(mods):
+        m = mods[i]
+        if isinstance(m, nn.ReflectionPad2d):
+            x = ops.reflect_pad(x, _pad_size(m)); i += 1
+        elif isinstance(m, (nn.Conv2d, nn.ConvTranspose2d)):
+            x = m(x); i += 1
+        elif isinstance(m, nn.BatchNorm2d):
+            act = 1 if i + 1 < len(mods) and isinstance(mods[i + 1], nn.ReLU) else 0
+            last = i + 1 + act == len(mods)
+            x = _bn(m, x, act, residual if last else None)
+            if last:
+                residual = None
+            i += 1 + act
+        elif isinstance(m, nn.ReLU):
+            x = torch.relu(x); i += 1
+        elif isinstance(m, (nn.Tanh, nn.Sigmoid, nn.Dropout)):
+            x = m(x); i += 1
+        else:
+            raise NotImplementedError(f"trainable autoencoder: {type(m).__name__} is not on the shipped configs' path")
+    return x if residual is None else x + residual
+
+
+def _attn(a, x):
+    """NonLocalAttenion2D.forward (ref/models/submodules.py:150-176) on the HIP path"""
+    N, C, H, W = x.shape
+    A, V = a.attn_dim, a.value_dim
+    tok = x.permute(0, 2, 3, 1).reshape(N * H * W, C)               # a view when x is channels_last
+    ws = [a.Wq.weight, a.Wk.weight, a.Wv.weight]
+    bs = [a.Wq.bias, a.Wk.bias, a.Wv.bias] if a.bias else None
+    width = 2 * A + V
+    pad = -width % 32                                                # the GEMM's dgrad wants an inner dimension % 32 == 0
+    if pad:
+        ws = ws + [torch.zeros(pad, C, device=x.device)]
+        if bs is not None:
+            bs = bs + [torch.zeros(pad, device=x.device)]
+    qkv = ops.linear(tok, torch.cat(ws, 0), torch.cat(bs, 0) if bs is not None else None)
+    o = ops.nonlocal_attn_packed(qkv, N, H, W, A, V)
+    out = ops.linear(o, a.out_proj.weight, a.out_proj.bias).view(N, H, W, C).permute(0, 3, 1, 2)
+    relu = isinstance(a.activ_func, nn.ReLU)
+    if isinstance(a.norm_func, nn.BatchNorm2d):
+        h = _bn(a.norm_func, out, 1 if relu else 0)
+        if not relu:
+            h = a.activ_func(h)
+    else:
+        h = a.activ_func(a.norm_func(out))
+    return x + a.gamma * h
+
+
+def _fact(m, x):
+    """Factorized3DConvAttn.forward with learn_3d=False (ref/models/submodules.py:80-95)"""
+    if m.conv_first:
+        return _attn(m.attn2d, _run_seq(m.spatial_conv, x, residual=x)) + x
+    y = _attn(m.attn2d, x)
+    return _run_seq(m.spatial_conv, y, residual=y) + x
+
+
+def _encoder_forward(enc, x):
+    N, T = x.shape[:2]
+    x = x.flatten(0, 1)
+    if getattr(enc, "_npvp_channels_last", False):
+        x = x.contiguous(memory_format=torch.channels_last)
+    x = _run_seq(enc.block1, _run_seq(enc.block0, x))
+    for i in range(1, enc.n_downsampling):
+        x = _run_seq(getattr(enc, f'block{i + 1}_conv'), _fact(getattr(enc, f'block{i + 1}_3dConvAttn'), x))
+    for i in range(enc.num_res_blocks):
+        rb = getattr(enc, f'res_conv_{i}')
+        x = _fact(getattr(enc, f'res_3dConvAttn_{i}'), x)
+        x = _run_seq(rb.conv_block, x, residual=x)
+    x = torch.relu(x)
+    return x.reshape(N, T, *x.shape[1:])
+
+
+def _decoder_forward(dec, x):
+    N, T = x.shape[:2]
+    x = x.flatten(0, 1)
+    if not x.is_contiguous():
+        x = x.contiguous()
+    y = _run_seq(dec.model, x)
+    return y.reshape(N, T, *y.shape[1:])
+
+
+def prepare_trainable_autoencoder(enc, dec, channels_last=True):
+    """Route the pair's forward through the HIP training ops (in place, on these two instances); state-dict keys are unchanged.
+    Train mode: batch statistics (running statistics updated); eval mode: running statistics.  channels_last: the encoder's
+    activations run in torch.channels_last memory (BatchNorm layout 0; the attention's token matrix is then a view), the decoder's
+    stay NCHW (layout 1), as in the frozen path (to_device_layout).  Returns (enc, dec)."""
+    if not isinstance(enc, ResnetEncoder) or not isinstance(dec, ResnetDecoder):
+        raise TypeError("prepare_trainable_autoencoder: (ResnetEncoder, ResnetDecoder) expected")
+    for m in list(enc.modules()) + list(dec.modules()):
+        if isinstance(m, Factorized3DConvAttn) and not isinstance(m.spatial_conv, nn.Sequential):
+            raise RuntimeError("prepare_trainable_autoencoder: this pair has been fused for the frozen Stage-2 path")
+        if isinstance(m, nn.BatchNorm2d) and m.momentum is None:
+            raise NotImplementedError("prepare_trainable_autoencoder: BatchNorm2d(momentum=None) is not supported")
+    enc.forward = types.MethodType(_encoder_forward, enc)
+    dec.forward = types.MethodType(_decoder_forward, dec)
+    enc._npvp_trainable = dec._npvp_trainable = True
+    enc._npvp_channels_last = bool(channels_last)
+    return enc, dec

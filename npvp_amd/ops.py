@@ -1963,3 +1963,186 @@ class _BiasAct(torch.autograd.Function):
 
 def bias_act(x, bias, act=0, residual=None):
     return _BiasAct.apply(x, bias, residual, act)
+
+
+# --------------------------------------------------------------------------- Stage-1 autoencoder training (csrc/ae_train.hip)
+def _nchw_layout(x, what):
+    """(outer, inner, layout) of an (N,C,H,W) tensor in channels_last (layout 0: rows [N*H*W][C]) or contiguous (layout 1: planes)
+    memory; anything else is made contiguous first by the caller"""
+    N, C, H, W = x.shape
+    if x.is_contiguous(memory_format=torch.channels_last) and not x.is_contiguous():
+        return N * H * W, C, 0
+    if x.is_contiguous():
+        return N * C, H * W, 1
+    raise RuntimeError(f"{what}: x must be contiguous or channels_last")
+
+
+def _like_layout(t, layout):
+    return t.contiguous(memory_format=torch.channels_last if layout == 0 else torch.contiguous_format)
+
+
+class _BnActTrain(torch.autograd.Function):
+    """BatchNorm2d (batch statistics in training, running statistics in eval) -> act (0 none, 1 ReLU) [-> + residual] as one
+    statistics pass and one apply pass forward, one sum pass and one dx pass backward (npvp_bn_*)."""
+
+    @staticmethod
+    def forward(ctx, x, w, b, residual, running_mean, running_var, momentum, eps, act, train):
+        remember(ctx)
+        _chk(x, w, b, residual, running_mean, running_var)
+        if x.dim() != 4:
+            raise RuntimeError("bn_act_train: x must be (N, C, H, W)")
+        if not (x.is_contiguous() or x.is_contiguous(memory_format=torch.channels_last)):
+            x = x.contiguous()
+        outer, inner, layout = _nchw_layout(x, "bn_act_train")
+        C = x.shape[1]
+        if w.shape != (C,) or b.shape != (C,):
+            raise RuntimeError(f"bn_act_train: weight / bias must be ({C},)")
+        if residual is not None:
+            if residual.shape != x.shape:
+                raise RuntimeError("bn_act_train: residual shape differs from x")
+            residual = _like_layout(residual, layout)
+        if not train and running_mean is None:
+            raise RuntimeError("bn_act_train: eval mode needs running statistics")
+        L = lib()
+        y = torch.empty_like(x)
+        mean = torch.empty(C, dtype=torch.float32, device=x.device)
+        rstd = torch.empty_like(mean)
+        sums, count = None, 0
+        if train:
+            sums = torch.empty(2 * C, dtype=torch.float64, device=x.device)
+            ws, wsn = _ws(L.npvp_bn_workspace_bytes(C), x.device)
+            check(L.npvp_bn_stats(_ptr(x), outer, inner, C, layout, _ptr(sums), _ptr(ws), wsn, _stream()), "npvp_bn_stats")
+            count = outer * inner // C
+        upd = train and running_mean is not None
+        check(L.npvp_bn_act_apply(_ptr(x), _ptr(w), _ptr(b), _ptr(residual), _ptr(sums), count, float(eps), float(momentum or 0.0),
+                                  _ptr(running_mean) if upd or not train else None, _ptr(running_var) if upd or not train else None,
+                                  outer, inner, C, layout, act, _ptr(y), _ptr(mean), _ptr(rstd), _stream()), "npvp_bn_act_apply")
+        ctx.save_for_backward(x, w, b, mean, rstd)
+        ctx.act, ctx.train, ctx.layout, ctx.has_res = act, bool(train), layout, residual is not None
+        return y
+
+    @scoped
+    def backward(ctx, g):
+        x, w, b, mean, rstd = ctx.saved_tensors
+        _chk(g)
+        g = _like_layout(g, ctx.layout)
+        outer, inner, layout = _nchw_layout(x, "bn_act_train")
+        C = x.shape[1]
+        L = lib()
+        dx = torch.empty_like(x)
+        dw = torch.empty(C, dtype=torch.float32, device=x.device)
+        db = torch.empty_like(dw)
+        ws, wsn = _ws(L.npvp_bn_workspace_bytes(C), x.device)
+        check(L.npvp_bn_act_bwd(_ptr(g), _ptr(x), _ptr(mean), _ptr(rstd), _ptr(w), _ptr(b), outer, inner, C, layout, ctx.act,
+                                int(ctx.train), _ptr(dx), _ptr(dw), _ptr(db), _ptr(ws), wsn, _stream()), "npvp_bn_act_bwd")
+        return dx, dw, db, (g if ctx.has_res else None), None, None, None, None, None, None
+
+
+def bn_act_train(x, w, b, running_mean=None, running_var=None, momentum=0.1, eps=1e-5, act=0, train=True, residual=None):
+    """act(batch_norm(x)) (+ residual) for an (N,C,H,W) fp32 tensor, contiguous (NCHW planes) or channels_last (rows); running
+    statistics are updated in place in training mode (torch's momentum rule, unbiased variance)"""
+    if act not in (0, 1):
+        raise RuntimeError("bn_act_train: act must be 0 (none) or 1 (ReLU)")
+    if train and running_mean is not None and momentum is None:
+        raise RuntimeError("bn_act_train: momentum=None (cumulative average) is not supported")
+    if (running_mean is None) != (running_var is None):
+        raise RuntimeError("bn_act_train: running_mean and running_var go together")
+    return _BnActTrain.apply(x, w, b, residual, running_mean, running_var, momentum, eps, act, bool(train))
+
+
+_NL_SHAPES = {(8, 32), (16, 64), (32, 128), (64, 256)}
+
+
+class _NonLocalAttn(torch.autograd.Function):
+    """softmax(q k^T) v of NonLocalAttenion2D (unscaled scores, 2x2 max-pooled keys / values) from ONE projection tensor
+    qkv [F*H*W, ld] = [q | k | v | zero padding]; the gradient comes back in the same layout (npvp_nonlocal_attn_*)."""
+
+    @staticmethod
+    def forward(ctx, qkv, F, H, W, A, V):
+        remember(ctx)
+        _chk(qkv)
+        qkv = _c(qkv)
+        ld = qkv.shape[1]
+        o = torch.empty(F * H * W, V, dtype=torch.float32, device=qkv.device)
+        lse = torch.empty(F * H * W, dtype=torch.float32, device=qkv.device)
+        p = qkv.data_ptr()
+        check(lib().npvp_nonlocal_attn_fwd(p, ld, p + 4 * A, ld, p + 8 * A, ld, _ptr(o), V, _ptr(lse), F, H, W, A, V, _stream()),
+              "npvp_nonlocal_attn_fwd")
+        ctx.save_for_backward(qkv, lse)
+        ctx.dims = (F, H, W, A, V)
+        return o
+
+    @scoped
+    def backward(ctx, go):
+        qkv, lse = ctx.saved_tensors
+        F, H, W, A, V = ctx.dims
+        _chk(go)
+        go = _c(go)
+        ld = qkv.shape[1]
+        dqkv = torch.empty_like(qkv)
+        if ld > 2 * A + V:
+            dqkv[:, 2 * A + V:].zero_()
+        D = torch.empty(2 * F * H * W, dtype=torch.float32, device=qkv.device)
+        p, d = qkv.data_ptr(), dqkv.data_ptr()
+        check(lib().npvp_nonlocal_attn_bwd(p, ld, p + 4 * A, ld, p + 8 * A, ld, _ptr(go), V, _ptr(lse), _ptr(D),
+                                           d, ld, d + 4 * A, ld, d + 8 * A, ld, F, H, W, A, V, _stream()), "npvp_nonlocal_attn_bwd")
+        return dqkv, None, None, None, None, None
+
+
+def nonlocal_attn_packed(qkv, F, H, W, A, V):
+    """qkv [F*H*W, ld >= 2A+V] (columns q | k | v, k and v UNPOOLED) -> softmax(q pool(k)^T) pool(v)  [F*H*W, V]"""
+    if (A, V) not in _NL_SHAPES:
+        raise RuntimeError(f"nonlocal_attn: (attn dim, value dim) = ({A}, {V}) is not one of the AE configs' {sorted(_NL_SHAPES)}")
+    if H * W != {8: 4096, 16: 1024, 32: 256, 64: 64}[A] or H % 2 or W & (W - 1):
+        raise RuntimeError(f"nonlocal_attn: a {H}x{W} grid at C = {8 * A} is not one of the AE configs' (64x64 @ 64, 32x32 @ 128, "
+                           "16x16 @ 256, 8x8 @ 512)")
+    if qkv.dim() != 2 or qkv.shape[0] != F * H * W or qkv.shape[1] < 2 * A + V:
+        raise RuntimeError(f"nonlocal_attn: qkv must be [F*H*W, >= {2 * A + V}]")
+    return _NonLocalAttn.apply(qkv, F, H, W, A, V)
+
+
+def nonlocal_attn(q, k, v, H, W):
+    """q, k, v (F, H*W, a / a / v) - k and v the projections BEFORE the 2x2 max-pool - -> (F, H*W, v)"""
+    F, P, A = q.shape
+    V = v.shape[-1]
+    if k.shape != q.shape or v.shape[:2] != q.shape[:2] or P != H * W:
+        raise RuntimeError("nonlocal_attn: q / k (F, H*W, a), v (F, H*W, v)")
+    qkv = torch.cat([q.reshape(F * P, A), k.reshape(F * P, A), v.reshape(F * P, V)], 1)
+    return nonlocal_attn_packed(qkv, F, H, W, A, V).view(F, P, V)
+
+
+class _ReflectPad(torch.autograd.Function):
+    """ReflectionPad2d(P) forward, gather-form backward (npvp_reflect_pad)"""
+
+    @staticmethod
+    def forward(ctx, x, P):
+        remember(ctx)
+        _chk(x)
+        if x.dim() != 4:
+            raise RuntimeError("reflect_pad: x must be (N, C, H, W)")
+        if not (x.is_contiguous() or x.is_contiguous(memory_format=torch.channels_last)):
+            x = x.contiguous()
+        N, C, H, W = x.shape
+        if not (1 <= P < H and P < W):
+            raise RuntimeError(f"reflect_pad: padding {P} must be >= 1 and < the input's H, W ({H}, {W})")
+        layout = _nchw_layout(x, "reflect_pad")[2]
+        y = torch.empty((N, C, H + 2 * P, W + 2 * P), dtype=torch.float32, device=x.device,
+                        memory_format=torch.channels_last if layout == 0 else torch.contiguous_format)
+        planes = N if layout == 0 else N * C
+        check(lib().npvp_reflect_pad(_ptr(x), _ptr(y), planes, H, W, C, P, layout, 0, _stream()), "npvp_reflect_pad")
+        ctx.geo = (N, C, H, W, P, layout)
+        return y
+
+    @scoped
+    def backward(ctx, g):
+        N, C, H, W, P, layout = ctx.geo
+        _chk(g)
+        g = _like_layout(g, layout)
+        dx = torch.empty((N, C, H, W), dtype=torch.float32, device=g.device,
+                         memory_format=torch.channels_last if layout == 0 else torch.contiguous_format)
+        check(lib().npvp_reflect_pad(_ptr(g), _ptr(dx), N if layout == 0 else N * C, H, W, C, P, layout, 1, _stream()), "npvp_reflect_pad")
+        return dx, None
+
+
+def reflect_pad(x, P):
+    return _ReflectPad.apply(x, int(P))

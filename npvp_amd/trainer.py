@@ -748,3 +748,81 @@ class GraphedTrainStep:
             self.graph.replay()
         self.replays += 1
         return self.out
+
+
+# --------------------------------------------------------------------------- Stage 1: the autoencoder (LitAE)
+class AEPair(torch.nn.Module):
+    """LitAE's two children (ref/models/ResNetAutoEncoder.py:13-19): VPTR_Enc, VPTR_Dec.  Its parameters() are ordered encoder first,
+    decoder second - the order of LitAE.configure_optimizers (ref :46-49) - and its state_dict() keys are LitAE's."""
+
+    def __init__(self, enc, dec):
+        super().__init__()
+        self.VPTR_Enc, self.VPTR_Dec = enc, dec
+
+
+def ae_optimizer(enc, dec, lr=1e-4):
+    """LitAE.configure_optimizers (ref/models/ResNetAutoEncoder.py:46-49): Adam(enc + dec, lr=AE_lr, betas=(0.5, 0.999)), no clipping,
+    no scheduler - as FlatAdamW with weight_decay=0 (AdamW without decay is Adam's update).  The pair is kept as `opt.ae_pair`."""
+    pair = AEPair(enc, dec)
+    opt = FlatAdamW(pair, lr=lr, betas=(0.5, 0.999), eps=1e-8, weight_decay=0.0)
+    opt.ae_pair = pair
+    return opt
+
+
+def ae_train_step(enc, dec, opt, past_frames, future_frames):
+    """LitAE.training_step / shared_step (ref/models/ResNetAutoEncoder.py:27-44): x = cat(past, future, dim=1),
+    loss = L1(dec(enc(x)), x), backward, optimiser step.  `opt` from ae_optimizer; the pair prepared with
+    prepare_trainable_autoencoder.  Returns the loss as a device scalar."""
+    if not getattr(enc, "_npvp_trainable", False) or not getattr(dec, "_npvp_trainable", False):
+        raise RuntimeError("ae_train_step: call prepare_trainable_autoencoder(enc, dec) first")
+    with ops.use(opt.ctx):
+        ops.WgradStream.join()
+        opt.zero_grad()
+        x = torch.cat([past_frames, future_frames], dim=1).contiguous()
+        loss = ops.l1_mean(dec(enc(x)), x)
+        loss.backward()
+        opt.step()
+    return loss.detach()
+
+
+def ae_val_step(enc, dec, past_frames, future_frames):
+    """LitAE.validation_step (ref/models/ResNetAutoEncoder.py:32-35) as Lightning runs it: eval mode (BatchNorm on running
+    statistics), no_grad.  Returns (loss device scalar, reconstruction); the modules' modes are restored."""
+    modes = enc.training, dec.training
+    enc.eval(); dec.eval()
+    try:
+        with torch.no_grad():
+            x = torch.cat([past_frames, future_frames], dim=1).contiguous()
+            rec = dec(enc(x))
+            loss = ops.l1_mean(rec, x)
+    finally:
+        enc.train(modes[0]); dec.train(modes[1])
+    return loss, rec
+
+
+def save_ae_checkpoint(path, enc, dec, opt=None, epoch=0, global_step=0):
+    """A LitAE Lightning checkpoint: state_dict with VPTR_Enc. / VPTR_Dec. keys, optimizer_states = [Adam state in LitAE's parameter
+    order], epoch, global_step.  Loadable by load_ae_checkpoint, by load_lightning_checkpoint(path, None, enc, dec) (Stage 2's
+    Predictor.resume_AE_ckpt) and by the reference's LitAE."""
+    for role, m in (("enc", enc), ("dec", dec)):
+        _reject_fused_autoencoder(m, role)
+    pair = opt.ae_pair if opt is not None else AEPair(enc, dec)
+    if pair.VPTR_Enc is not enc or pair.VPTR_Dec is not dec:
+        raise RuntimeError("save_ae_checkpoint: the optimiser belongs to another pair")
+    sd = {k: v.detach().cpu().clone() for k, v in pair.state_dict().items()}
+    ck = {"state_dict": sd, "epoch": int(epoch), "global_step": int(global_step), "pytorch-lightning_version": "1.6.5",
+          "lr_schedulers": [], "loops": None}
+    if opt is not None:
+        ck["optimizer_states"] = [opt.state_dict(pair)]
+    torch.save(ck, path)
+
+
+def load_ae_checkpoint(path, enc, dec, opt=None, strict=True):
+    """Load a LitAE checkpoint (the reference's or save_ae_checkpoint's) into the pair and, if given, the ae_optimizer.
+    Returns (epoch, global_step)."""
+    epoch, step = load_lightning_checkpoint(path, None, enc, dec, strict=strict)
+    if opt is not None:
+        ck = torch.load(path, map_location="cpu", weights_only=True)
+        if ck.get("optimizer_states"):
+            opt.load_state_dict(ck["optimizer_states"][0], opt.ae_pair)
+    return epoch, step

@@ -1,0 +1,117 @@
+"""Stage-1 autoencoder training step (LitAE, ref/models/ResNetAutoEncoder.py:27-49): the HIP path (prepare_trainable_autoencoder +
+ae_train_step + FlatAdamW) against the stock path (the same modules in train mode on PyTorch-ROCm + torch.optim.Adam) at a config's
+real batch, on the same seeded weights and frames.  One JSON line: ms per step, peak allocated memory, loss of each path and their
+relative difference, and the algorithmic bytes of the new BatchNorm / attention kernels per step (for a share of the HBM peak from a
+separate `rocprofv3 --kernel-trace --stats` run).
+Usage: python tools/ae_train_bench.py --config {BAIR,KTH,KITTI} [--steps 10] [--warmup 3] [--batch B]"""
+import argparse
+import copy
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import torch                      # noqa: E402
+import torch.nn as nn             # noqa: E402
+
+# the AE: sections and Dataset batch / clip lengths of ref/configs/config_{BAIR,KTH,KITTI}_Autoencoder.yaml
+CONFIGS = {
+    "BAIR": dict(AE=dict(ngf=64, n_downsampling=3, num_res_blocks=2, out_layer='Tanh', learn_3d=False), ch=3, S=64, B=8, T=12),
+    "KTH": dict(AE=dict(ngf=64, n_downsampling=3, num_res_blocks=2, out_layer='Tanh', learn_3d=False), ch=1, S=64, B=8, T=20),
+    "KITTI": dict(AE=dict(ngf=32, n_downsampling=4, num_res_blocks=3, out_layer='Tanh', learn_3d=False), ch=3, S=128, B=16, T=9),
+}
+
+
+def algorithmic_bytes(enc, dec, frames, S):
+    """HBM bytes the new kernels must move per step at minimum (fp32): BatchNorm forward = stats read + apply read / write
+    (+ residual read), backward = sum pass (x, g) + dx pass (x, g, dx); attention = q, k, v read + o written forward, q, k, v, o,
+    dO read + dq, dk, dv written backward (the score matrix stays on chip).  The shapes come from a one-frame probe of COPIES in
+    eval mode: the modules passed in are left as they are (running statistics included)."""
+    enc, dec = copy.deepcopy(enc).eval(), copy.deepcopy(dec).eval()
+    from npvp_amd.models.ResNetAutoEncoder import NonLocalAttenion2D
+    # BatchNorm element counts from the conv outputs of a one-frame probe
+    counts = []
+
+    def bn_hook(m, inp, out):
+        counts.append(inp[0].numel())
+    hs = [m.register_forward_hook(bn_hook) for m in list(enc.modules()) + list(dec.modules()) if isinstance(m, nn.BatchNorm2d)]
+    att = []
+
+    def at_hook(m, inp, out):
+        N, C, H, W = inp[0].shape
+        att.append(H * W * (2 * (C // 8) + C // 2 + C // 2))
+    hs += [m.register_forward_hook(at_hook) for m in enc.modules() if isinstance(m, NonLocalAttenion2D)]
+    with torch.no_grad():
+        dec(enc(torch.zeros(1, 1, enc.block0[1].in_channels, S, S)))
+    for h in hs:
+        h.remove()
+    bn = 4 * frames * sum(n * (1 + 2) + n * 2 + n * 3 for n in counts)           # fwd 3 passes-worth, bwd 5 (residual not counted)
+    attn = 4 * frames * sum(e + 2 * e + e for e in att)                            # fwd q,k,v,o ; bwd q,k,v,o,dO + dq,dk,dv
+    return bn, attn
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--config", choices=sorted(CONFIGS), default="BAIR")
+    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--batch", type=int, default=None)
+    ap.add_argument("--paths", default="stock,hip")
+    a = ap.parse_args()
+    import npvp_amd
+    from oracle import ops as O
+    if not torch.cuda.is_available():
+        raise SystemExit("ae_train_bench needs an MI355X")
+    cfg = CONFIGS[a.config]
+    B, T, S, ch = a.batch or cfg["B"], cfg["T"], cfg["S"], cfg["ch"]
+    dev = "cuda:0"
+    enc0, dec0 = npvp_amd.build_autoencoder(cfg["AE"], ch)
+    O.key_hashed_fill(npvp_amd.AEPair(enc0, dec0), 1)
+    x = torch.tanh(O.seeded_randn((B, T, ch, S, S), 2)).to(dev)
+    past, fut = x[:, : T // 2].contiguous(), x[:, T // 2:].contiguous()
+    out = {"config": a.config, "batch": B, "frames_per_step": B * T, "res": S}
+    out["bn_bytes_per_step"], out["attn_bytes_per_step"] = algorithmic_bytes(enc0, dec0, B * T, S)
+    losses = {}
+    for path in a.paths.split(","):
+        enc, dec = copy.deepcopy(enc0), copy.deepcopy(dec0)
+        if path == "stock":
+            enc, dec = enc.to(dev), dec.to(dev)
+            opt = torch.optim.Adam(list(enc.parameters()) + list(dec.parameters()), lr=1e-4, betas=(0.5, 0.999))
+
+            def step():
+                opt.zero_grad()
+                xx = torch.cat([past, fut], 1)
+                loss = (dec(enc(xx)) - xx).abs().mean()
+                loss.backward()
+                opt.step()
+                return loss.detach()
+        else:
+            enc, dec = enc.to(dev).to(memory_format=torch.channels_last), dec.to(dev)
+            npvp_amd.prepare_trainable_autoencoder(enc, dec)
+            opt = npvp_amd.ae_optimizer(enc, dec, lr=1e-4)
+            step = lambda: npvp_amd.ae_train_step(enc, dec, opt, past, fut)
+        first = float(step())
+        losses[path] = first
+        for _ in range(max(a.warmup - 1, 0)):
+            step()
+        torch.cuda.synchronize()
+        torch.cuda.reset_peak_memory_stats()
+        t0 = time.perf_counter()
+        for _ in range(a.steps):
+            step()
+        torch.cuda.synchronize()
+        out[f"{path}_ms_per_step"] = round((time.perf_counter() - t0) * 1e3 / a.steps, 3)
+        out[f"{path}_peak_alloc_MiB"] = round(torch.cuda.max_memory_allocated() / 2 ** 20, 1)
+        out[f"{path}_loss_step1"] = first
+        del enc, dec, opt, step
+        torch.cuda.empty_cache()
+    if "stock" in losses and "hip" in losses:
+        out["loss_rel_diff"] = abs(losses["hip"] - losses["stock"]) / abs(losses["stock"])
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
