@@ -30,6 +30,7 @@ SIGNATURES = {
     "npvp_graph_node_counts": (c_ll, [c_p, c_p, c_p, c_int]),
     "npvp_gemm_workspace_bytes": (c_ll, [c_int, c_int, c_int]),
     "npvp_gemm_kernel_id": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
+    "npvp_gemm_route": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_p]),
     "npvp_gemm_f32": (c_int, [c_int, c_int, c_int, c_int, c_int, c_p, c_ll, c_p, c_ll, c_p, c_ll, c_p, c_int, c_p, c_p,
                               c_p, c_ll, c_f, c_int, c_int, c_int, c_p, c_u, c_f, c_int, c_p, c_p, c_int, c_p, c_p, c_p, c_p, c_p,
                               c_f, c_int, c_int, c_u, c_p, c_ll, c_p]),

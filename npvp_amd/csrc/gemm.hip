@@ -533,17 +533,44 @@ extern "C" int npvp_split_weights_batched(const void* desc, int count, hipStream
 // by it so that they line up with the per-kernel rows of a rocprofv3 trace): 0 gemm_f32_kernel, 1 gemm_split_db_kernel,
 // 2 gemm_wide_kernel (128 x 256 tiles), 3 gemm_wgrad_wide_kernel, 4 gemm_wide_kernel's 128 x 128 instantiation.  has_planes = b_pre
 // will be passed.
+struct GemmRoute { int id, variant, splits, steps; };
+static GemmRoute plan_route(int a_kc, int b_kc, int M, int N, int K, int precision, bool has_planes, bool plain_epilogue);
+
 extern "C" int npvp_gemm_kernel_id(int a_kc, int b_kc, int M, int N, int K, int precision, int has_planes) {
-  if (precision == 0) return 0;
-  if (precision == 6) {
-    if (a_kc && has_planes && gemm_f16_variant(M, N, K)) return gemm_f16_variant(M, N, K) == 1 ? 5 : 7;
-    if (!a_kc && !b_kc && f16_wgrad_splits(M, N, K) > 0) return 6;
-    return 1;
+  return plan_route(a_kc, b_kc, M, N, K, precision, has_planes != 0, true).id;
+}
+
+// The whole route of a launch (include/npvp_hip.h): the conditions of npvp_gemm_f32 below in the order it tests them, over the same
+// helpers (pick_splits, gemm_f16_variant, f16_wgrad_splits, gemm_wide_variant, wide_wgrad_splits), for a caller that hands over every
+// amax slot precision 6 asks for and a workspace of npvp_gemm_workspace_bytes.  npvp_gemm_kernel_id and npvp_gemm_route both answer
+// from it: one copy of the rules beside the dispatcher's own.
+static GemmRoute plan_route(int a_kc, int b_kc, int M, int N, int K, int precision, bool has_planes, bool plain_epilogue) {
+  const bool want_h = precision == 6;
+  if (want_h) precision = 4;
+  int splits = pick_splits(M, N, K);
+  if (splits > 1 && !plain_epilogue) splits = 1;
+  const bool planes_ok = has_planes && a_kc && K % 16 == 0 && N % 8 == 0;
+  int id = precision == 0 ? 0 : 1, variant = 0;
+  const int step = precision == 0 ? BK : 16;
+  if (want_h && planes_ok && gemm_f16_variant(M, N, K)) {
+    variant = gemm_f16_variant(M, N, K); id = variant == 1 ? 5 : 7; splits = 1;
+  } else if (want_h && !a_kc && !b_kc && plain_epilogue && f16_wgrad_splits(M, N, K) > 0) {
+    id = 6; splits = f16_wgrad_splits(M, N, K);
+  } else if (!want_h && precision == 4 && planes_ok && splits == 1 && gemm_wide_takes(M, N, K)) {
+    variant = gemm_wide_variant(M, N, K); id = variant == 1 ? 2 : 4;
+  } else if (precision == 4 && !a_kc && !b_kc && plain_epilogue && wide_wgrad_splits(M, N, K) > 0) {
+    id = 3; splits = wide_wgrad_splits(M, N, K);
   }
-  if (precision == 4 && a_kc && has_planes && pick_splits(M, N, K) == 1 && gemm_wide_takes(M, N, K))
-    return gemm_wide_variant(M, N, K) == 1 ? 2 : 4;
-  if (precision == 4 && !a_kc && !b_kc && wide_wgrad_splits(M, N, K) > 0) return 3;
-  return 1;
+  return GemmRoute{id, variant, splits, K / splits / step};
+}
+
+extern "C" int npvp_gemm_route(int a_kc, int b_kc, int M, int N, int K, int precision, int has_planes, int plain_epilogue, int* out4) {
+  NPVP_CHECK_ARG(out4 && M > 0 && N > 0 && K > 0, "gemm_route: empty problem or no result array");
+  NPVP_CHECK_ARG(precision == 0 || precision == 4 || precision == 5 || precision == 6, "gemm_route: precision must be 0, 4, 5 or 6");
+  NPVP_CHECK_ARG(K % BK == 0 && M % 4 == 0 && N % 4 == 0 && !(a_kc == 0 && b_kc == 1), "gemm_route: not a problem npvp_gemm_f32 accepts");
+  const GemmRoute r = plan_route(a_kc, b_kc, M, N, K, precision, has_planes != 0, plain_epilogue != 0);
+  out4[0] = r.id; out4[1] = r.variant; out4[2] = r.splits; out4[3] = r.steps;
+  return NPVP_OK;
 }
 
 // See include/npvp_hip.h for the contract.
