@@ -95,14 +95,19 @@ long long npvp_graph_node_counts(void* graph, long long* counts, long long* mems
 long long npvp_gemm_workspace_bytes(int M, int N, int K);
 /* which kernel npvp_gemm_f32 picks for a shape: 0 gemm_f32_kernel, 1 gemm_split_db_kernel (128 x 128 tiles), 2
  * gemm_wide_kernel<2,4,2,2> (128 x 256 tiles, weight planes by LDS-DMA), 3 gemm_wgrad_wide_kernel, 4 gemm_wide_kernel<2,2,2,2>
- * (the same kernel on 128 x 128 tiles: outputs too small to fill the chip with wide tiles).  Pure function (measurement aid). */
+ * (the same kernel on 128 x 128 tiles: outputs too small to fill the chip with wide tiles), 5 gemm_f16_kernel<2,4,2,2> (precision 6,
+ * 128 x 256 tiles), 6 gemm_wgrad_f16_kernel, 7 gemm_f16_kernel on smaller tiles.  The first word of npvp_gemm_route with a plain
+ * epilogue.  Pure function (measurement aid; ops.gemm also decides from it which amax slots to fill). */
 int npvp_gemm_kernel_id(int a_kc, int b_kc, int M, int N, int K, int precision, int has_planes);
-/* The whole route of a launch, for tests that must prove which leaf of the dispatcher they hit (tests/gemm_route_cases.py):
- * out4 = {kernel id as above (5 / 7 fp16 forward / dgrad, 6 fp16 weight gradient), tile variant (precision 6, ids 5 / 7: 1 = 128 x 256,
- * 2 = 128 x 128, 3 = 128 x 64, 4 = 64 x 128 tiles; precision 4, ids 2 / 4: 1 = 128 x 256, 2 = 128 x 128; 0 elsewhere), split-K count of
- * the launch given a workspace of npvp_gemm_workspace_bytes, K-steps per split of that kernel (steps of 16, of 32 for id 0)}.
- * plain_epilogue = no bias / activation / aux_out / residual / dropout (only such launches split K or take a weight-gradient kernel);
- * precision 6 assumes the amax slots are handed over.  With plain_epilogue = 1, out4[0] == npvp_gemm_kernel_id.  Pure function. */
+/* The whole route of a launch, for tests that must prove which leaf of the dispatcher they hit (tests/gemm_route_cases.py).  It is the
+ * dispatcher's own plan: npvp_gemm_f32 launches what the same planner returns for the facts of its arguments, this query reports what it
+ * returns for a caller that hands over a workspace of npvp_gemm_workspace_bytes and (precision 6) both amax slots, and asks for no frame
+ * statistics.  A caller that leaves the workspace or a slot out gets the same answer with that kernel's condition failing: precision 6
+ * without slots runs as precision 4 without planes, a split plan without its workspace runs unsplit on the 128 x 128 kernel.
+ * out4 = {kernel id as above, tile variant (precision 6, ids 5 / 7: 1 = 128 x 256, 2 = 128 x 128, 3 = 128 x 64, 4 = 64 x 128 tiles;
+ * precision 4, ids 2 / 4: 1 = 128 x 256, 2 = 128 x 128; 0 elsewhere), split-K count of the launch, K-steps per split of that kernel (steps
+ * of 16, of 32 for id 0)}.  plain_epilogue = no bias / activation / aux_out / residual / dropout (only such launches split K or take a
+ * weight-gradient kernel).  With plain_epilogue = 1, out4[0] == npvp_gemm_kernel_id.  Pure function. */
 int npvp_gemm_route(int a_kc, int b_kc, int M, int N, int K, int precision, int has_planes, int plain_epilogue, int* out4);
 int npvp_gemm_f32(int a_kc, int b_kc, int M, int N, int K, const float* A, long long lda, const float* B, long long ldb,
                   float* C, long long ldc, const float* bias, int act, const float* aux_in, float* aux_out,

@@ -331,19 +331,50 @@ inline int pick_colgroups(long long b_bytes, int tiles_m, int tiles_n) {
   return 1;
 }
 
-// gemm_wide.hip: 128 x 256 tile, 4 waves, A = fp32 [M][K] split on the fly, B = pre-split planes.  Returns true if it
-// took the launch (shape / operand requirements met), false if the caller should use the 128 x 128 kernel.
-bool launch_gemm_wide(GemmParams& p, hipStream_t stream);
-bool gemm_wide_takes(int M, int N, int K);
-int gemm_wide_variant(int M, int N, int K);      // 0 not taken, 1 = 128 x 256 tiles, 2 = 128 x 128 tiles
-// weight gradients (A = dy [K][M], B = x [K][N], both fp32): split count (0 = shape not taken) and launch; the caller sets
-// p.K / p.C / p.colsum for the split exactly as for the 128 x 128 kernel and runs the split-K reductions afterwards.
-int wide_wgrad_splits(int M, int N, int K);
-bool launch_gemm_wgrad_wide(GemmParams& p, int splits, hipStream_t stream);
+// bytes of a split-K workspace: the partial slabs [splits][M][N] followed by the column-sum partials [splits][M]
+inline long long splitk_workspace_bytes(int splits, int M, int N) {
+  return ((long long)splits * M * N + (long long)splits * M) * 4;
+}
+
+// aim a launch of `splits` K-slices of K / splits each at such a workspace (p.M / p.N are set): the kernels store raw partial tiles to
+// C + z*M*ldc and the column sums of slice z to colsum + z*M; whoever launched reduces them afterwards (splitk_reduce_body)
+inline void aim_at_workspace(GemmParams& p, int K, int splits, void* workspace, bool colsum) {
+  p.K = K / splits; p.C = (float*)workspace; p.ldc = p.N;
+  p.colsum = colsum ? (float*)workspace + (long long)splits * p.M * p.N : nullptr;
+}
+
+// split count of the two 128 x 256-tile weight-gradient kernels (A = dy [K][M], B = x [K][N], both fp32; K = token rows): ~512
+// workgroups (2 per CU; wide kernel: 256 / 128 workgroups gave a c2 step of 397 / 366 ms against 336 ms, 1024 / 2048 335.4 / 338.2
+// against 332.0; fp16 kernel: 256 / 384 / 1024 measured within noise of 512), >= 16 K-steps per split,
+// multiples of 8 from 8 on (one K-chunk per XCD).  0 = shape not taken: fewer than `min_rows` token rows.
+inline int wgrad_splits(int M, int N, int K, int min_rows) {
+  if ((K & 15) || M < 64 || N < 128 || K < min_rows) return 0;
+  const int tiles = ((M + 127) / 128) * ((N + 255) / 256);
+  int s = (512 + tiles - 1) / tiles;
+  const int maxs = K / 256;
+  if (s > maxs) s = maxs;
+  if (s > 64) s = 64;
+  if (s >= 8) s &= ~7;
+  while (s > 1 && (K % (s * 16)) != 0) --s;
+  return s < 1 ? 1 : s;
+}
+// gemm_wide.hip's bf16x6 kernel.  Below ~32 K token rows the 128 x 128 kernel (3 workgroups per CU, finer tiles) is as fast or faster:
+// measured 168 vs 166 TF at 20 480 rows, 144 vs 134 TF at 8 192 rows, 179 vs 189 TF at 114 688 rows.
+inline int wide_wgrad_splits(int M, int N, int K) { return wgrad_splits(M, N, K, 32768); }
+// gemm_f16.hip's fp16 kernel.  From 1 024 token rows (round 5; 4 096 before): the encoder of an 8-clip shard (1 024 - 2 048 rows) then
+// takes the chained / fused route instead of the 128 x 128 bf16 kernel + a split-K reduction launch + a column-sum launch per
+// weight gradient.
+inline int f16_wgrad_splits(int M, int N, int K) { return wgrad_splits(M, N, K, 1024); }
+
+// The launchers run what the planner of gemm.hip (plan_gemm) chose: they set p.tiles_* / p.colgroups for their tiles and launch.
+// gemm_wide.hip: 128 x 256 (variant 1) or 128 x 128 (variant 2) tiles, 4 waves, A = fp32 [M][K] split on the fly, B = pre-split planes
+int wide_variant(int M, int N, int K);           // 0 not taken (the 128 x 128 gemm_split_db_kernel runs)
+void launch_gemm_wide(GemmParams& p, int variant, hipStream_t stream);
+// weight gradients: p.splits K-slices; for more than one the caller has aimed p at the workspace and reduces afterwards
+void launch_gemm_wgrad_wide(GemmParams& p, hipStream_t stream);
 // gemm_f16.hip: the two-term fp16 forms of the three (precision 6)
-int gemm_f16_variant(int M, int N, int K);       // 0 not taken, 1 = 128 x 256 tiles, 2 = 128 x 128 tiles
-bool launch_gemm_f16(GemmParams& p, hipStream_t stream);
-int f16_wgrad_splits(int M, int N, int K);
-bool launch_gemm_wgrad_f16(GemmParams& p, int splits, hipStream_t stream);
+int gemm_f16_variant(int M, int N, int K);       // 0 not taken, 1 = 128 x 256 tiles, 2 = 128 x 128, 3 = 128 x 64, 4 = 64 x 128
+void launch_gemm_f16(GemmParams& p, int variant, hipStream_t stream);
+void launch_gemm_wgrad_f16(GemmParams& p, hipStream_t stream);
 
 }  // namespace npvp

@@ -505,7 +505,7 @@ using namespace npvp;
 extern "C" long long npvp_gemm_workspace_bytes(int M, int N, int K) {
   const int s = pick_splits(M, N, K), sw = wide_wgrad_splits(M, N, K), sh = f16_wgrad_splits(M, N, K);
   const int m = (s > sw ? s : sw) > sh ? (s > sw ? s : sw) : sh;
-  return m > 1 ? ((long long)m * M * N + (long long)m * M) * 4 : 0;
+  return m > 1 ? splitk_workspace_bytes(m, M, N) : 0;
 }
 
 // w [N][K] fp32 -> bf16 planes (3 terms each): F for y = x w^T (B operand [N][K]), D for dx = dy w (B operand [K][N]).
@@ -529,47 +529,86 @@ extern "C" int npvp_split_weights_batched(const void* desc, int count, hipStream
   return NPVP_OK;
 }
 
-// Which kernel npvp_gemm_f32 runs for a problem (a pure function of the shape; bench.py groups its live event-pair timings
-// by it so that they line up with the per-kernel rows of a rocprofv3 trace): 0 gemm_f32_kernel, 1 gemm_split_db_kernel,
-// 2 gemm_wide_kernel (128 x 256 tiles), 3 gemm_wgrad_wide_kernel, 4 gemm_wide_kernel's 128 x 128 instantiation.  has_planes = b_pre
-// will be passed.
-struct GemmRoute { int id, variant, splits, steps; };
-static GemmRoute plan_route(int a_kc, int b_kc, int M, int N, int K, int precision, bool has_planes, bool plain_epilogue);
+// ---- the dispatcher: ONE planner.  npvp_gemm_f32 launches the plan, npvp_gemm_route / npvp_gemm_kernel_id report it. ---------------
+// What the choice of kernel depends on, as plain facts:
+struct GemmFacts {
+  int a_kc, b_kc, M, N, K, precision;   // precision as the caller gave it: 6 = the fp16 kernels where they apply, else 4 WITHOUT planes
+  bool planes;                          // pre-split planes of B are handed over (b_pre)
+  bool plain;                           // no bias, act == 0, no aux_out, no residual, drop_p == 0
+  bool amax;                            // both operand amax slots are handed over (the fp16 kernels scale by them)
+  bool rowstats;                        // frame statistics are requested
+  long long ws_bytes;                   // split-K workspace available (0: none)
+};
+// Kernel id: 0 gemm_f32_kernel, 1 gemm_split_db_kernel (both 128 x 128 tiles), 2 / 4 gemm_wide_kernel on 128 x 256 / 128 x 128 tiles,
+// 3 gemm_wgrad_wide_kernel, 5 / 7 gemm_f16_kernel on 128 x 256 / smaller tiles, 6 gemm_wgrad_f16_kernel.  variant: the tile variant of
+// ids 2 / 4 (wide_variant) and 5 / 7 (gemm_f16_variant), else 0.  steps: K-steps per split (of 32 for id 0, of 16 otherwise).
+struct GemmPlan {
+  int id, variant, splits, steps;
+  bool planes;                          // the kernel reads the planes
+};
 
-extern "C" int npvp_gemm_kernel_id(int a_kc, int b_kc, int M, int N, int K, int precision, int has_planes) {
-  return plan_route(a_kc, b_kc, M, N, K, precision, has_planes != 0, true).id;
+static GemmPlan plan_gemm(const GemmFacts& f) {
+  const int M = f.M, N = f.N, K = f.K;
+  const bool want_h = f.precision == 6;
+  const int precision = want_h ? 4 : f.precision;
+  // the 128 x 128 kernels split K only with a plain epilogue and a workspace that holds whatever kernel the shape may run on
+  int s128 = pick_splits(M, N, K);
+  if (s128 > 1 && (!f.plain || f.ws_bytes < npvp_gemm_workspace_bytes(M, N, K))) s128 = 1;
+  const bool planes_ok = f.planes && f.a_kc && K % 16 == 0 && N % 8 == 0;
+  const bool wgrad = !f.a_kc && !f.b_kc && f.plain && !f.rowstats;
+  // a weight-gradient kernel takes its own split count s (0: shape not taken) if the workspace holds its slabs and column sums
+  auto fits = [&](int s) { return s == 1 || (s > 1 && f.ws_bytes >= splitk_workspace_bytes(s, M, N)); };
+  GemmPlan pl = {precision == 0 ? 0 : 1, 0, s128, 0, false};
+  int v = 0, s = 0;
+  if (want_h && planes_ok && f.amax && (v = gemm_f16_variant(M, N, K)) != 0) {
+    pl.id = v == 1 ? 5 : 7; pl.variant = v; pl.splits = 1; pl.planes = true;
+  } else if (want_h && wgrad && f.amax && fits(s = f16_wgrad_splits(M, N, K))) {
+    pl.id = 6; pl.splits = s;
+  } else if (!want_h && precision == 4 && planes_ok && s128 == 1 && (v = wide_variant(M, N, K)) != 0) {
+    pl.id = v == 1 ? 2 : 4; pl.variant = v; pl.planes = true;
+  } else if (precision == 4 && wgrad && fits(s = wide_wgrad_splits(M, N, K))) {
+    pl.id = 3; pl.splits = s;
+  } else {
+    // the 128 x 128 kernels; fp16 planes (want_h) are not what the bf16 kernel reads, and its rowstats instantiation stages none
+    pl.planes = !want_h && precision == 4 && planes_ok && s128 == 1 && !f.rowstats;
+  }
+  pl.steps = K / pl.splits / (precision == 0 ? BK : 16);
+  return pl;
 }
 
-// The whole route of a launch (include/npvp_hip.h): the conditions of npvp_gemm_f32 below in the order it tests them, over the same
-// helpers (pick_splits, gemm_f16_variant, f16_wgrad_splits, gemm_wide_variant, wide_wgrad_splits), for a caller that hands over every
-// amax slot precision 6 asks for and a workspace of npvp_gemm_workspace_bytes.  npvp_gemm_kernel_id and npvp_gemm_route both answer
-// from it: one copy of the rules beside the dispatcher's own.
-static GemmRoute plan_route(int a_kc, int b_kc, int M, int N, int K, int precision, bool has_planes, bool plain_epilogue) {
-  const bool want_h = precision == 6;
-  if (want_h) precision = 4;
-  int splits = pick_splits(M, N, K);
-  if (splits > 1 && !plain_epilogue) splits = 1;
-  const bool planes_ok = has_planes && a_kc && K % 16 == 0 && N % 8 == 0;
-  int id = precision == 0 ? 0 : 1, variant = 0;
-  const int step = precision == 0 ? BK : 16;
-  if (want_h && planes_ok && gemm_f16_variant(M, N, K)) {
-    variant = gemm_f16_variant(M, N, K); id = variant == 1 ? 5 : 7; splits = 1;
-  } else if (want_h && !a_kc && !b_kc && plain_epilogue && f16_wgrad_splits(M, N, K) > 0) {
-    id = 6; splits = f16_wgrad_splits(M, N, K);
-  } else if (!want_h && precision == 4 && planes_ok && splits == 1 && gemm_wide_takes(M, N, K)) {
-    variant = gemm_wide_variant(M, N, K); id = variant == 1 ? 2 : 4;
-  } else if (precision == 4 && !a_kc && !b_kc && plain_epilogue && wide_wgrad_splits(M, N, K) > 0) {
-    id = 3; splits = wide_wgrad_splits(M, N, K);
-  }
-  return GemmRoute{id, variant, splits, K / splits / step};
+// The queries answer for a caller that hands over every amax slot precision 6 asks for and a workspace of npvp_gemm_workspace_bytes,
+// and asks for no frame statistics (include/npvp_hip.h).  bench.py groups its live event-pair timings by the kernel id so that they
+// line up with the per-kernel rows of a rocprofv3 trace.
+static GemmPlan plan_query(int a_kc, int b_kc, int M, int N, int K, int precision, int has_planes, bool plain) {
+  return plan_gemm(GemmFacts{a_kc, b_kc, M, N, K, precision, has_planes != 0, plain, true, false, npvp_gemm_workspace_bytes(M, N, K)});
+}
+
+extern "C" int npvp_gemm_kernel_id(int a_kc, int b_kc, int M, int N, int K, int precision, int has_planes) {
+  return plan_query(a_kc, b_kc, M, N, K, precision, has_planes, true).id;
 }
 
 extern "C" int npvp_gemm_route(int a_kc, int b_kc, int M, int N, int K, int precision, int has_planes, int plain_epilogue, int* out4) {
   NPVP_CHECK_ARG(out4 && M > 0 && N > 0 && K > 0, "gemm_route: empty problem or no result array");
   NPVP_CHECK_ARG(precision == 0 || precision == 4 || precision == 5 || precision == 6, "gemm_route: precision must be 0, 4, 5 or 6");
   NPVP_CHECK_ARG(K % BK == 0 && M % 4 == 0 && N % 4 == 0 && !(a_kc == 0 && b_kc == 1), "gemm_route: not a problem npvp_gemm_f32 accepts");
-  const GemmRoute r = plan_route(a_kc, b_kc, M, N, K, precision, has_planes != 0, plain_epilogue != 0);
+  const GemmPlan r = plan_query(a_kc, b_kc, M, N, K, precision, has_planes, plain_epilogue != 0);
   out4[0] = r.id; out4[1] = r.variant; out4[2] = r.splits; out4[3] = r.steps;
+  return NPVP_OK;
+}
+
+// the second launch of a split-K plan: C (+)= alpha * the sum of p's slabs; a float4-aligned bias gradient rides along, any other
+// takes a launch of its own
+static int finish_splitk(const GemmParams& p, float* C, long long ldc, float* colsum_a, hipStream_t stream) {
+  const long long total4 = (long long)p.M * p.N / 4;
+  int blocks = (int)((total4 + 255) / 256); if (blocks > 2048) blocks = 2048;
+  const bool cs_here = colsum_a && ((uintptr_t)colsum_a % 16) == 0;
+  NPVP_LAUNCH(splitk_reduce_kernel, dim3(blocks), dim3(256), 0, stream, (const float*)p.C, C, p.M, p.N, ldc, p.splits, p.alpha,
+              p.accum, cs_here ? (const float*)p.colsum : nullptr, cs_here ? colsum_a : nullptr, p.c_amax);
+  NPVP_CHECK_LAUNCH();
+  if (colsum_a && !cs_here && launch_sum_rows(p.colsum, colsum_a, p.splits, p.M, p.M, stream, p.accum)) {
+    npvp_set_error("gemm: column-sum reduce launch failed");
+    return NPVP_ERR_LAUNCH;
+  }
   return NPVP_OK;
 }
 
@@ -590,7 +629,6 @@ extern "C" int npvp_gemm_f32(int a_kc, int b_kc, int M, int N, int K, const floa
   // precision 6 = fp16 two-term kernels where they apply (a row-major A with fp16 planes of B + both amax slots; weight
   // gradients with both amax slots), the three-term bf16 kernels WITHOUT planes everywhere else
   const bool want_h = precision == 6;
-  if (want_h) precision = 4;
   NPVP_CHECK_ARG(K % BK == 0, "gemm: K must be a multiple of 32");
   NPVP_CHECK_ARG(M % 4 == 0 && N % 4 == 0, "gemm: M and N must be multiples of 4");
   NPVP_CHECK_ARG(((uintptr_t)A % 16) == 0 && ((uintptr_t)B % 16) == 0 && ((uintptr_t)C % 16) == 0, "gemm: pointers must be 16-byte aligned");
@@ -605,128 +643,60 @@ extern "C" int npvp_gemm_f32(int a_kc, int b_kc, int M, int N, int K, const floa
   NPVP_CHECK_ARG(!colsum_a || a_kc == 0, "gemm: colsum_a is the column sum of a [K][M] operand (a_kc = 0)");
   NPVP_CHECK_ARG(!b_pre || ((uintptr_t)b_pre % 16) == 0, "gemm: b_pre must be 16-byte aligned");
 
-  GemmParams p;
-  p.A = A; p.B = B; p.C = C; p.bias = bias; p.residual = residual; p.aux_out = aux_out; p.aux_in = aux_in;
-  p.seed = seed; p.lda = lda; p.ldb = ldb; p.ldc = ldc; p.ldr = ldr; p.M = M; p.N = N; p.K = K; p.act = act;
-  p.drop = make_drop_spec(drop_p, salt, drop_mode, drop_g1, drop_g2);
   // row-group mask on operand A (see GemmParams::adrop): only the fp16 kernels implement it, and only with whole K-steps per group
   NPVP_CHECK_ARG(adrop_p >= 0.f && adrop_p < 0.5f, "gemm: adrop_p must be in [0, 0.5) (the masked operand must stay inside its amax scale)");
   NPVP_CHECK_ARG(adrop_p == 0.f || (seed && want_h && adrop_g1 > 0 && adrop_g2 > 0 && (a_kc || adrop_g1 % 16 == 0)),
                  "gemm: adrop needs precision 6, a device seed and (for a weight gradient) groups of a multiple of 16 rows");
+  NPVP_CHECK_ARG(!rowstats || ((precision == 4 || want_h) && a_kc && b_kc && M % 64 == 0 && N % 128 == 0 && act == 0 && !aux_out && !residual &&
+                               drop_p == 0.f && !accumulate),
+                 "gemm: rowstats needs the default (bf16x6) forward layout, M % 64 == 0, N % 128 == 0 and a bias-only epilogue");
+
+  const bool plain = !bias && act == 0 && !aux_out && !residual && drop_p == 0.f;
+  const GemmPlan plan = plan_gemm(GemmFacts{a_kc, b_kc, M, N, K, precision, b_pre != nullptr, plain,
+                                            a_amax && b_amax, rowstats != nullptr, workspace ? ws_bytes : 0});
+  NPVP_CHECK_ARG(adrop_p == 0.f || plan.id >= 5, "gemm: adrop was requested but this shape does not run on the fp16 kernels (npvp_gemm_kernel_id tells)");
+
+  GemmParams p;
+  p.A = A; p.B = B; p.bias = bias; p.residual = residual; p.aux_out = aux_out; p.aux_in = aux_in;
+  p.seed = seed; p.lda = lda; p.ldb = ldb; p.ldr = ldr; p.M = M; p.N = N; p.act = act;
+  p.drop = make_drop_spec(drop_p, salt, drop_mode, drop_g1, drop_g2);
   p.adrop = make_drop_spec(adrop_p, adrop_salt, 1, adrop_g1, adrop_g2);
   p.alpha = alpha;
-  p.tiles_m = (M + BM - 1) / BM; p.tiles_n = (N + BN - 1) / BN;
-  int splits = pick_splits(M, N, K);
-  const bool plain = !bias && act == 0 && !aux_out && !residual && drop_p == 0.f;
-  if (splits > 1 && (!plain || ws_bytes < npvp_gemm_workspace_bytes(M, N, K) || !workspace || (N % 4) != 0)) splits = 1;
-  p.splits = splits;
-  p.colsum = colsum_a;
   p.rowstats = rowstats;
   p.a_amax = a_amax; p.b_amax = b_amax; p.c_amax = c_amax; p.range_flag = range_flag;
   p.prev = ReduceJob{};
-  NPVP_CHECK_ARG(!rowstats || (precision == 4 && a_kc && b_kc && M % 64 == 0 && N % 128 == 0 && act == 0 && !aux_out && !residual &&
-                               drop_p == 0.f && !accumulate),
-                 "gemm: rowstats needs the default (bf16x6) forward layout, M % 64 == 0, N % 128 == 0 and a bias-only epilogue");
   p.accum = accumulate ? 1 : 0;
-  // pre-split B planes are only consumed by the bf16x6 kernels with a row-major A and an unsplit reduction
-  const void* b_pre_arg = b_pre;
-  p.b_pre = (precision == 4 && a_kc && splits == 1 && K % 16 == 0 && N % 8 == 0) ? b_pre : nullptr;
+  p.b_pre = plan.planes ? b_pre : nullptr;
   p.b_pre_plane = (long long)N * K;
-  b_pre = p.b_pre;
+  p.splits = plan.splits;
+  if (plan.splits > 1) aim_at_workspace(p, K, plan.splits, workspace, colsum_a != nullptr);
+  else { p.K = K; p.C = C; p.ldc = ldc; p.colsum = colsum_a; }
+  // the 128 x 128 kernels' tiling; the launchers of gemm_wide.hip / gemm_f16.hip set their own
+  p.tiles_m = (M + BM - 1) / BM; p.tiles_n = (N + BN - 1) / BN;
+  p.colgroups = (plan.id <= 1 && plan.splits == 1) ? pick_colgroups((long long)N * K * 4, p.tiles_m, p.tiles_n) : 1;
 
-  if (want_h) {
-    if (b_pre_arg && a_kc && K % 16 == 0 && N % 8 == 0 && a_amax && b_amax) {
-      p.b_pre = b_pre_arg; p.splits = 1;
-      if (launch_gemm_f16(p, stream)) {
-        NPVP_CHECK_LAUNCH();
-        return NPVP_OK;
-      }
-      p.splits = splits;
-    }
-    p.b_pre = b_pre = nullptr;               // fp16 planes are not what the bf16 kernels read
-    if (!a_kc && !b_kc && a_amax && b_amax && !bias && act == 0 && !aux_out && !residual && drop_p == 0.f && !rowstats &&
-        N % 4 == 0 && M % 4 == 0) {
-      const int sh = f16_wgrad_splits(M, N, K);
-      if (sh == 1 || (sh > 1 && workspace && ws_bytes >= ((long long)sh * M * N + (long long)sh * M) * 4)) {
-        splits = sh; p.splits = sh;
-        p.colgroups = 1;
-        if (sh > 1) {
-          p.K = K / sh; p.C = (float*)workspace; p.ldc = N;
-          if (colsum_a) p.colsum = (float*)workspace + (long long)sh * M * N;
-        }
-        launch_gemm_wgrad_f16(p, sh, stream);
-        NPVP_CHECK_LAUNCH();
-        if (sh > 1) {
-          const long long total4 = (long long)M * N / 4;
-          int blocks = (int)((total4 + 255) / 256); if (blocks > 2048) blocks = 2048;
-          const bool cs_here = colsum_a && M % 4 == 0 && ((uintptr_t)colsum_a % 16) == 0;       // (a float4-aligned bias gradient rides along)
-          NPVP_LAUNCH(splitk_reduce_kernel, dim3(blocks), dim3(256), 0, stream, (const float*)workspace, C, M, N, ldc,
-                             sh, alpha, p.accum, cs_here ? (const float*)p.colsum : nullptr, cs_here ? colsum_a : nullptr, c_amax);
-          NPVP_CHECK_LAUNCH();
-          if (colsum_a && !cs_here && launch_sum_rows(p.colsum, colsum_a, sh, M, M, stream, p.accum)) {
-            npvp_set_error("gemm: column-sum reduce launch failed");
-            return NPVP_ERR_LAUNCH;
-          }
-        }
-        return NPVP_OK;
-      }
-    }
-  }
-
-  NPVP_CHECK_ARG(adrop_p == 0.f, "gemm: adrop was requested but this shape does not run on the fp16 kernels (npvp_gemm_kernel_id tells)");
-
-  // large forward / dgrad shapes: 256 x 256 tiles (gemm_wide.hip); it declines what it is not built for
-  if (b_pre && launch_gemm_wide(p, stream)) {
-    NPVP_CHECK_LAUNCH();
-    return NPVP_OK;
-  }
-
-  // weight gradients (dW = dy^T x): 128 x 256 tiles, row-major staging + transposing LDS reads (gemm_wide.hip)
-  bool wide_wgrad = false;
-  if (precision == 4 && !a_kc && !b_kc && plain && !rowstats && N % 4 == 0 && M % 4 == 0) {
-    const int sw = wide_wgrad_splits(M, N, K);
-    if (sw == 1 || (sw > 1 && workspace && ws_bytes >= ((long long)sw * M * N + (long long)sw * M) * 4)) {
-      wide_wgrad = true;
-      splits = sw; p.splits = sw;
-    }
-  }
-
-  p.colgroups = splits == 1 ? pick_colgroups((long long)N * K * 4, p.tiles_m, p.tiles_n) : 1;
-  if (splits > 1) {
-    p.K = K / splits; p.C = (float*)workspace; p.ldc = N;
-    if (colsum_a) p.colsum = (float*)workspace + (long long)splits * M * N;
-  }
-
-  dim3 grid(p.tiles_m * p.tiles_n, splits), block(GEMM_THREADS);
-  if (wide_wgrad) {
-    launch_gemm_wgrad_wide(p, splits, stream);
-  } else if (precision == 0) {
-    if (a_kc && b_kc) NPVP_LAUNCH((gemm_f32_kernel<true, true>), grid, block, 0, stream, p);
-    else if (a_kc && !b_kc) NPVP_LAUNCH((gemm_f32_kernel<true, false>), grid, block, 0, stream, p);
-    else NPVP_LAUNCH((gemm_f32_kernel<false, false>), grid, block, 0, stream, p);
-  } else if (precision == 4) {
-    if (rowstats) NPVP_LAUNCH((gemm_split_db_kernel<3, true, true, false, true>), grid, block, 0, stream, p);
-    else if (b_pre && a_kc) NPVP_LAUNCH((gemm_split_db_kernel<3, true, true, true>), grid, block, 0, stream, p);
-    else if (a_kc && b_kc) NPVP_LAUNCH((gemm_split_db_kernel<3, true, true, false>), grid, block, 0, stream, p);
-    else if (a_kc && !b_kc) NPVP_LAUNCH((gemm_split_db_kernel<3, true, false, false>), grid, block, 0, stream, p);
-    else NPVP_LAUNCH((gemm_split_db_kernel<3, false, false, false>), grid, block, 0, stream, p);
-  } else {
-    if (a_kc && b_kc) NPVP_LAUNCH((gemm_split_db_kernel<2, true, true, false>), grid, block, 0, stream, p);
-    else if (a_kc && !b_kc) NPVP_LAUNCH((gemm_split_db_kernel<2, true, false, false>), grid, block, 0, stream, p);
-    else NPVP_LAUNCH((gemm_split_db_kernel<2, false, false, false>), grid, block, 0, stream, p);
+  const dim3 grid(p.tiles_m * p.tiles_n, plan.splits), block(GEMM_THREADS);
+  switch (plan.id) {
+    case 5: case 7: launch_gemm_f16(p, plan.variant, stream); break;
+    case 6: launch_gemm_wgrad_f16(p, stream); break;
+    case 2: case 4: launch_gemm_wide(p, plan.variant, stream); break;
+    case 3: launch_gemm_wgrad_wide(p, stream); break;
+    case 0:
+      if (a_kc && b_kc) NPVP_LAUNCH((gemm_f32_kernel<true, true>), grid, block, 0, stream, p);
+      else if (a_kc) NPVP_LAUNCH((gemm_f32_kernel<true, false>), grid, block, 0, stream, p);
+      else NPVP_LAUNCH((gemm_f32_kernel<false, false>), grid, block, 0, stream, p);
+      break;
+    default:                               // 1: two (precision 5) or three (4, and what 6 leaves to it) bf16 terms
+      if (precision == 5) {
+        if (a_kc && b_kc) NPVP_LAUNCH((gemm_split_db_kernel<2, true, true, false>), grid, block, 0, stream, p);
+        else if (a_kc) NPVP_LAUNCH((gemm_split_db_kernel<2, true, false, false>), grid, block, 0, stream, p);
+        else NPVP_LAUNCH((gemm_split_db_kernel<2, false, false, false>), grid, block, 0, stream, p);
+      } else if (rowstats) NPVP_LAUNCH((gemm_split_db_kernel<3, true, true, false, true>), grid, block, 0, stream, p);
+      else if (plan.planes) NPVP_LAUNCH((gemm_split_db_kernel<3, true, true, true>), grid, block, 0, stream, p);
+      else if (a_kc && b_kc) NPVP_LAUNCH((gemm_split_db_kernel<3, true, true, false>), grid, block, 0, stream, p);
+      else if (a_kc) NPVP_LAUNCH((gemm_split_db_kernel<3, true, false, false>), grid, block, 0, stream, p);
+      else NPVP_LAUNCH((gemm_split_db_kernel<3, false, false, false>), grid, block, 0, stream, p);
   }
   NPVP_CHECK_LAUNCH();
-  if (splits > 1) {
-    const long long total4 = (long long)M * N / 4;
-    int blocks = (int)((total4 + 255) / 256); if (blocks > 2048) blocks = 2048;
-    const bool cs_here = colsum_a && M % 4 == 0 && ((uintptr_t)colsum_a % 16) == 0;
-    NPVP_LAUNCH(splitk_reduce_kernel, dim3(blocks), dim3(256), 0, stream, (const float*)workspace, C, M, N, ldc,
-                       splits, alpha, p.accum, cs_here ? (const float*)p.colsum : nullptr, cs_here ? colsum_a : nullptr, c_amax);
-    NPVP_CHECK_LAUNCH();
-    if (colsum_a && !cs_here && launch_sum_rows(p.colsum, colsum_a, splits, M, M, stream, p.accum)) {
-      npvp_set_error("gemm: column-sum reduce launch failed");
-      return NPVP_ERR_LAUNCH;
-    }
-  }
-  return NPVP_OK;
+  return plan.splits > 1 ? finish_splitk(p, C, ldc, colsum_a, stream) : NPVP_OK;
 }

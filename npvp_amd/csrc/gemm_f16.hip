@@ -610,22 +610,6 @@ __global__ __launch_bounds__(256, 2) void gemm_f16_group_kernel(GemmGroup g) {
   }
 }
 
-// split count of the fp16 weight-gradient kernel: ~512 workgroups, >= 16 K-steps per split; 0 = shape not taken.  From 1 024 token
-// rows (round 5; 4 096 before): the encoder of an 8-clip shard (1 024 - 2 048 rows) then takes the chained / fused route instead of
-// the 128 x 128 bf16 kernel + a split-K reduction launch + a column-sum launch per weight gradient.
-int f16_wgrad_splits(int M, int N, int K) {
-  if ((K & 15) || M < 64 || N < 128 || K < 1024) return 0;
-  const int tiles = ((M + 127) / 128) * ((N + 255) / 256);
-  const int want = 512;                 // workgroups per launch (256 / 384 / 1024 measured within noise of it: DESIGN.md section 5)
-  int s = (want + tiles - 1) / tiles;
-  const int maxs = K / 256;
-  if (s > maxs) s = maxs;
-  if (s > 64) s = 64;
-  if (s >= 8) s &= ~7;
-  while (s > 1 && (K % (s * 16)) != 0) --s;
-  return s < 1 ? 1 : s;
-}
-
 // blocks that reduce a [M][N] split-K result inside the next launch: a multiple of that launch's tile count (whole grid rows)
 static int reduce_rows_for(const ReduceJob& j, int tiles) {
   if (!j.ws) return 0;
@@ -636,14 +620,13 @@ static int reduce_rows_for(const ReduceJob& j, int tiles) {
   return (int)((want + tiles - 1) / tiles);
 }
 
-bool launch_gemm_wgrad_f16(GemmParams& p, int splits, hipStream_t stream) {
+void launch_gemm_wgrad_f16(GemmParams& p, hipStream_t stream) {
   p.tiles_m = (p.M + 127) / 128;
   p.tiles_n = (p.N + 255) / 256;
   const int tiles = p.tiles_m * p.tiles_n, rr = reduce_rows_for(p.prev, tiles);
   p.prev.blocks = rr * tiles;
-  dim3 grid(tiles, splits + rr), block(256);
+  dim3 grid(tiles, p.splits + rr), block(256);
   NPVP_LAUNCH((gemm_wgrad_f16_kernel<2, 4, 2, 2>), grid, block, 0, stream, p);
-  return true;
 }
 
 // forward / dgrad with scaled fp16 planes: 1 = 128 x 256 tiles, 2 = 128 x 128 tiles (outputs that 128 x 256 tiles do not
@@ -667,38 +650,29 @@ int gemm_f16_variant(int M, int N, int K) {
   return 2;
 }
 
-// the tiling of a forward / dgrad launch: -> variant (0 = not taken), p.tiles_* / p.colgroups set for it
-static int prep_gemm_f16(GemmParams& p, int v128 = 0) {
-  if (!p.b_pre || !p.a_amax || !p.b_amax || p.splits != 1 || p.colsum || ((uintptr_t)p.b_pre & 15) != 0) return 0;
-  if (p.adrop.thresh && (p.adrop.mode != 1 || !p.seed)) return 0;
-  int v = gemm_f16_variant(p.M, p.N, p.K);
-  if (v == 4 && v128) v = 2;                         // (the caller wants 128 x 128 tiles where 64 x 128 would be taken)
-  if (v == 0 || (p.rowstats && (p.N % 64 != 0 || p.M % 64 != 0))) return 0;
+// the tiling of a forward / dgrad launch on the tiles of variant v (1 .. 4): p.tiles_* / p.colgroups
+static void prep_gemm_f16(GemmParams& p, int v) {
   const int bn = v == 1 ? 256 : (v == 3 ? 64 : 128);
   p.tiles_m = v == 4 ? (p.M + 63) / 64 : (p.M + 127) / 128;
   p.tiles_n = (p.N + bn - 1) / bn;
   p.colgroups = pick_colgroups((long long)p.N * p.K * 4, p.tiles_m, p.tiles_n);
-  return v;
 }
 
-bool launch_gemm_f16(GemmParams& p, hipStream_t stream) {
-  const int v = prep_gemm_f16(p);
-  if (v == 0) return false;
+void launch_gemm_f16(GemmParams& p, int v, hipStream_t stream) {
+  if (p.rowstats && v != 1) v = 2;                     // frame statistics exist for 128 x 256 and 128 x 128 tiles only
+  prep_gemm_f16(p, v);
   dim3 grid(p.tiles_m * p.tiles_n), block(256);
   if (v == 1) {
     if (p.rowstats) NPVP_LAUNCH((gemm_f16_kernel<2, 4, 2, 2, true>), grid, block, 0, stream, p);
     else NPVP_LAUNCH((gemm_f16_kernel<2, 4, 2, 2, false>), grid, block, 0, stream, p);
-  } else if (v == 3 && !p.rowstats) {
+  } else if (v == 3) {
     NPVP_LAUNCH((gemm_f16_kernel<2, 1, 2, 2, false, 2, 3>), grid, block, 0, stream, p);
-  } else if (v == 4 && !p.rowstats) {
+  } else if (v == 4) {
     NPVP_LAUNCH((gemm_f16_kernel<1, 2, 2, 2, false, 2, 3>), grid, block, 0, stream, p);
   } else {
-    if (v == 4) { p.tiles_m = (p.M + 127) / 128; grid = dim3(p.tiles_m * p.tiles_n); p.colgroups = pick_colgroups((long long)p.N * p.K * 4, p.tiles_m, p.tiles_n); }
-    if (v == 3) { p.tiles_n = (p.N + 127) / 128; grid = dim3(p.tiles_m * p.tiles_n); p.colgroups = pick_colgroups((long long)p.N * p.K * 4, p.tiles_m, p.tiles_n); }
     if (p.rowstats) NPVP_LAUNCH((gemm_f16_kernel<2, 2, 2, 2, true, 2, 3>), grid, block, 0, stream, p);
     else NPVP_LAUNCH((gemm_f16_kernel<2, 2, 2, 2, false, 2, 3>), grid, block, 0, stream, p);
   }
-  return true;
 }
 
 // ---- amax of a tensor: slot[32] = max(slot, |x|) --------------------------------------------------------------------
@@ -826,7 +800,7 @@ extern "C" int npvp_wgrad_f16_chainable(int M, int N, int K) {
 
 extern "C" long long npvp_wgrad_f16_chain_workspace_bytes(int M, int N, int K) {
   const int s = f16_wgrad_splits(M, N, K);
-  return s > 1 ? ((long long)s * M * N + (long long)s * M) * 4 : 0;
+  return s > 1 ? splitk_workspace_bytes(s, M, N) : 0;
 }
 
 extern "C" int npvp_wgrad_f16_chained(int M, int N, int K, const float* dy, long long lda, const float* x, long long ldb, float* dw,
@@ -844,17 +818,17 @@ extern "C" int npvp_wgrad_f16_chained(int M, int N, int K, const float* dy, long
                  "wgrad_f16_chained: adrop needs a device seed and groups of a multiple of 16 rows");
   const int sh = f16_wgrad_splits(M, N, K);
   GemmParams p = {};
-  p.A = dy; p.B = x; p.lda = lda; p.ldb = ldb; p.M = M; p.N = N; p.K = K / sh; p.alpha = 1.f;
-  p.C = (float*)workspace; p.ldc = N; p.splits = sh; p.colgroups = 1; p.accum = accumulate ? 1 : 0;
-  p.colsum = db ? (float*)workspace + (long long)sh * M * N : nullptr;
+  p.A = dy; p.B = x; p.lda = lda; p.ldb = ldb; p.M = M; p.N = N; p.alpha = 1.f;
+  p.splits = sh; p.colgroups = 1; p.accum = accumulate ? 1 : 0;
+  aim_at_workspace(p, K, sh, workspace, db != nullptr);
   p.seed = seed;
   p.drop = make_drop_spec(0.f, 0u, 0, 1, 1);
   p.adrop = make_drop_spec(adrop_p, adrop_salt, 1, adrop_g1, adrop_g2);
   p.a_amax = a_amax; p.b_amax = b_amax; p.range_flag = range_flag;
   if (prev_job) p.prev = *reinterpret_cast<const ReduceJob*>(prev_job);
-  launch_gemm_wgrad_f16(p, sh, stream);
+  launch_gemm_wgrad_f16(p, stream);
   NPVP_CHECK_LAUNCH();
-  ReduceJob mine = {(const float*)workspace, dw, ldc, M, N, sh, accumulate ? 1 : 0, 1.f, 0, db ? p.colsum : nullptr, db};
+  ReduceJob mine = {(const float*)workspace, dw, ldc, M, N, sh, accumulate ? 1 : 0, 1.f, 0, p.colsum, db};
   *reinterpret_cast<ReduceJob*>(my_job) = mine;
   return NPVP_OK;
 }
@@ -899,12 +873,13 @@ extern "C" int npvp_linear_bwd_f16(int R, int N, int K, const float* dy, long lo
   // workgroups beside it, else 128 x 128 (8 192 rows: 256 + 256 workgroups in one round beat 512 + 256 in one and a half -
   // profiles/r05_linear_bwd_bench.txt)
   const int t128 = ((R + 127) / 128) * ((K + 127) / 128), wwg = ((N + 127) / 128) * ((K + 255) / 256) * sh;
-  const int v = prep_gemm_f16(d, 2 * t128 + wwg > 512 ? 1 : 0);
-  NPVP_CHECK_ARG(v == 2 || v == 3 || v == 4, "linear_bwd_f16: the dgrad is not a small-tile launch");
+  int v = gemm_f16_variant(R, K, N);                     // 2, 3 or 4 (npvp_linear_bwd_f16_takes)
+  if (v == 4 && 2 * t128 + wwg > 512) v = 2;
+  prep_gemm_f16(d, v);
   GemmParams& w = g.p[1];
-  w.A = dy; w.B = x; w.lda = ldy; w.ldb = ldxx; w.M = N; w.N = K; w.K = R / sh; w.alpha = 1.f;
-  w.C = (float*)workspace; w.ldc = K; w.splits = sh; w.colgroups = 1; w.accum = 1;
-  w.colsum = db ? (float*)workspace + (long long)sh * N * K : nullptr;
+  w.A = dy; w.B = x; w.lda = ldy; w.ldb = ldxx; w.M = N; w.N = K; w.alpha = 1.f;
+  w.splits = sh; w.colgroups = 1; w.accum = 1;
+  aim_at_workspace(w, R, sh, workspace, db != nullptr);
   w.seed = seed;
   w.drop = make_drop_spec(0.f, 0u, 0, 1, 1);
   w.adrop = d.adrop;
@@ -922,7 +897,7 @@ extern "C" int npvp_linear_bwd_f16(int R, int N, int K, const float* dy, long lo
   else if (v == 4) NPVP_LAUNCH((gemm_f16_group_kernel<1, 2>), dim3(g.first[2]), dim3(256), 0, stream, g);
   else NPVP_LAUNCH((gemm_f16_group_kernel<2, 1>), dim3(g.first[2]), dim3(256), 0, stream, g);
   NPVP_CHECK_LAUNCH();
-  ReduceJob mine = {(const float*)workspace, dw, ldw, N, K, sh, 1, 1.f, 0, db ? w.colsum : nullptr, db};
+  ReduceJob mine = {(const float*)workspace, dw, ldw, N, K, sh, 1, 1.f, 0, w.colsum, db};
   *reinterpret_cast<ReduceJob*>(my_job) = mine;
   return NPVP_OK;
 }

@@ -339,27 +339,11 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN) / 2) void gemm_wgrad_wide_k
   });
 }
 
-// split count of the wide weight-gradient kernel: ~512 workgroups (2 per CU), >= 16 K-steps per split
-int wide_wgrad_splits(int M, int N, int K) {
-  // 0 = not taken.  Below ~32 K token rows the 128 x 128 kernel (3 workgroups per CU, finer tiles) is as fast or faster:
-  // measured 168 vs 166 TF at 20 480 rows, 144 vs 134 TF at 8 192 rows, 179 vs 189 TF at 114 688 rows.
-  if ((K & 15) || M < 64 || N < 128 || K < 32768) return 0;
-  const int tiles = ((M + 127) / 128) * ((N + 255) / 256);
-  int s = (512 + tiles - 1) / tiles;        // (256 / 128 workgroups: c2 step 397 / 366 ms against 336 ms; 1024 / 2048: 335.4 / 338.2 against 332.0)
-  const int maxs = K / 256;
-  if (s > maxs) s = maxs;
-  if (s > 64) s = 64;
-  if (s >= 8) s &= ~7;                                         // multiples of 8: one K-chunk per XCD
-  while (s > 1 && (K % (s * 16)) != 0) --s;
-  return s < 1 ? 1 : s;
-}
-
-bool launch_gemm_wgrad_wide(GemmParams& p, int splits, hipStream_t stream) {
+void launch_gemm_wgrad_wide(GemmParams& p, hipStream_t stream) {
   p.tiles_m = (p.M + 127) / 128;
   p.tiles_n = (p.N + 255) / 256;
-  dim3 grid(p.tiles_m * p.tiles_n, splits), block(256);
+  dim3 grid(p.tiles_m * p.tiles_n, p.splits), block(256);
   NPVP_LAUNCH((gemm_wgrad_wide_kernel<2, 4, 2, 2>), grid, block, 0, stream, p);
-  return true;
 }
 
 // Which kernel for an [M, N] output: estimated time = rounds over the CUs x relative cost of one round.  The wide kernel
@@ -375,8 +359,8 @@ static bool wide_pays(int M, int N) {
 // Which instantiation takes an [M, N] x K forward / dgrad problem with pre-split planes: 0 none (128 x 128 gemm_split_db_kernel),
 // 1 = 128 x 256 tiles, 2 = 128 x 128 tiles of the same kernel for small outputs (the per-GPU shards of the multi-GPU configs:
 // 8 192 token rows: 173 / 169 TF forward / dgrad against 155 / 153 TF of the older 128 x 128 kernel; 2 048 rows: 70 / 90
-// against 58 / 81).  Also behind npvp_gemm_kernel_id.
-static int wide_variant(int M, int N, int K) {
+// against 58 / 81).
+int wide_variant(int M, int N, int K) {
   if ((K & 15) || (N & 7) || M < 128) return 0;
   if (wide_pays(M, N)) return 1;
   // 128 x 128 tiles of this kernel run 2 workgroups per CU, the older 128 x 128 kernel 3: this one wins while all its tiles are
@@ -385,26 +369,20 @@ static int wide_variant(int M, int N, int K) {
   const int tiles128 = ((M + 127) / 128) * (N / 128);
   return (N % 128 == 0 && tiles128 <= 512) ? 2 : 0;
 }
-bool gemm_wide_takes(int M, int N, int K) { return wide_variant(M, N, K) != 0; }
-int gemm_wide_variant(int M, int N, int K) { return wide_variant(M, N, K); }
 
-bool launch_gemm_wide(GemmParams& p, hipStream_t stream) {
-  if (!p.b_pre || p.splits != 1 || p.colsum || ((uintptr_t)p.b_pre & 15) != 0) return false;
-  const int v = wide_variant(p.M, p.N, p.K);
-  if (v == 0 || (p.rowstats && (p.N % 64 != 0 || p.M % 64 != 0))) return false;
-  const int bn = v == 1 ? 256 : 128;
+void launch_gemm_wide(GemmParams& p, int variant, hipStream_t stream) {
+  const int bn = variant == 1 ? 256 : 128;
   p.tiles_m = (p.M + 127) / 128;
   p.tiles_n = (p.N + bn - 1) / bn;
   p.colgroups = pick_colgroups((long long)p.N * p.K * 6, p.tiles_m, p.tiles_n);
   dim3 grid(p.tiles_m * p.tiles_n), block(256);
-  if (v == 1) {
+  if (variant == 1) {
     if (p.rowstats) NPVP_LAUNCH((gemm_wide_kernel<2, 4, 2, 2, true>), grid, block, 0, stream, p);
     else NPVP_LAUNCH((gemm_wide_kernel<2, 4, 2, 2, false>), grid, block, 0, stream, p);
   } else {
     if (p.rowstats) NPVP_LAUNCH((gemm_wide_kernel<2, 2, 2, 2, true>), grid, block, 0, stream, p);
     else NPVP_LAUNCH((gemm_wide_kernel<2, 2, 2, 2, false>), grid, block, 0, stream, p);
   }
-  return true;
 }
 
 }  // namespace npvp

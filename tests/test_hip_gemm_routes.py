@@ -382,3 +382,108 @@ def test_one_launch_backward_on_a_ragged_shape(ops):
     assert gbv1.padding_intact() and gbv2.padding_intact(), "a bias gradient was written outside db[:N]"
     assert torch.equal(dx1.v, dx2.v), "the fused dgrad differs from the stand-alone launch"
     assert torch.equal(gw1.v, gw2.v) and torch.equal(gb1, gb2), "the fused weight gradient differs from the stand-alone launch"
+
+
+# ---- what a C caller may leave out: the workspace and the amax slots (ops.gemm always hands both over, and npvp_gemm_route answers for
+# a caller that does - so these branches of the planner are reached through ctypes only).  Bars: bf16x6's, as every launch below
+# runs on the three-term bf16 kernels.
+
+def raw_gemm(a_kc, b_kc, M, N, K, A, B, C, prec, bias=None, colsum=None, planes=None, a_amax=None, b_amax=None, ws=None, wsn=0,
+             adrop_p=0.0, seed=None):
+    """npvp_gemm_f32 as a C caller sees it -> (return code, launches made)"""
+    from npvp_amd._lib import lib
+    L = lib()
+    ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+    n0 = L.npvp_launch_count()
+    rc = L.npvp_gemm_f32(a_kc, b_kc, M, N, K, A.data_ptr(), A.stride(0), B.data_ptr(), B.stride(0), C.data_ptr(), C.stride(0),
+                         ptr(bias), 0, None, None, None, 0, 0.0, 0, 1, 1, ptr(seed), 0, 1.0, prec, ptr(colsum), ptr(planes), 0, None,
+                         ptr(a_amax), ptr(b_amax), None, None, adrop_p, 4, max(M // 4, 1), 0, ptr(ws), wsn,
+                         torch.cuda.current_stream().cuda_stream)
+    return rc, L.npvp_launch_count() - n0
+
+
+def test_fp16_forward_without_an_amax_slot_runs_as_bf16x6_without_planes(ops):
+    """precision 6 with fp16 planes but no a_amax, on a shape gemm_f16_kernel would take: the three-term bf16 kernel without planes,
+    bit-identical to the precision-4 call that hands no planes over"""
+    ops.set_gemm_precision("f16x3")
+    M, N, K = 2080, 224, 96
+    assert route_now(1, 1, M, N, K, "f16x3", 1, 1)[:2] == (5, 1) and route_now(1, 1, M, N, K, "bf16x6", 0, 1) == (1, 0, 1, 6)
+    g = torch.Generator(device=DEV).manual_seed(61)
+    A = Buf(M, K, torch.randn(M, K, device=DEV, generator=g), extra_ld=4)
+    W = Buf(N, K, torch.randn(N, K, device=DEV, generator=g) / math.sqrt(K))
+    planes, w_amax = ops.WeightPlanes.get(W.v, "F")
+    six, four = Buf(M, N, fill="pattern"), Buf(M, N, fill="pattern")
+    assert raw_gemm(1, 1, M, N, K, A.v, W.v, six.v, 6, planes=planes, b_amax=w_amax) == (0, 1)
+    assert raw_gemm(1, 1, M, N, K, A.v, W.v, four.v, 4) == (0, 1)
+    close(six.v, A.v.double() @ W.v.double().T, tol=T.TOL["bf16x6"], what="f16x3 without a_amax | 2080x224x96")
+    assert six.padding_intact() and four.padding_intact()
+    assert torch.equal(six.v, four.v), "precision 6 without an amax slot is not the bf16x6 launch without planes"
+
+
+@pytest.mark.parametrize("short_by", [None, 4], ids=["no workspace", "workspace 4 bytes short"])
+def test_fp16_weight_gradient_without_its_workspace_runs_unsplit(ops, short_by):
+    """precision 6, both amax slots, 5 splits planned (npvp_gemm_route), but no workspace / one 4 bytes short of the fp16 kernel's
+    need: the unsplit 128 x 128 bf16 kernel, bit-identical to the precision-4 call without a workspace, bias gradient included"""
+    from npvp_amd._lib import lib
+    ops.set_gemm_precision("f16x3")
+    M, N, K = 520, 264, 2080
+    assert route_now(0, 0, M, N, K, "f16x3", 0, 1) == (6, 0, 5, 26) and route_now(0, 0, M, N, K, "bf16x6", 0, 1) == (1, 0, 5, 26)
+    g = torch.Generator(device=DEV).manual_seed(62)
+    dy = Buf(K, M, torch.randn(K, M, device=DEV, generator=g), extra_ld=4)
+    x = Buf(K, N, torch.randn(K, N, device=DEV, generator=g))
+    sa, sb = ops.amax_of(dy.v), ops.amax_of(x.v)
+    need = lib().npvp_wgrad_f16_chain_workspace_bytes(M, N, K)
+    assert need > 0 and need <= lib().npvp_gemm_workspace_bytes(M, N, K)
+    ws, wsn = (None, 0) if short_by is None else (torch.empty(need // 4 + 64, dtype=torch.float32, device=DEV), need - short_by)
+    six, four = Buf(M, N, fill="pattern"), Buf(M, N, fill="pattern")
+    db6, db4 = Vec(M), Vec(M)
+    assert raw_gemm(0, 0, M, N, K, dy.v, x.v, six.v, 6, colsum=db6.v, a_amax=sa, b_amax=sb, ws=ws, wsn=wsn) == (0, 1)
+    assert raw_gemm(0, 0, M, N, K, dy.v, x.v, four.v, 4, colsum=db4.v) == (0, 1)
+    close(six.v, dy.v.double().T @ x.v.double(), tol=T.TOL["bf16x6"], what="f16x3 wgrad without workspace | 520x264x2080 | dw")
+    close(db6.v.reshape(1, -1), dy.v.double().sum(0).reshape(1, -1), tol=T.TOL["bf16x6"], what="f16x3 wgrad without workspace | 520x264x2080 | db")
+    assert six.padding_intact() and four.padding_intact() and db6.padding_intact() and db4.padding_intact()
+    assert torch.equal(six.v, four.v) and torch.equal(db6.v, db4.v), "not the unsplit bf16x6 launch"
+
+
+def test_split_k_forward_with_and_without_a_workspace(ops):
+    """a forward shape pick_splits splits 8 ways (6 tiles, K = 2048, plain): two launches with a workspace, one without, both within
+    the bars; with a bias it is never split - one launch, bit-identical with and without a workspace"""
+    from npvp_amd._lib import lib
+    ops.set_gemm_precision("bf16x6")
+    M, N, K = 260, 136, 2048
+    assert route_now(1, 1, M, N, K, "bf16x6", 0, 1) == (1, 0, 8, 16) and route_now(1, 1, M, N, K, "bf16x6", 0, 0) == (1, 0, 1, 128)
+    g = torch.Generator(device=DEV).manual_seed(63)
+    A = Buf(M, K, torch.randn(M, K, device=DEV, generator=g), extra_ld=4)
+    W = Buf(N, K, torch.randn(N, K, device=DEV, generator=g) / math.sqrt(K))
+    bias = vec(N, torch.randn(N, device=DEV, generator=g))
+    ref = A.v.double() @ W.v.double().T
+    wsb = lib().npvp_gemm_workspace_bytes(M, N, K)
+    assert wsb > 0
+    ws = torch.empty(wsb // 4 + 64, dtype=torch.float32, device=DEV)
+    out = {}
+    for name, b, w, launches in (("split", None, ws, 2), ("no workspace", None, None, 1), ("bias", bias, ws, 1), ("bias, no workspace", bias, None, 1)):
+        C = Buf(M, N, fill="pattern")
+        assert raw_gemm(1, 1, M, N, K, A.v, W.v, C.v, 4, bias=b, ws=w, wsn=wsb if w is not None else 0) == (0, launches), name
+        close(C.v, ref if b is None else ref + b.double(), tol=T.TOL["bf16x6"], what=f"db3<1,1> | 260x136x2048 | {name}")
+        assert C.padding_intact(), name
+        out[name] = C.v.clone()
+    assert torch.equal(out["bias"], out["bias, no workspace"]), "a launch with an epilogue must not depend on the workspace"
+
+
+def test_a_drop_on_a_shape_the_fp16_kernels_decline_is_an_argument_error(ops):
+    """adrop_p > 0 with precision 6 at M = 68 (gemm_f16_variant takes 128 rows or more): the argument error, nothing launched"""
+    ops.set_gemm_precision("f16x3")
+    M, N, K = 68, 136, 64
+    assert route_now(1, 0, M, N, K, "f16x3", 1, 1)[0] == 1
+    g = torch.Generator(device=DEV).manual_seed(64)
+    A = Buf(M, K, torch.randn(M, K, device=DEV, generator=g))
+    W = Buf(K, N, torch.randn(K, N, device=DEV, generator=g))
+    planes, w_amax = ops.WeightPlanes.get(W.v, "D")
+    sa = ops.amax_of(A.v)
+    seed = torch.zeros(2, dtype=torch.int64, device=DEV)
+    C = Buf(M, N, fill="pattern")
+    assert raw_gemm(1, 0, M, N, K, A.v, W.v, C.v, 6, planes=planes, a_amax=sa, b_amax=w_amax, adrop_p=0.25, seed=seed) == (-1, 0)
+    torch.cuda.synchronize()
+    assert bool((C.base.view(torch.int32) == PATTERN).all()), "the refused call wrote to C"
+    assert raw_gemm(1, 0, M, N, K, A.v, W.v, C.v, 6, planes=planes, a_amax=sa, b_amax=w_amax) == (0, 1)
+    close(C.v, A.v.double() @ W.v.double(), tol=T.TOL["bf16x6"], what="db3 planes dropped | 68x136x64 | after the refused call")

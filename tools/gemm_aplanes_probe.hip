@@ -430,10 +430,11 @@ int main(int argc, char** argv) {
     p.A = A; p.lda = K; p.C = C0; p.ldc = N; p.M = M; p.N = N; p.K = K; p.alpha = 1.f; p.splits = 1;
     p.b_pre = PW; p.b_pre_plane = (long long)N * K; p.a_amax = slotA; p.b_amax = slotW;
     GemmParams q = p;
-    if (!launch_gemm_f16(q, 0)) { printf("the product kernel did not take the shape\n"); return 2; }
+    const int pv = gemm_f16_variant(M, N, K);
+    if (pv == 0) { printf("the product kernel does not take the shape\n"); return 2; }
+    launch_gemm_f16(q, pv, 0);
     GemmParams v = p; v.C = C1;
-    if (prep_gemm_f16(v) != 1) {        // (small outputs: the product takes smaller tiles; the variants are 128 x 256-tile kernels)
-      v.tiles_m = (M + 127) / 128; v.tiles_n = (N + 255) / 256; v.colgroups = pick_colgroups((long long)N * K * 4, v.tiles_m, v.tiles_n); }
+    prep_gemm_f16(v, 1);                // (small outputs: the product takes smaller tiles; the variants are 128 x 256-tile kernels)
     const dim3 grid(v.tiles_m * v.tiles_n), block(256);
     const long long a_plane_bytes = (long long)M * K * 2;
     npvp::gemm_f16_aplanes_kernel<2><<<grid, block>>>(v, (const char*)PA, a_plane_bytes);
