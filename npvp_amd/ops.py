@@ -774,39 +774,17 @@ class _LayerNorm(torch.autograd.Function):
     def forward(ctx, x, w, b, eps, relu):
         remember(ctx)
         _chk(x, w, b)
-        C = x.shape[-1]
-        x2 = _c(x).reshape(-1, C)
-        rows = x2.shape[0]
-        y = torch.empty_like(x2)
-        mean = torch.empty(rows, dtype=torch.float32, device=x.device)
-        rstd = torch.empty_like(mean)
-        slot = _new_slot(x.device)
-        check(lib().npvp_layernorm_fwd(_ptr(x2), _ptr(w), _ptr(b), _ptr(y), _ptr(mean), _ptr(rstd), rows, C, eps,
-                                       int(relu), _ptr(slot), _stream()), "npvp_layernorm_fwd")
-        tag_amax(y, slot)
-        ctx.save_for_backward(x2, w, b, mean, rstd)
+        x2 = _c(x).reshape(-1, x.shape[-1])
+        y, st = _raw_ln_fwd(x2, w, b, eps, int(relu))
+        ctx.save_for_backward(x2, w, b, st)
         ctx.relu, ctx.shape = int(relu), x.shape
         ctx.sink = _ln_sink(w, b)
         return y.reshape(x.shape)
 
     @scoped
     def backward(ctx, dy):
-        x2, w, b, mean, rstd = ctx.saved_tensors
-        rows, C = x2.shape
-        dy2 = _c(dy).reshape(rows, C)
-        L = lib()
-        dx = torch.empty_like(x2)
-        sk = ctx.sink
-        dw, db = (sk[0][0], sk[1][0]) if sk else (torch.empty_like(w), torch.empty_like(b))
-        ws, wsn = _ws(L.npvp_layernorm_bwd_workspace_bytes(rows, C), x2.device)
-        slot = _new_slot(x2.device)
-        check(L.npvp_layernorm_bwd(_ptr(dy2), _ptr(x2), _ptr(w), _ptr(b), _ptr(mean), _ptr(rstd), _ptr(dx), _ptr(dw),
-                                   _ptr(db), rows, C, ctx.relu, _p(0), _sink_mode(sk), _ptr(slot), _ptr(ws), wsn, _stream()),
-              "npvp_layernorm_bwd")
-        tag_amax(dx, slot)
-        if sk:
-            _sunk_ln_reduce(sk, ws, rows, C)
-            return dx.reshape(ctx.shape), None, None, None, None
+        x2, w, b, st = ctx.saved_tensors
+        dx, dw, db = _raw_ln_bwd(_c(dy).reshape(x2.shape), x2, w, b, st, None, ctx.sink, ctx.relu)
         return dx.reshape(ctx.shape), dw, db, None, None
 
 
@@ -822,29 +800,21 @@ def _sink_mode(sk):
     return 0 if not sk else (2 if (_S._cur.wgrad.enabled or _S._cur.reduce.enabled) else 1)
 
 
-def _sunk_ln_reduce(sk, ws, rows, C):
-    gw, gb = sk[0][0], sk[1][0]
+def _reduce_partials(sk, ws, gw, gb, direct, job, what, tail, accumulated):
+    """The parameter-gradient partials a backward kernel left in `ws` -> the gradient slices gw / gb of the sink `sk`: as a job of
+    the ReduceQueue (`job`, the library's *_job form), else by `direct` on the gradient stream, else - neither of the two - on
+    this stream: nothing is left to do when `accumulated` (the kernel added to the slices itself: _sink_mode gave 1), `direct`
+    runs here otherwise.  tail: the scalar arguments both forms take after the three addresses."""
     if _S._cur.reduce.enabled:
-        _S._cur.reduce.add(lib().npvp_layernorm_bwd_reduce_job, "npvp_layernorm_bwd_reduce_job", (_ptr(ws), _ptr(gw), _ptr(gb), rows, C, 1),
-                        (gw.data_ptr(), gb.data_ptr()), ws, sk)
-    elif _S._cur.wgrad.enabled:
-        # (deferred: every value is bound NOW, the closure runs a few launches later)
-        _S._cur.wgrad.run(lambda ws=ws, gw=gw, gb=gb, rows=rows, C=C: check(
-            lib().npvp_layernorm_bwd_reduce(_ptr(ws), _ptr(gw), _ptr(gb), rows, C, 1, _stream()), "npvp_layernorm_bwd_reduce"), ws, wrote=sk)
+        _S._cur.reduce.add(job, what + " (ReduceQueue job)", (_ptr(ws), _ptr(gw), _ptr(gb)) + tail, (gw.data_ptr(), gb.data_ptr()), ws, sk)
+        return
+    # (deferred on the gradient stream: every value is bound NOW, the closure runs a few launches later)
+    fn = lambda ws=ws, gw=gw, gb=gb: check(direct(_ptr(ws), _ptr(gw), _ptr(gb), *tail, _stream()), what)
+    if _S._cur.wgrad.enabled:
+        _S._cur.wgrad.run(fn, ws, wrote=sk)
     else:
-        _S._cur.grad_sink.wrote(*sk)
-
-
-def _sunk_fln_reduce(sk, ws, dw, db, frames, PF):
-    """the frame-LayerNorm parameter-gradient partials left in `ws` (accumulate mode 2) -> the gradient slices"""
-    if _S._cur.reduce.enabled:
-        _S._cur.reduce.add(lib().npvp_frameln_act_bwd_reduce_job, "npvp_frameln_act_bwd_reduce_job", (_ptr(ws), _ptr(dw), _ptr(db), frames, PF, 1),
-                        (dw.data_ptr(), db.data_ptr()), ws, sk)
-    elif _S._cur.wgrad.enabled:
-        _S._cur.wgrad.run(lambda ws=ws, dw=dw, db=db, frames=frames, PF=PF: check(
-            lib().npvp_frameln_act_bwd_reduce(_ptr(ws), _ptr(dw), _ptr(db), frames, PF, 1, _stream()), "npvp_frameln_act_bwd_reduce"),
-            ws, wrote=sk)
-    else:
+        if not accumulated:
+            fn()
         _S._cur.grad_sink.wrote(*sk)
 
 
@@ -863,11 +833,10 @@ class _LayerNormNchw(torch.autograd.Function):
         C = x.shape[-1]
         x3 = _c(x).reshape(N * T, H * W, C)
         out = torch.empty(N, T, C, H, W, dtype=torch.float32, device=x.device)
-        mean = torch.empty(N * T * H * W, dtype=torch.float32, device=x.device)
-        rstd = torch.empty_like(mean)
-        check(lib().npvp_layernorm_nchw_fwd(_ptr(x3), _ptr(w), _ptr(b), _ptr(out), _ptr(mean), _ptr(rstd), N * T, H * W, C, eps,
+        st = torch.empty(2, N * T * H * W, dtype=torch.float32, device=x.device)
+        check(lib().npvp_layernorm_nchw_fwd(_ptr(x3), _ptr(w), _ptr(b), _ptr(out), _row(st, 0), _row(st, 1), N * T, H * W, C, eps,
                                             int(relu), _stream()), "npvp_layernorm_nchw_fwd")
-        ctx.save_for_backward(x3, w, b, mean, rstd)
+        ctx.save_for_backward(x3, w, b, st)
         ctx.relu, ctx.shape = int(relu), x.shape
         ctx.sink = _ln_sink(w, b)
         return out
@@ -876,25 +845,12 @@ class _LayerNormNchw(torch.autograd.Function):
     def backward(ctx, dy):
         # dy (N,T,C,H,W) -> canonical rows (the LDS-tiled transpose), then the row-wise LayerNorm backward: a fused backward
         # through the forward kernel's tile was 3x slower than these two kernels
-        x3, w, b, mean, rstd = ctx.saved_tensors
+        x3, w, b, st = ctx.saved_tensors
         F_, P, C = x3.shape
-        L = lib()
         dy = _c(dy)
         dy2 = torch.empty(F_ * P, C, dtype=torch.float32, device=dy.device)
-        check(L.npvp_transpose(_ptr(dy), _ptr(dy2), F_, C, P, _stream()), "npvp_transpose")
-        rows = F_ * P
-        x2 = x3.reshape(rows, C)
-        dx = torch.empty_like(x2)
-        sk = ctx.sink
-        dw, db = (sk[0][0], sk[1][0]) if sk else (torch.empty_like(w), torch.empty_like(b))
-        ws, wsn = _ws(L.npvp_layernorm_bwd_workspace_bytes(rows, C), x2.device)
-        slot = _new_slot(x2.device)
-        check(L.npvp_layernorm_bwd(_ptr(dy2), _ptr(x2), _ptr(w), _ptr(b), _ptr(mean), _ptr(rstd), _ptr(dx), _ptr(dw), _ptr(db),
-                                   rows, C, ctx.relu, _p(0), _sink_mode(sk), _ptr(slot), _ptr(ws), wsn, _stream()), "npvp_layernorm_bwd")
-        tag_amax(dx, slot)
-        if sk:
-            _sunk_ln_reduce(sk, ws, rows, C)
-            return (dx.reshape(ctx.shape),) + (None,) * 8
+        check(lib().npvp_transpose(_ptr(dy), _ptr(dy2), F_, C, P, _stream()), "npvp_transpose")
+        dx, dw, db = _raw_ln_bwd(dy2, x3.reshape(F_ * P, C), w, b, st, None, ctx.sink, ctx.relu)
         return (dx.reshape(ctx.shape), dw, db) + (None,) * 6
 
 
@@ -916,42 +872,20 @@ class _LayerNormRes(torch.autograd.Function):
     def forward(ctx, x, w, b, eps):
         remember(ctx)
         _chk(x, w, b)
-        C = x.shape[-1]
-        x2 = _c(x).reshape(-1, C)
-        rows = x2.shape[0]
-        y = torch.empty_like(x2)
-        mean = torch.empty(rows, dtype=torch.float32, device=x.device)
-        rstd = torch.empty_like(mean)
-        slot = _new_slot(x.device)
-        check(lib().npvp_layernorm_fwd(_ptr(x2), _ptr(w), _ptr(b), _ptr(y), _ptr(mean), _ptr(rstd), rows, C, eps, 0,
-                                       _ptr(slot), _stream()), "npvp_layernorm_fwd")
-        tag_amax(y, slot)
-        ctx.save_for_backward(x2, w, b, mean, rstd)
+        x2 = _c(x).reshape(-1, x.shape[-1])
+        y, st = _raw_ln_fwd(x2, w, b, eps)
+        ctx.save_for_backward(x2, w, b, st)
         ctx.shape = x.shape
         ctx.sink = _ln_sink(w, b)
         return x.view_as(x), y.reshape(x.shape)
 
     @scoped
     def backward(ctx, dres, dy):
-        x2, w, b, mean, rstd = ctx.saved_tensors
-        rows, C = x2.shape
-        L = lib()
         if dy is None:
             return dres, None, None, None
-        sk = ctx.sink
-        dx = torch.empty_like(x2)
-        dw, db = (sk[0][0], sk[1][0]) if sk else (torch.empty_like(w), torch.empty_like(b))
-        ws, wsn = _ws(L.npvp_layernorm_bwd_workspace_bytes(rows, C), x2.device)
-        dy2 = _c(dy).reshape(rows, C)
-        dr2 = None if dres is None else _c(dres).reshape(rows, C)
-        slot = _new_slot(x2.device)
-        check(L.npvp_layernorm_bwd(_ptr(dy2), _ptr(x2), _ptr(w), _ptr(b), _ptr(mean), _ptr(rstd), _ptr(dx), _ptr(dw),
-                                   _ptr(db), rows, C, 0, _ptr(dr2), _sink_mode(sk), _ptr(slot), _ptr(ws), wsn, _stream()),
-              "npvp_layernorm_bwd")
-        tag_amax(dx, slot)
-        if sk:
-            _sunk_ln_reduce(sk, ws, rows, C)
-            return dx.reshape(ctx.shape), None, None, None
+        x2, w, b, st = ctx.saved_tensors
+        dr2 = None if dres is None else _c(dres).reshape(x2.shape)
+        dx, dw, db = _raw_ln_bwd(_c(dy).reshape(x2.shape), x2, w, b, st, dr2, ctx.sink)
         return dx.reshape(ctx.shape), dw, db, None
 
 
@@ -968,34 +902,27 @@ class _PosFuse(torch.autograd.Function):
         remember(ctx)
         _chk(x, add, beta, gamma)
         x = _c(x)
-        F_, PF = N * T, x.numel() // (N * T)
         beta = _c(beta)
         add_c = None if add is None else _c(add)
         gamma_c = None if gamma is None else _c(gamma)
-        y = torch.empty_like(x)
-        mean = torch.empty(F_, dtype=torch.float32, device=x.device)
-        rstd = torch.empty_like(mean)
-        slot = _new_slot(x.device)
-        check(lib().npvp_posfuse_fwd(_ptr(x), _ptr(add_c), _ptr(beta), _ptr(gamma_c), _ptr(y), _ptr(mean), _ptr(rstd), N, T,
-                                     PF, 1e-5, _ptr(slot), _stream()), "npvp_posfuse_fwd")
-        tag_amax(y, slot)
-        ctx.save_for_backward(x, add_c, gamma_c, mean, rstd)
-        ctx.N, ctx.T, ctx.PF = N, T, PF
+        y, st = _raw_posfuse_fwd(x, add_c, beta, gamma_c, N, T)
+        ctx.save_for_backward(x, add_c, gamma_c, st)
+        ctx.N, ctx.T, ctx.PF = N, T, x.numel() // (N * T)
         ctx.beta_shape = beta.shape
         return y
 
     @scoped
     def backward(ctx, dy):
-        x, add, gamma, mean, rstd = ctx.saved_tensors
+        x, add, gamma, st = ctx.saved_tensors
         N, T, PF = ctx.N, ctx.T, ctx.PF
         dy = _c(dy)
-        du, dbeta, dgamma = _posfuse_bwd_call(dy, x, add, gamma, mean, rstd, N, T, PF, ctx.beta_shape, ctx.needs_input_grad[2],
+        du, dbeta, dgamma = _posfuse_bwd_call(dy, x, add, gamma, st, N, T, PF, ctx.beta_shape, ctx.needs_input_grad[2],
                                               gamma is not None and ctx.needs_input_grad[3])
         dadd = reduce_mid(du.view(N, T, PF)).view(add.shape) if (add is not None and ctx.needs_input_grad[1]) else None
         return du, dadd, dbeta, dgamma, None, None
 
 
-def _posfuse_bwd_call(dy, x, add, gamma, mean, rstd, N, T, PF, beta_shape, want_beta, want_gamma, beta_sink=None, gamma_sink=None):
+def _posfuse_bwd_call(dy, x, add, gamma, st, N, T, PF, beta_shape, want_beta, want_gamma, beta_sink=None, gamma_sink=None):
     """-> du, dbeta, dgamma: one entry point; the sums over the batch come out of the apply pass when the shape allows
     (npvp_posfuse_bwd_fused), else through a dy*uhat scratch and two reductions inside the library.  With sinks (ActSink) the
     table gradients are accumulated in place and None is returned for them."""
@@ -1019,8 +946,7 @@ def _posfuse_bwd_call(dy, x, add, gamma, mean, rstd, N, T, PF, beta_shape, want_
         dgamma = torch.empty(gamma.shape, dtype=torch.float32, device=x.device) if want_gamma else None
     dyxh = torch.empty_like(x) if (want_gamma and not L.npvp_posfuse_bwd_fused(N, T, PF)) else None
     ws, wsn = _ws(8 * N * T, x.device)
-    mp, rp = (mean, rstd) if isinstance(mean, int) else (_ptr(mean), _ptr(rstd))        # (tensors or device addresses)
-    check(L.npvp_posfuse_bwd(_ptr(dy), _ptr(x), _ptr(add), _ptr(gamma), mp, rp, _ptr(du), _ptr(dyxh), _ptr(dbeta),
+    check(L.npvp_posfuse_bwd(_ptr(dy), _ptr(x), _ptr(add), _ptr(gamma), _row(st, 0), _row(st, 1), _ptr(du), _ptr(dyxh), _ptr(dbeta),
                              _ptr(dgamma), N, T, PF, 1 if acc else 0, _ptr(ws), wsn, _stream()), "npvp_posfuse_bwd")
     return (du, None, None) if sunk else (du, dbeta, dgamma)
 
@@ -1182,12 +1108,7 @@ class _FFN(torch.autograd.Function):
         _chk(xn, x, w1, b1, w2, b2)
         C = xn.shape[-1]
         xn2, x2 = _c(xn).reshape(-1, C), _c(x).reshape(-1, C)
-        R, Fh = xn2.shape[0], w1.shape[0]
-        d2, d3 = Drop(p), Drop(p)
-        h = torch.empty(R, Fh, dtype=torch.float32, device=xn.device)
-        a_slot = _new_slot(xn.device)
-        a = tag_amax(linear_fwd(xn2, w1, b1, act=1, aux_out=h, drop=d2, y_amax=a_slot), a_slot)
-        y = linear_fwd(a, w2, b2, residual=x2, drop=d3)
+        h, a, y, d2, d3 = _ffn_fwd(xn2, x2, w1, b1, w2, b2, p)
         ctx.save_for_backward(xn2, h, a, w1, w2)
         ctx.d2, ctx.d3, ctx.shape = d2, d3, x.shape
         s1, s2 = _wb_sink(w1, b1), _wb_sink(w2, b2)
@@ -1212,6 +1133,15 @@ class _FFN(torch.autograd.Function):
         dw1, db1 = linear_wgrad(dh, xn2, True)
         dxn = linear_dgrad(dh, w1)
         return dxn.reshape(ctx.shape), dy, dw1, db1, dw2, db2, None
+
+
+def _ffn_fwd(xn2, x2, w1, b1, w2, b2, p):
+    """-> h = linear1(xn2) (saved for GELU'), a = drop2(GELU(h)), y = x2 + drop3(linear2(a)), and the two dropout sites"""
+    d2, d3 = Drop(p), Drop(p)
+    h = torch.empty(xn2.shape[0], w1.shape[0], dtype=torch.float32, device=xn2.device)
+    a_slot = _new_slot(xn2.device)
+    a = tag_amax(linear_fwd(xn2, w1, b1, act=1, aux_out=h, drop=d2, y_amax=a_slot), a_slot)
+    return h, a, linear_fwd(a, w2, b2, residual=x2, drop=d3), d2, d3
 
 
 def ffn(xn, x, w1, b1, w2, b2, p):
@@ -1313,6 +1243,54 @@ def attn(q, k, v, cfg):
     return _Attn.apply(q, k, v, cfg)
 
 
+def _fln_bwd(dout, h, mean, rstd, w, b, frames, PF, d, dp, T, sk, psum=None, nparts=0, want_amax=True):
+    """frame-LN backward (with its own statistics pass, or with the producer's `psum`); parameter gradients into the
+    sink (partials reduced on the gradient stream) or returned; want_amax: dh feeds a GEMM (gets an amax slot)"""
+    L = lib()
+    dev = h.device
+    dh = torch.empty_like(h)
+    slot = _new_slot(dev, want_amax)
+    tag_amax(dh, slot)
+    dw, db = (sk[0][0], sk[1][0]) if sk else (torch.empty_like(w), torch.empty_like(b))
+    ws, wsn = _ws(L.npvp_frameln_act_bwd_workspace_bytes(frames, PF), dev)
+    mode = _sink_mode(sk)
+    if psum is None:
+        seed = _S._cur.rng.seed_tensor(dev) if (d.on or dp.on) else None
+        check(L.npvp_frameln_act_bwd(_ptr(dout), _ptr(h), _ptr(mean), _ptr(rstd), _ptr(w), _ptr(b), _ptr(dh), _ptr(dw), _ptr(db),
+                                     frames, PF, d.p, d.salt, dp.p, dp.salt, T, _ptr(seed), mode, _ptr(slot), _ptr(ws), wsn,
+                                     _stream()), "npvp_frameln_act_bwd")
+    else:
+        pe = HbmProbe.begin()
+        check(L.npvp_frameln_act_bwd_apply(_ptr(dout), _ptr(h), _ptr(mean), _ptr(rstd), _ptr(w), _ptr(b), _ptr(psum), nparts,
+                                           _ptr(dh), _ptr(dw), _ptr(db), frames, PF, mode, _ptr(slot), _ptr(ws), wsn, _stream()),
+              "npvp_frameln_act_bwd_apply")
+        HbmProbe.end(pe, "npvp::frameln_act_bwd_fused_kernel", 4.0 * 3 * frames * PF)            # reads dout, h; writes dh
+    if sk:
+        _reduce_partials(sk, ws, dw, db, L.npvp_frameln_act_bwd_reduce, L.npvp_frameln_act_bwd_reduce_job, "npvp_frameln_act_bwd_reduce",
+                         (frames, PF, 1), True)
+        return dh, None, None
+    return dh, dw, db
+
+
+def _fln_pgrad(dout, h, mean, rstd, w, b, frames, PF, d, sk):
+    """frame-LN backward without the input gradient (npvp_frameln_act_bwd_pgrad): -> psum [frames][PF/1024][2], dw, db
+    (None, None when they went into the sink); mean / rstd are device addresses"""
+    L = lib()
+    dev = h.device
+    psum = torch.empty(frames * (PF // 1024) * 2, dtype=torch.float32, device=dev)
+    dw, db = (sk[0][0], sk[1][0]) if sk else (torch.empty_like(w), torch.empty_like(b))
+    ws, wsn = _ws(L.npvp_frameln_act_bwd_workspace_bytes(frames, PF), dev)
+    seed = _S._cur.rng.seed_tensor(dev) if d.on else None
+    check(L.npvp_frameln_act_bwd_pgrad(_ptr(dout), _ptr(h), mean, rstd, _ptr(w), _ptr(b), _ptr(psum), _ptr(dw), _ptr(db),
+                                       frames, PF, d.p, d.salt, 0.0, 0, 1, _ptr(seed), _sink_mode(sk), _ptr(ws), wsn, _stream()),
+          "npvp_frameln_act_bwd_pgrad")
+    if sk:
+        _reduce_partials(sk, ws, dw, db, L.npvp_frameln_act_bwd_reduce, L.npvp_frameln_act_bwd_reduce_job, "npvp_frameln_act_bwd_reduce",
+                         (frames, PF, 1), True)
+        return psum, None, None
+    return psum, dw, db
+
+
 class _FrameLnAct(torch.autograd.Function):
     """out = res + droppath_n(drop(GELU(LayerNorm((Ch,H,W))(h))))   (ref VidHRFormer.py:381-382,384-386,388-390)"""
 
@@ -1349,20 +1327,7 @@ class _FrameLnAct(torch.autograd.Function):
         h, mean, rstd, w_cl, b_cl = ctx.saved_tensors
         frames, PF, d, dp, fps, has_res = ctx.cfg
         dout = _c(dout)
-        L = lib()
-        dh = torch.empty_like(h)
-        sk = ctx.sink
-        dw, db = (sk[0][0], sk[1][0]) if sk else (torch.empty_like(w_cl), torch.empty_like(b_cl))
-        ws, wsn = _ws(L.npvp_frameln_act_bwd_workspace_bytes(frames, PF), h.device)
-        seed = _S._cur.rng.seed_tensor(h.device) if (d.on or dp.on) else None
-        slot = _new_slot(h.device)
-        check(L.npvp_frameln_act_bwd(_ptr(dout), _ptr(h), _ptr(mean), _ptr(rstd), _ptr(w_cl), _ptr(b_cl), _ptr(dh), _ptr(dw),
-                                     _ptr(db), frames, PF, d.p, d.salt, dp.p, dp.salt, fps, _ptr(seed), _sink_mode(sk), _ptr(slot),
-                                     _ptr(ws), wsn, _stream()), "npvp_frameln_act_bwd")
-        tag_amax(dh, slot)
-        if sk:
-            _sunk_fln_reduce(sk, ws, dw, db, frames, PF)
-            dw = db = None
+        dh, dw, db = _fln_bwd(dout, h, mean, rstd, w_cl, b_cl, frames, PF, d, dp, fps, ctx.sink)
         return dh, dw, db, (dout if has_res else None), None, None, None, None, None, None
 
 
@@ -1487,55 +1452,6 @@ class _MlpDwbn(torch.autograd.Function):
         ctx.sink_dw = sd if (sd and sd[1] is not None) else None
         return out
 
-    @staticmethod
-    def _fln_bwd(L, dout, h, mean, rstd, w, b, frames, PF, d, dp, T, sk, psum=None, nparts=0, want_amax=True):
-        """frame-LN backward (with its own statistics pass, or with the producer's `psum`); parameter gradients into the
-        sink (partials reduced on the gradient stream) or returned; want_amax: dh feeds a GEMM (gets an amax slot)"""
-        dev = h.device
-        dh = torch.empty_like(h)
-        slot = _new_slot(dev, want_amax)
-        tag_amax(dh, slot)
-        dw, db = (sk[0][0], sk[1][0]) if sk else (torch.empty_like(w), torch.empty_like(b))
-        ws, wsn = _ws(L.npvp_frameln_act_bwd_workspace_bytes(frames, PF), dev)
-        mode = _sink_mode(sk)
-        if psum is None:
-            seed = _S._cur.rng.seed_tensor(dev) if (d.on or dp.on) else None
-            check(L.npvp_frameln_act_bwd(_ptr(dout), _ptr(h), _ptr(mean), _ptr(rstd), _ptr(w), _ptr(b), _ptr(dh), _ptr(dw), _ptr(db),
-                                         frames, PF, d.p, d.salt, dp.p, dp.salt, T, _ptr(seed), mode, _ptr(slot), _ptr(ws), wsn,
-                                         _stream()), "npvp_frameln_act_bwd")
-        else:
-            pe = HbmProbe.begin()
-            check(L.npvp_frameln_act_bwd_apply(_ptr(dout), _ptr(h), _ptr(mean), _ptr(rstd), _ptr(w), _ptr(b), _ptr(psum), nparts,
-                                               _ptr(dh), _ptr(dw), _ptr(db), frames, PF, mode, _ptr(slot), _ptr(ws), wsn, _stream()),
-                  "npvp_frameln_act_bwd_apply")
-            HbmProbe.end(pe, "npvp::frameln_act_bwd_fused_kernel", 4.0 * 3 * frames * PF)            # reads dout, h; writes dh
-        if sk:
-            _sunk_fln_reduce(sk, ws, dw, db, frames, PF)
-            return dh, None, None
-        return dh, dw, db
-
-    @staticmethod
-    def _fln_pgrad(L, dout, h, mean, rstd, w, b, frames, PF, d, sk):
-        """frame-LN backward without the input gradient (npvp_frameln_act_bwd_pgrad): -> psum [frames][PF/1024][2], dw, db
-        (None, None when they went into the sink); mean / rstd are device addresses"""
-        dev = h.device
-        psum = torch.empty(frames * (PF // 1024) * 2, dtype=torch.float32, device=dev)
-        dw, db = (sk[0][0], sk[1][0]) if sk else (torch.empty_like(w), torch.empty_like(b))
-        ws, wsn = _ws(L.npvp_frameln_act_bwd_workspace_bytes(frames, PF), dev)
-        seed = _S._cur.rng.seed_tensor(dev) if d.on else None
-        check(L.npvp_frameln_act_bwd_pgrad(_ptr(dout), _ptr(h), mean, rstd, _ptr(w), _ptr(b), _ptr(psum), _ptr(dw), _ptr(db),
-                                           frames, PF, d.p, d.salt, 0.0, 0, 1, _ptr(seed), _sink_mode(sk), _ptr(ws), wsn, _stream()),
-              "npvp_frameln_act_bwd_pgrad")
-        if sk:
-            _sunk_fln_reduce(sk, ws, dw, db, frames, PF)
-            return psum, None, None
-        return psum, dw, db
-
-    @staticmethod
-    def _lin_bwd(dy, x, w, sk, has_b):
-        """dgrad on this stream, weight (+bias) gradient into the sink on the gradient stream or returned"""
-        return linear_bwd(dy, x, w, True if has_b else None, sk)      # (`b` only says whether there is a bias gradient to take)
-
     @scoped
     def backward(ctx, dout):
         x, h1, h2, a2, h3, stats, wtb, w1, w2, n1w, n1b, n2w, n2b, n3w, n3b = ctx.saved_tensors
@@ -1546,16 +1462,15 @@ class _MlpDwbn(torch.autograd.Function):
         Co = h3.shape[1]
         dev = x.device
         dout = _c(dout)
-        F_ = _MlpDwbn
-        dh3, gn3w, gn3b = F_._fln_bwd(L, dout, h3, stats[4], stats[5], n3w, n3b, frames, 64 * Co, d3, dp, T, s_n3)
-        da2, gw2, gb2 = F_._lin_bwd(dh3, a2, w2, s_fc2, has_b2)
+        dh3, gn3w, gn3b = _fln_bwd(dout, h3, stats[4], stats[5], n3w, n3b, frames, 64 * Co, d3, dp, T, s_n3)
+        da2, gw2, gb2 = linear_bwd(dh3, a2, w2, True if has_b2 else None, s_fc2)     # (`b` only says whether there is a bias gradient to take)
         fuse_n2 = MID_BWD_N2 and hid // 16 <= 256
         if fuse_n2:
             # norm2's backward WITHOUT its input gradient: frame sums (partials) + parameter gradients in one pass over da2 / h2;
             # dh2 is evaluated inside the fused middle's backward below and never written (2 passes over [R, hidden] less)
-            psum2, gn2w, gn2b = F_._fln_pgrad(L, da2, h2, _row(stats, 2), _row(stats, 3), n2w, n2b, frames, 64 * hid, d2, s_n2)
+            psum2, gn2w, gn2b = _fln_pgrad(da2, h2, _row(stats, 2), _row(stats, 3), n2w, n2b, frames, 64 * hid, d2, s_n2)
         else:
-            dh2, gn2w, gn2b = F_._fln_bwd(L, da2, h2, stats[2], stats[3], n2w, n2b, frames, 64 * hid, d2, NO_DROP, 1, s_n2,
+            dh2, gn2w, gn2b = _fln_bwd(da2, h2, stats[2], stats[3], n2w, n2b, frames, 64 * hid, d2, NO_DROP, 1, s_n2,
                                           want_amax=False)
             del da2
         # fused middle backward: da1, depthwise weight / bias gradient (a1 recomputed from h1), norm1's backward statistics
@@ -1583,26 +1498,17 @@ class _MlpDwbn(torch.autograd.Function):
             # straight into the gradient slots (on the gradient stream, like every in-place gradient write): the chunk partials
             # are reduced, transposed and accumulated by ONE launch there - no reduction on this stream, no transpose, none of
             # autograd's accumulate adds
-            fn = lambda ws=ws, gw=sk_dw[0][0], gb=sk_dw[1][0], F=frames, C=hid: check(
-                L.npvp_mlpdw_mid_bwd_reduce_into(_ptr(ws), _ptr(gw), _ptr(gb), F, C, _stream()), "npvp_mlpdw_mid_bwd_reduce_into")
-            if _S._cur.reduce.enabled:
-                gw, gb = sk_dw[0][0], sk_dw[1][0]
-                _S._cur.reduce.add(L.npvp_mlpdw_mid_bwd_reduce_job, "npvp_mlpdw_mid_bwd_reduce_job", (_ptr(ws), _ptr(gw), _ptr(gb), frames, hid),
-                                (gw.data_ptr(), gb.data_ptr()), ws, sk_dw)
-            elif _S._cur.wgrad.enabled:
-                _S._cur.wgrad.run(fn, ws, wrote=sk_dw)
-            else:
-                fn()
-                _S._cur.grad_sink.wrote(*sk_dw)
+            _reduce_partials(sk_dw, ws, sk_dw[0][0], sk_dw[1][0], L.npvp_mlpdw_mid_bwd_reduce_into, L.npvp_mlpdw_mid_bwd_reduce_job,
+                             "npvp_mlpdw_mid_bwd_reduce_into", (frames, hid), False)
             gdww = gdwb = None
         else:
             gdww = torch.empty(hid, 1, 3, 3, dtype=torch.float32, device=dev)
             check(L.npvp_transpose(_ptr(dwtb), _ptr(gdww), 1, 9, hid, _stream()), "npvp_transpose")
             gdwb = dwtb[9]
-        dh1, gn1w, gn1b = F_._fln_bwd(L, da1, h1, stats[0], stats[1], n1w, n1b, frames, 64 * hid, NO_DROP, NO_DROP, 1, s_n1,
+        dh1, gn1w, gn1b = _fln_bwd(da1, h1, stats[0], stats[1], n1w, n1b, frames, 64 * hid, NO_DROP, NO_DROP, 1, s_n1,
                                       psum=psum, nparts=nparts)
         del da1
-        dx, gw1, gb1 = F_._lin_bwd(dh1, x, w1, s_fc1, has_b1)
+        dx, gw1, gb1 = linear_bwd(dh1, x, w1, True if has_b1 else None, s_fc1)
         return (dx, dout if has_res else None, gw1, gb1, gn1w, gn1b, gdww, gdwb, gn2w, gn2b, gw2, gb2, gn3w, gn3b,
                 None, None, None, None)
 
@@ -1625,31 +1531,36 @@ def mlpdwbn(x, res, w1, b1, n1w, n1b, dww, dwb, n2w, n2b, w2, b2, n3w, n3b, fram
 # of kernel launches - nothing in between needs autograd's bookkeeping.  Against one node per kernel this removes ~3/4 of the
 # Python / autograd work per step (the 8-clip shards of c3 / c4 were bound by it) and the [R, C] gradient adds autograd
 # inserted where LN(x) feeds two consumers (they become the `residual` input of a dgrad GEMM's epilogue).
-def _raw_ln_fwd(x2, w, b, eps):
+# The _raw_* helpers below are THE call sites of the norm entry points: the per-kernel nodes above (_LayerNorm, _LayerNormRes,
+# _LayerNormNchw, _PosFuse) go through them too.
+def _raw_ln_fwd(x2, w, b, eps, relu=0):
+    """-> LN(x2) (+ ReLU), its statistics [2, rows] (mean, rstd)"""
     rows, C = x2.shape
     y = torch.empty_like(x2)
     st = torch.empty(2, rows, dtype=torch.float32, device=x2.device)
     slot = _new_slot(x2.device)
-    check(lib().npvp_layernorm_fwd(_ptr(x2), _ptr(w), _ptr(b), _ptr(y), _row(st, 0), _row(st, 1), rows, C, eps, 0, _ptr(slot),
+    check(lib().npvp_layernorm_fwd(_ptr(x2), _ptr(w), _ptr(b), _ptr(y), _row(st, 0), _row(st, 1), rows, C, eps, relu, _ptr(slot),
                                    _stream()), "npvp_layernorm_fwd")
     return tag_amax(y, slot), st
 
 
-def _raw_ln_bwd(dy2, x2, w, b, st, dres, sk):
-    """-> dx, dw, db (None, None when the parameter gradients went into the sink)"""
+def _raw_ln_bwd(dy2, x2, w, b, st, dres, sk, relu=0, probe=False):
+    """-> dx (+ dres, the residual branch's gradient), dw, db (None, None when the parameter gradients went into the sink);
+    probe: the launch is one of those HbmProbe brackets (the sub-layer nodes')"""
     L = lib()
     rows, C = x2.shape
     dx = torch.empty_like(x2)
     dw, db = (sk[0][0], sk[1][0]) if sk else (torch.empty_like(w), torch.empty_like(b))
     ws, wsn = _ws(L.npvp_layernorm_bwd_workspace_bytes(rows, C), x2.device)
     slot = _new_slot(x2.device)
-    pe = HbmProbe.begin()
+    pe = HbmProbe.begin() if probe else None
     check(L.npvp_layernorm_bwd(_ptr(dy2), _ptr(x2), _ptr(w), _ptr(b), _row(st, 0), _row(st, 1), _ptr(dx), _ptr(dw), _ptr(db), rows, C,
-                               0, _ptr(dres), _sink_mode(sk), _ptr(slot), _ptr(ws), wsn, _stream()), "npvp_layernorm_bwd")
+                               relu, _ptr(dres), _sink_mode(sk), _ptr(slot), _ptr(ws), wsn, _stream()), "npvp_layernorm_bwd")
     HbmProbe.end(pe, "npvp::ln_bwd_kernel<2>", 4.0 * (3 + (dres is not None)) * rows * C)            # reads dy, x (+ dres); writes dx
     tag_amax(dx, slot)
     if sk:
-        _sunk_ln_reduce(sk, ws, rows, C)
+        _reduce_partials(sk, ws, dw, db, L.npvp_layernorm_bwd_reduce, L.npvp_layernorm_bwd_reduce_job, "npvp_layernorm_bwd_reduce",
+                         (rows, C, 1), True)
         return dx, None, None
     return dx, dw, db
 
@@ -1689,7 +1600,7 @@ def _raw_posfuse_bwd(dy, x, add, beta_shape, gamma, st, N, T, want_add, sinks=(N
     """-> du [like x], dadd, dbeta, dgamma; sinks = the ActSinks of (beta, gamma, add) where the caller found them: those gradients
     are accumulated in place and come back as None"""
     PF = x.numel() // (N * T)
-    du, dbeta, dgamma = _posfuse_bwd_call(dy, x, add, gamma, _row(st, 0), _row(st, 1), N, T, PF, beta_shape, True, gamma is not None,
+    du, dbeta, dgamma = _posfuse_bwd_call(dy, x, add, gamma, st, N, T, PF, beta_shape, True, gamma is not None,
                                           sinks[0], sinks[1])
     dadd = None
     if add is not None and want_add:
@@ -1754,7 +1665,7 @@ class _SelfAttnSublayer(torch.autograd.Function):
         du, dadd, dbeta, dgamma = _raw_posfuse_bwd(dfused, x1, add, beta_shape, gamma, pst, N, T, ctx.needs_input_grad[6], ctx.act_sinks)
         # dx1 = dv Wv + du: the second consumer's gradient rides in as the dgrad GEMM's residual input (no separate add)
         dx1, gwv, gbv = linear_bwd(dv, x1, wv, bv, s_v, residual=du)
-        dx, glw, glb = _raw_ln_bwd(dx1, x2, lw, lb, lst, dy2, s_ln)
+        dx, glw, glb = _raw_ln_bwd(dx1, x2, lw, lb, lst, dy2, s_ln, probe=True)
         return (dx.view(xshape), glw, glb, None, dbeta, dgamma, dadd, gwqk, gbqk, gwv, gbv, gwo, gbo, None, None, None, None)
 
 
@@ -1813,7 +1724,7 @@ class _CrossAttnSublayer(torch.autograd.Function):
                 dmem = linear_dgrad(g_, w_).view(shape)
         gk = _lin_grads(dk, k2, wk, bk, s_k)
         gv = _lin_grads(dv, m2, wv, bv, s_v)
-        dx, glw, glb = _raw_ln_bwd(du, x2, lw, lb, lst, dy2, s_ln)
+        dx, glw, glb = _raw_ln_bwd(du, x2, lw, lb, lst, dy2, s_ln, probe=True)
         return (dx.view(xshape), glw, glb, None, dbeta, dgamma, dadd, dkey, dmem, gq[0], gq[1], gk[0], gk[1], gv[0], gv[1], gwo, gbo,
                 None, None, None, None)
 
@@ -1828,12 +1739,7 @@ class _FfnSublayer(torch.autograd.Function):
         C = x.shape[-1]
         x2 = _c(x).reshape(-1, C)
         xn, lst = _raw_ln_fwd(x2, lw, lb, eps)
-        R, Fh = x2.shape[0], w1.shape[0]
-        d2, d3 = Drop(p), Drop(p)
-        h = torch.empty(R, Fh, dtype=torch.float32, device=x.device)
-        a_slot = _new_slot(x.device)
-        a = tag_amax(linear_fwd(xn, w1, b1, act=1, aux_out=h, drop=d2, y_amax=a_slot), a_slot)
-        y = linear_fwd(a, w2, b2, residual=x2, drop=d3)
+        h, a, y, d2, d3 = _ffn_fwd(xn, x2, w1, b1, w2, b2, p)
         ctx.save_for_backward(x2, xn, lst, h, a, lw, lb, w1, b1, w2, b2)
         ctx.cfg = (d2, d3, x.shape)
         ctx.sinks = (_ln_sink(lw, lb), _wb_sink(w1, b1), _wb_sink(w2, b2))
@@ -1851,7 +1757,7 @@ class _FfnSublayer(torch.autograd.Function):
         dh, gw2, gb2 = linear_bwd(dz2, a, w2, b2, s2, act=3, aux_in=h, drop=d2, dx_amax=dh_slot, a_drop=ad)
         tag_amax(dh, dh_slot)
         dxn, gw1, gb1 = linear_bwd(dh, xn, w1, b1, s1)
-        dx, glw, glb = _raw_ln_bwd(dxn, x2, lw, lb, lst, dy2, s_ln)
+        dx, glw, glb = _raw_ln_bwd(dxn, x2, lw, lb, lst, dy2, s_ln, probe=True)
         return dx.view(xshape), glw, glb, None, gw1, gb1, gw2, gb2, None
 
 
