@@ -221,9 +221,14 @@ int npvp_layernorm_bwd_reduce(const void* workspace, float* dw, float* db, long 
  * npvp_mlpdw_mid_bwd_reduce_into) each sum a set of partial rows into a gradient slice nobody reads before the optimiser: ~150
  * small launches per backward pass.  The *_reduce_job forms take the same arguments and, instead of launching, write a 48-byte job
  * record to HOST memory at `job`; npvp_sum_rows_multi runs n such records (back to back at `jobs`) with ceil(n / 40) launches, the
- * records travelling in the kernels' argument blocks (nothing to upload or keep alive; graph-capturable).  Same per-column
- * summation scheme as the single launches, fixed order.  The workspaces must stay alive until npvp_sum_rows_multi has been
- * enqueued behind their producers (same stream, or a stream ordered after it). */
+ * records travelling in the kernels' argument blocks (nothing to upload or keep alive; graph-capturable).  Each form sums in a
+ * fixed order of its own.  One plan (csrc/norm.hip plan_sum_rows) picks the column blocks of both, so a queued job is bit-identical
+ * to the single launch wherever the two split the partial rows over the same lanes: the float4 walk (fewer than 64 partial rows
+ * over >= 4096 columns: the frame LayerNorm) and every set of 64 or more partial rows (LayerNorm from 253 token rows on).  It is
+ * equal to rounding where they do not: fewer than 64 partial rows off the float4 walk (LayerNorm below 253 rows, a frame LayerNorm
+ * below 4096 columns: 4 row lanes in the single launch, 16 in the queued one) and npvp_mlpdw_mid_bwd_reduce_into, whose kernel
+ * walks the chunks serially per thread.  The workspaces must stay alive until npvp_sum_rows_multi has been enqueued behind their
+ * producers (same stream, or a stream ordered after it). */
 int npvp_layernorm_bwd_reduce_job(const void* workspace, float* dw, float* db, long long rows, int C, int accumulate, void* job);
 int npvp_frameln_act_bwd_reduce_job(const void* workspace, float* dw, float* db, int frames, int per_frame, int accumulate, void* job);
 int npvp_mlpdw_mid_bwd_reduce_job(const void* workspace, float* gw, float* gb, int frames, int Ch, void* job);

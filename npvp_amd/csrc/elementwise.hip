@@ -5,7 +5,7 @@
 // ref/models/Predictor.py:346; sums over the batch for the positional-table gradients), the
 // decoder-only gradient-norm clip and AdamW update of the training step
 // (ref/models/Predictor.py:135-136,197).
-#include "common.h"
+#include "partials.h"
 
 namespace npvp {
 
@@ -262,21 +262,23 @@ extern "C" int npvp_broadcast_mid(const float* in, float* out, int A, int B, lon
 
 static int colsum_chunks(long long rows) { return (int)(rows < 128 ? rows : 128); }
 
-extern "C" long long npvp_colsum_workspace_bytes(long long rows, int N) { return (long long)colsum_chunks(rows) * N * 4; }
+// workspace of npvp_colsum: partial rows [chunks][N]
+static Partials colsum_partials(const void* ws, float* out, long long rows, int N, int accumulate) {
+  return make_partials(ws, 0, rows, colsum_chunks(rows), N, out, accumulate);
+}
+
+extern "C" long long npvp_colsum_workspace_bytes(long long rows, int N) { return colsum_partials(nullptr, nullptr, rows, N, 0).bytes; }
 
 // out[n] = sum_r x[r][n]
 extern "C" int npvp_colsum(const float* x, long long rows, int N, long long ld, float* out, int accumulate, void* workspace,
                            long long ws_bytes, hipStream_t stream) {
   NPVP_CHECK_ARG(rows > 0 && N > 0 && N % 4 == 0 && ld % 4 == 0, "colsum: bad shape");
   NPVP_CHECK_ARG(workspace && ws_bytes >= npvp_colsum_workspace_bytes(rows, N), "colsum: workspace too small");
-  const int chunks = colsum_chunks(rows);
-  const int rpc = (int)((rows + chunks - 1) / chunks), nchunks = (int)((rows + rpc - 1) / rpc);
-  NPVP_LAUNCH(colsum_partial_kernel, dim3((N / 4 + 255) / 256, nchunks), dim3(256), 0, stream, x, (float*)workspace,
-                     rows, N, ld, rpc);
+  const Partials P = colsum_partials(workspace, out, rows, N, accumulate);
+  NPVP_LAUNCH(colsum_partial_kernel, dim3((N / 4 + 255) / 256, P.job.nb), dim3(256), 0, stream, x, P.part(), rows, N, ld,
+                     P.per);
   NPVP_CHECK_LAUNCH();
-  const int rc = launch_sum_rows((const float*)workspace, out, nchunks, N, N, stream, accumulate);
-  if (rc) { npvp_set_error("colsum: reduce launch failed"); return rc; }
-  return NPVP_OK;
+  return finish_partials(P.job, 0, stream, "colsum: reduce launch failed");
 }
 
 namespace npvp {

@@ -21,6 +21,7 @@
 // so that the 8 XCDs each walk a contiguous run of tiles (B = the weight stays in the
 // XCD's L2; each A row-panel is fetched by one XCD).
 #include "gemm.h"
+#include "partials.h"
 #include <type_traits>
 
 namespace npvp {
@@ -605,11 +606,8 @@ static int finish_splitk(const GemmParams& p, float* C, long long ldc, float* co
   NPVP_LAUNCH(splitk_reduce_kernel, dim3(blocks), dim3(256), 0, stream, (const float*)p.C, C, p.M, p.N, ldc, p.splits, p.alpha,
               p.accum, cs_here ? (const float*)p.colsum : nullptr, cs_here ? colsum_a : nullptr, p.c_amax);
   NPVP_CHECK_LAUNCH();
-  if (colsum_a && !cs_here && launch_sum_rows(p.colsum, colsum_a, p.splits, p.M, p.M, stream, p.accum)) {
-    npvp_set_error("gemm: column-sum reduce launch failed");
-    return NPVP_ERR_LAUNCH;
-  }
-  return NPVP_OK;
+  if (!colsum_a || cs_here) return NPVP_OK;
+  return finish_partials(make_partials(p.colsum, 0, p.splits, p.splits, p.M, colsum_a, p.accum).job, 0, stream, "gemm: column-sum reduce launch failed");
 }
 
 // See include/npvp_hip.h for the contract.

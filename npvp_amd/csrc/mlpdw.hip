@@ -3,7 +3,7 @@
 // gradient (same kernel, taps flipped) and weight/bias gradient.  HBM bound: one read + one write of
 // the hidden tensor (the 9 neighbour taps hit L1/L2).  Weights are tap-major [9][Ch] so that a lane's
 // 4 channels are one float4.
-#include "common.h"
+#include "partials.h"
 #include <cstring>
 #include <cstdlib>
 
@@ -604,9 +604,14 @@ extern "C" int npvp_mlpdw_mid_fwd_parts(const float* h1, const float* part1, int
 
 static int mid_chunks(int frames) { return frames < 128 ? frames : 128; }      // 256 / 512 chunks: no change of the c2 step
 
-// workspace of npvp_mlpdw_mid_bwd: weight-gradient partials [chunks][10][Ch]
+// workspace of npvp_mlpdw_mid_bwd: weight-gradient partials [chunks][10][Ch].  Their sums go to dwt_db [10][Ch] (out_b null:
+// mode 0) or straight into the Conv2d gradients gw [Ch][9] / gb [Ch], always accumulating (out_b = gb: mode 1, queued form only).
+static Partials mid_partials(const void* ws, float* out, float* out_b, int frames, int Ch, int accumulate) {
+  return make_partials(ws, 0, frames, mid_chunks(frames), 10 * Ch, out, accumulate, out_b, out_b ? Ch : 0, out_b ? 1 : 0);
+}
+
 extern "C" long long npvp_mlpdw_mid_bwd_workspace_bytes(int frames, int Ch) {
-  return (long long)mid_chunks(frames) * 10 * Ch * 4;
+  return mid_partials(nullptr, nullptr, nullptr, frames, Ch, 0).bytes;
 }
 
 // Fused MlpDWBN middle, backward: da1 (gradient w.r.t. a1 = gelu(norm1(h1)), [frames, 64, Ch]), dwt_db [10][Ch] (depthwise
@@ -617,19 +622,16 @@ static int mid_bwd_launch(const float* dh2, const float* h1, const float* mean1,
                           int Ch, int accumulate, void* workspace, long long ws_bytes, hipStream_t stream, const MidN2* n2) {
   NPVP_CHECK_ARG(frames > 0 && H == 8 && W == 8 && Ch > 0 && Ch % 512 == 0, "mlpdw_mid_bwd: needs an 8x8 grid and Ch % 512 == 0");
   NPVP_CHECK_ARG(workspace && ws_bytes >= npvp_mlpdw_mid_bwd_workspace_bytes(frames, Ch), "mlpdw_mid_bwd: workspace too small");
-  const int chunks = mid_chunks(frames), fpc = (frames + chunks - 1) / chunks, nchunks = (frames + fpc - 1) / fpc;
+  const Partials P = mid_partials(workspace, dwt_db, nullptr, frames, Ch, accumulate);
   // one channel per thread: the windows of a1, dh2, gelu'(y1) w1n and hhat (10 rows of 8) fit 242 VGPRs without spilling
   if (n2)
-    NPVP_LAUNCH((mlpdw_mid_bwd_kernel<1, true>), dim3(Ch / 256, nchunks), dim3(256), 0, stream, dh2, h1, mean1, rstd1, w1n,
-                       b1n, wt, da1, (float*)workspace, psum, Ch, frames, fpc, *n2);
+    NPVP_LAUNCH((mlpdw_mid_bwd_kernel<1, true>), dim3(Ch / 256, P.job.nb), dim3(256), 0, stream, dh2, h1, mean1, rstd1, w1n,
+                       b1n, wt, da1, P.part(), psum, Ch, frames, P.per, *n2);
   else
-    NPVP_LAUNCH((mlpdw_mid_bwd_kernel<1, false>), dim3(Ch / 256, nchunks), dim3(256), 0, stream, dh2, h1, mean1, rstd1, w1n,
-                       b1n, wt, da1, (float*)workspace, psum, Ch, frames, fpc, MidN2{});
+    NPVP_LAUNCH((mlpdw_mid_bwd_kernel<1, false>), dim3(Ch / 256, P.job.nb), dim3(256), 0, stream, dh2, h1, mean1, rstd1, w1n,
+                       b1n, wt, da1, P.part(), psum, Ch, frames, P.per, MidN2{});
   NPVP_CHECK_LAUNCH();
-  if (accumulate == 2) return NPVP_OK;        // the caller reduces the partials (npvp_mlpdw_mid_bwd_reduce)
-  const int rc = launch_sum_rows((const float*)workspace, dwt_db, nchunks, 10 * Ch, 10 * Ch, stream, accumulate);
-  if (rc) { npvp_set_error("mlpdw_mid_bwd: reduce launch failed"); return rc; }
-  return NPVP_OK;
+  return finish_partials(P.job, accumulate, stream, "mlpdw_mid_bwd: reduce launch failed");      // (2: npvp_mlpdw_mid_bwd_reduce*)
 }
 
 extern "C" int npvp_mlpdw_mid_bwd(const float* dh2, const float* h1, const float* mean1, const float* rstd1, const float* w1n,
@@ -674,30 +676,21 @@ __global__ void mid_bwd_reduce_into_kernel(const float* __restrict__ part, float
 extern "C" int npvp_mlpdw_mid_bwd_reduce_into(const void* workspace, float* gw, float* gb, int frames, int Ch,
                                               hipStream_t stream) {
   NPVP_CHECK_ARG(workspace && gw && gb && frames > 0 && Ch > 0, "mlpdw_mid_bwd_reduce_into: bad arguments");
-  const int chunks = mid_chunks(frames), fpc = (frames + chunks - 1) / chunks, nchunks = (frames + fpc - 1) / fpc;
-  NPVP_LAUNCH(mid_bwd_reduce_into_kernel, dim3((10 * Ch + 255) / 256), dim3(256), 0, stream, (const float*)workspace, gw, gb,
-                     Ch, nchunks);
+  const SumRowsJob j = mid_partials(workspace, gw, gb, frames, Ch, 1).job;
+  NPVP_LAUNCH(mid_bwd_reduce_into_kernel, dim3((10 * Ch + 255) / 256), dim3(256), 0, stream, j.in, gw, gb, Ch, j.nb);
   NPVP_CHECK_LAUNCH();
   return NPVP_OK;
 }
 
-// the same as a 48-byte job record for npvp_sum_rows_multi (norm.hip: struct SumRowsJob, mode 1); nothing is launched
+// the same as a 48-byte job record for npvp_sum_rows_multi (SumRowsJob, mode 1); nothing is launched
 extern "C" int npvp_mlpdw_mid_bwd_reduce_job(const void* workspace, float* gw, float* gb, int frames, int Ch, void* job) {
   NPVP_CHECK_ARG(workspace && gw && gb && frames > 0 && Ch > 0 && job, "mlpdw_mid_bwd_reduce_job: bad arguments");
-  const int chunks = mid_chunks(frames), fpc = (frames + chunks - 1) / chunks, nchunks = (frames + fpc - 1) / fpc;
-  struct { const float* in; float* out; float* out_b; int nb, stride, ncols, split, accum, mode; } j =
-      {(const float*)workspace, gw, gb, nchunks, 10 * Ch, 10 * Ch, Ch, 1, 1};
-  static_assert(sizeof(j) == 48, "SumRowsJob");
-  memcpy(job, &j, sizeof(j));
-  return NPVP_OK;
+  return put_job(job, mid_partials(workspace, gw, gb, frames, Ch, 1).job);
 }
 
 extern "C" int npvp_mlpdw_mid_bwd_reduce(const void* workspace, float* dwt_db, int frames, int Ch, int accumulate,
                                          hipStream_t stream) {
-  const int chunks = mid_chunks(frames), fpc = (frames + chunks - 1) / chunks, nchunks = (frames + fpc - 1) / fpc;
-  const int rc = launch_sum_rows((const float*)workspace, dwt_db, nchunks, 10 * Ch, 10 * Ch, stream, accumulate ? 1 : 0);
-  if (rc) { npvp_set_error("mlpdw_mid_bwd_reduce: launch failed"); return rc; }
-  return NPVP_OK;
+  return finish_partials(mid_partials(workspace, dwt_db, nullptr, frames, Ch, accumulate).job, 0, stream, "mlpdw_mid_bwd_reduce: launch failed");
 }
 
 extern "C" int npvp_im2col3x3(const float* in, float* out, int frames, int H, int W, int C, int col2im, hipStream_t stream) {
@@ -709,24 +702,25 @@ extern "C" int npvp_im2col3x3(const float* in, float* out, int frames, int H, in
   return NPVP_OK;
 }
 
-extern "C" long long npvp_dwconv3x3_wgrad_workspace_bytes(int frames, int Ch) {
-  return (long long)dw_chunks(frames) * 10 * Ch * 4;
+// workspace of npvp_dwconv3x3_wgrad: partials [chunks][10][Ch], summed (never accumulated) into dwt_db [10][Ch]
+static Partials dw_partials(const void* ws, float* dwt_db, int frames, int Ch) {
+  return make_partials(ws, 0, frames, dw_chunks(frames), 10 * Ch, dwt_db, 0);
 }
+
+extern "C" long long npvp_dwconv3x3_wgrad_workspace_bytes(int frames, int Ch) { return dw_partials(nullptr, nullptr, frames, Ch).bytes; }
 
 // dwt [9][Ch], db [Ch] must be CONTIGUOUS as one [10][Ch] buffer: db = dwt + 9*Ch
 extern "C" int npvp_dwconv3x3_wgrad(const float* a, const float* dout, float* dwt_db, int frames, int H, int W, int Ch,
                                     void* workspace, long long ws_bytes, hipStream_t stream) {
   NPVP_CHECK_ARG(frames > 0 && H > 0 && W > 0 && Ch % 4 == 0, "dwconv_wgrad: bad shape");
   NPVP_CHECK_ARG(workspace && ws_bytes >= npvp_dwconv3x3_wgrad_workspace_bytes(frames, Ch), "dwconv_wgrad: workspace too small");
-  const int chunks = dw_chunks(frames), fpc = (frames + chunks - 1) / chunks, nchunks = (frames + fpc - 1) / fpc;
+  const Partials P = dw_partials(workspace, dwt_db, frames, Ch);
   if (H == 8 && W == 8)
-    NPVP_LAUNCH((dwconv3x3_wgrad_win_kernel<8, 8>), dim3((Ch / 4 + 255) / 256, nchunks), dim3(256), 0, stream, a, dout,
-                       (float*)workspace, Ch, frames, fpc);
+    NPVP_LAUNCH((dwconv3x3_wgrad_win_kernel<8, 8>), dim3((Ch / 4 + 255) / 256, P.job.nb), dim3(256), 0, stream, a, dout,
+                       P.part(), Ch, frames, P.per);
   else
-    NPVP_LAUNCH(dwconv3x3_wgrad_kernel, dim3((Ch / 4 + 63) / 64, nchunks), dim3(256), 0, stream, a, dout,
-                       (float*)workspace, H, W, Ch, frames, fpc);
+    NPVP_LAUNCH(dwconv3x3_wgrad_kernel, dim3((Ch / 4 + 63) / 64, P.job.nb), dim3(256), 0, stream, a, dout,
+                       P.part(), H, W, Ch, frames, P.per);
   NPVP_CHECK_LAUNCH();
-  const int rc = launch_sum_rows((const float*)workspace, dwt_db, nchunks, 10 * Ch, 10 * Ch, stream);
-  if (rc) { npvp_set_error("dwconv_wgrad: reduce launch failed"); return rc; }
-  return NPVP_OK;
+  return finish_partials(P.job, 0, stream, "dwconv_wgrad: reduce launch failed");
 }

@@ -8,7 +8,7 @@
 //   * frame-LN + per-element affine + GELU + dropout (+ residual, drop-path) apply
 // and their backward passes.  Algorithmic bytes: one read + one write of the activation per
 // pass (8 B/element); statistics passes re-read a frame that is L2 resident.
-#include "common.h"
+#include "partials.h"
 #include <cstring>
 #include <cstdlib>
 
@@ -794,19 +794,30 @@ __global__ __launch_bounds__(256) void frameln_act_bwd_pgrad_kernel(FlnParams p,
   st4(o + p.per_frame + e, ab);
 }
 
-int launch_sum_rows(const float* in, float* out, int nb, int stride, int ncols, hipStream_t stream, int accum, float* out_b,
-                    int split) {
-  // few partial rows (frame-LN params: 32 x 262144) -> 4 row lanes of 64 columns; many partial rows over few columns
-  // (bias / LayerNorm / split-K column sums: 512 x 1024) -> 16-column blocks with 64 row lanes: 4x the blocks
-  if (nb < 64 && ncols >= 4096 && ncols % 4 == 0 && stride % 4 == 0 && (!out_b || split % 4 == 0) && ((uintptr_t)in & 15) == 0)
-    NPVP_LAUNCH(sum_rows_wide_kernel, dim3((ncols + sum_rows_wide_cols() - 1) / sum_rows_wide_cols()), dim3(1024), 0, stream, in, out,
-                nb, stride, ncols, accum, out_b, out_b ? split : 0);
-  else if (nb >= 64 && ncols <= 8192)
-    NPVP_LAUNCH(sum_rows_kernel<16>, dim3((ncols + 15) / 16), dim3(1024), 0, stream, in, out, nb, stride, ncols, accum,
-                       out_b, split);
-  else
-    NPVP_LAUNCH(sum_rows_kernel<64>, dim3((ncols + 63) / 64), dim3(nb >= 64 ? 1024 : 256), 0, stream, in, out, nb, stride,
-                       ncols, accum, out_b, split);
+// The ONE choice of kernel for a set of partial rows: the columns a block owns, and the threads of the DIRECT launch.  Few partial
+// rows over many columns (frame-LN params: 32 x 262144) -> the float4 walk; many partial rows over few columns (bias / LayerNorm /
+// split-K column sums: 512 x 1024) -> 16-column blocks with 64 row lanes: 4x the blocks; else 64-column blocks.  launch_sum_rows
+// launches exactly this; npvp_sum_rows_multi takes `cw` from it and always runs 1024 threads.  So the direct and the queued form
+// of a job split the rows over the same lanes, and are bit-identical, on the float4 walk (one thread adds rows 0 .. nb-1), on the
+// 16-column path and on the 64-column path at nb >= 64; at nb < 64 on the 64-column path (LayerNorm below 253 rows, frame LN below
+// 4096 columns) the direct launch has 4 row lanes and the queued one 16: equal to rounding.  A mode-1 job never takes the float4
+// walk and exists queued only: its direct form, npvp_mlpdw_mid_bwd_reduce_into, has a kernel of its own that walks the chunks
+// serially per thread (equal to rounding as well).
+struct SumRowsPlan { int cw, threads; };
+static SumRowsPlan plan_sum_rows(const SumRowsJob& q) {
+  if (q.mode == 0 && q.nb < 64 && q.ncols >= 4096 && q.ncols % 4 == 0 && q.stride % 4 == 0 && (!q.out_b || q.split % 4 == 0)
+      && ((uintptr_t)q.in & 15) == 0)
+    return {sum_rows_wide_cols(), 1024};
+  if (q.nb >= 64 && q.ncols <= 8192) return {16, 1024};
+  return {64, q.nb >= 64 ? 1024 : 256};
+}
+
+int launch_sum_rows(const SumRowsJob& q, hipStream_t stream) {
+  if (q.mode != 0) return NPVP_ERR_ARG;
+  const SumRowsPlan pl = plan_sum_rows(q);
+  const auto kernel = pl.cw == sum_rows_wide_cols() ? sum_rows_wide_kernel : pl.cw == 16 ? sum_rows_kernel<16> : sum_rows_kernel<64>;
+  NPVP_LAUNCH(kernel, dim3((q.ncols + pl.cw - 1) / pl.cw), dim3(pl.threads), 0, stream, q.in, q.out, q.nb, q.stride, q.ncols, q.accum,
+              q.out_b, q.out_b ? q.split : 0);
   return hipGetLastError() == hipSuccess ? NPVP_OK : NPVP_ERR_LAUNCH;
 }
 
@@ -816,15 +827,7 @@ int launch_sum_rows(const float* in, float* out, int nb, int stride, int ncols, 
 // is replayed from a graph); the sets have no consumer before the optimiser, so they are queued on the host and summed by a
 // handful of launches when the backward pass ends.  The jobs travel in the kernel's ARGUMENT block (no device table to keep alive,
 // nothing for a graph replay to re-upload).  Per job the same scheme as sum_rows_kernel: a block owns `cw` columns (16 or 64) and
-// splits the nb partial rows over 1024 / cw row lanes; fixed summation order.
-struct SumRowsJob {
-  const float* in; float* out; float* out_b;   // out_b (nullable): columns >= split go to out_b[c - split]
-  int nb, stride, ncols, split;
-  int accum;                                   // 1: += into out / out_b
-  int mode;                                    // 0 plain; 1: depthwise-conv partials [10][Ch] (ncols = 10 Ch, split = Ch): tap t < 9 of channel c
-                                               //    -> out[c*9 + t], the bias row -> out_b[c]   (mid_bwd_reduce_into_kernel's map)
-};
-constexpr int SRJ_MAX = 40;
+// splits the nb partial rows over 1024 / cw row lanes; fixed summation order.  (SumRowsJob: partials.h; cw: plan_sum_rows.)
 struct SumRowsBatch { SumRowsJob j[SRJ_MAX]; int first[SRJ_MAX + 1]; int cw[SRJ_MAX]; int n; };
 
 __global__ __launch_bounds__(1024) void sum_rows_multi_kernel(SumRowsBatch b) {
@@ -879,19 +882,20 @@ static void fill_fln(FlnParams& p, const float* h, const float* mean, const floa
 
 using namespace npvp;
 
+// the instantiation for C = 256 NV of a LayerNorm kernel (NV float4 per lane), forward and backward
+#define LN_LAUNCH(kernel, C, ...)                                                                         \
+  switch ((C) / 256) {                                                                                    \
+    case 1: NPVP_LAUNCH(kernel<1>, __VA_ARGS__); break;  case 2: NPVP_LAUNCH(kernel<2>, __VA_ARGS__); break;   \
+    case 3: NPVP_LAUNCH(kernel<3>, __VA_ARGS__); break;  default: NPVP_LAUNCH(kernel<4>, __VA_ARGS__); break;  \
+  }
+
 extern "C" int npvp_layernorm_fwd(const float* x, const float* w, const float* b, float* y, float* mean, float* rstd,
                                   long long rows, int C, float eps, int relu, float* amax, hipStream_t stream) {
   NPVP_CHECK_ARG(rows > 0, "layernorm: no rows");
   NPVP_CHECK_ARG(C % 256 == 0 && C >= 256 && C <= 1024, "layernorm: C must be 256, 512, 768 or 1024");
   // <= 4096 blocks (16 waves per CU x 4 rounds): short waves would pay the per-block amax commit and the parameter loads per row
   const long long nb = (rows + 3) / 4;
-  dim3 grid((unsigned)(nb > 4096 ? 4096 : nb)), block(256);
-  switch (C / 256) {
-    case 1: NPVP_LAUNCH(ln_fwd_kernel<1>, grid, block, 0, stream, x, w, b, y, mean, rstd, rows, eps, relu, amax); break;
-    case 2: NPVP_LAUNCH(ln_fwd_kernel<2>, grid, block, 0, stream, x, w, b, y, mean, rstd, rows, eps, relu, amax); break;
-    case 3: NPVP_LAUNCH(ln_fwd_kernel<3>, grid, block, 0, stream, x, w, b, y, mean, rstd, rows, eps, relu, amax); break;
-    default: NPVP_LAUNCH(ln_fwd_kernel<4>, grid, block, 0, stream, x, w, b, y, mean, rstd, rows, eps, relu, amax); break;
-  }
+  LN_LAUNCH(ln_fwd_kernel, C, dim3((unsigned)(nb > 4096 ? 4096 : nb)), dim3(256), 0, stream, x, w, b, y, mean, rstd, rows, eps, relu, amax);
   NPVP_CHECK_LAUNCH();
   return NPVP_OK;
 }
@@ -901,8 +905,14 @@ static int ln_bwd_blocks(long long rows) {
   return (int)(b > 512 ? 512 : b);      // 2048 / 4096 blocks: no change of the c2 step (331.0 / 331.7 / 331.3 ms)
 }
 
+// partial rows [blocks][dw(C) | db(C)] at the start of the workspace (one row per block: no chunk split)
+static Partials ln_partials(const void* ws, float* dw, float* db, long long rows, int C, int accumulate) {
+  const int nb = ln_bwd_blocks(rows);
+  return make_partials(ws, 0, nb, nb, 2 * C, dw, accumulate, db, C);
+}
+
 extern "C" long long npvp_layernorm_bwd_workspace_bytes(long long rows, int C) {
-  return (long long)ln_bwd_blocks(rows) * 2 * C * 4;
+  return ln_partials(nullptr, nullptr, nullptr, rows, C, 0).bytes;
 }
 
 extern "C" int npvp_layernorm_bwd(const float* dy, const float* x, const float* w, const float* b, const float* mean,
@@ -911,24 +921,11 @@ extern "C" int npvp_layernorm_bwd(const float* dy, const float* x, const float* 
                                   hipStream_t stream) {
   NPVP_CHECK_ARG(rows > 0, "layernorm_bwd: no rows");
   NPVP_CHECK_ARG(C % 256 == 0 && C >= 256 && C <= 1024, "layernorm_bwd: C must be 256, 512, 768 or 1024");
-  const int nb = ln_bwd_blocks(rows);
-  NPVP_CHECK_ARG(workspace && ws_bytes >= (long long)nb * 2 * C * 4, "layernorm_bwd: workspace too small");
-  float* part = (float*)workspace;
-  dim3 grid(nb), block(256);
-  switch (C / 256) {
-    case 1: NPVP_LAUNCH(ln_bwd_kernel<1>, grid, block, 0, stream, dy, x, w, b, mean, rstd, dx, part, rows, relu, dres, amax); break;
-    case 2: NPVP_LAUNCH(ln_bwd_kernel<2>, grid, block, 0, stream, dy, x, w, b, mean, rstd, dx, part, rows, relu, dres, amax); break;
-    case 3: NPVP_LAUNCH(ln_bwd_kernel<3>, grid, block, 0, stream, dy, x, w, b, mean, rstd, dx, part, rows, relu, dres, amax); break;
-    default: NPVP_LAUNCH(ln_bwd_kernel<4>, grid, block, 0, stream, dy, x, w, b, mean, rstd, dx, part, rows, relu, dres, amax); break;
-  }
+  const Partials P = ln_partials(workspace, dw, db, rows, C, accumulate);
+  NPVP_CHECK_ARG(workspace && ws_bytes >= P.bytes, "layernorm_bwd: workspace too small");
+  LN_LAUNCH(ln_bwd_kernel, C, dim3(P.job.nb), dim3(256), 0, stream, dy, x, w, b, mean, rstd, dx, P.part(), rows, relu, dres, amax);
   NPVP_CHECK_LAUNCH();
-  // partial rows are [dw(C) | db(C)]
-  if (accumulate == 2) return NPVP_OK;      // the caller reduces the partials itself (npvp_layernorm_bwd_reduce)
-  if (launch_sum_rows((const float*)part, dw, nb, 2 * C, 2 * C, stream, accumulate, db, C)) {
-    npvp_set_error("layernorm_bwd: reduce launch failed");
-    return NPVP_ERR_LAUNCH;
-  }
-  return NPVP_OK;
+  return finish_partials(P.job, accumulate, stream, "layernorm_bwd: reduce launch failed");      // (2: npvp_layernorm_bwd_reduce)
 }
 
 // second stage of npvp_layernorm_bwd(accumulate = 2) on a stream of the caller's choice: dw, db (+)= column sums of the
@@ -936,25 +933,13 @@ extern "C" int npvp_layernorm_bwd(const float* dy, const float* x, const float* 
 extern "C" int npvp_layernorm_bwd_reduce(const void* workspace, float* dw, float* db, long long rows, int C, int accumulate,
                                          hipStream_t stream) {
   NPVP_CHECK_ARG(workspace && dw && db && rows > 0, "layernorm_bwd_reduce: bad arguments");
-  if (launch_sum_rows((const float*)workspace, dw, ln_bwd_blocks(rows), 2 * C, 2 * C, stream, accumulate ? 1 : 0, db, C)) {
-    npvp_set_error("layernorm_bwd_reduce: launch failed");
-    return NPVP_ERR_LAUNCH;
-  }
-  return NPVP_OK;
+  return finish_partials(ln_partials(workspace, dw, db, rows, C, accumulate).job, 0, stream, "layernorm_bwd_reduce: launch failed");
 }
 
 // The same reduction as a JOB for npvp_sum_rows_multi (48 bytes at `job`, see include/npvp_hip.h): nothing is launched.
-static void fill_job(void* job, const float* in, float* out, float* out_b, int nb, int stride, int ncols, int split, int accum, int mode) {
-  SumRowsJob j;
-  j.in = in; j.out = out; j.out_b = out_b; j.nb = nb; j.stride = stride; j.ncols = ncols; j.split = split; j.accum = accum; j.mode = mode;
-  memcpy(job, &j, sizeof(j));
-}
-static_assert(sizeof(SumRowsJob) == 48, "a job is 48 bytes (npvp_amd/ops.py ReduceQueue packs them back to back)");
-
 extern "C" int npvp_layernorm_bwd_reduce_job(const void* workspace, float* dw, float* db, long long rows, int C, int accumulate, void* job) {
   NPVP_CHECK_ARG(workspace && dw && db && rows > 0 && job, "layernorm_bwd_reduce_job: bad arguments");
-  fill_job(job, (const float*)workspace, dw, db, ln_bwd_blocks(rows), 2 * C, 2 * C, C, accumulate ? 1 : 0, 0);
-  return NPVP_OK;
+  return put_job(job, ln_partials(workspace, dw, db, rows, C, accumulate).job);
 }
 
 // `jobs` = n SumRowsJob records in HOST memory (filled by the *_reduce_job entry points); ceil(n / 40) launches
@@ -968,10 +953,7 @@ extern "C" int npvp_sum_rows_multi(const void* jobs, int n, hipStream_t stream) 
     for (int i = 0; i < b.n; ++i) {
       b.j[i] = J[at + i];
       NPVP_CHECK_ARG(b.j[i].in && b.j[i].out && b.j[i].nb > 0 && b.j[i].ncols > 0, "sum_rows_multi: bad job");
-      const SumRowsJob& q = b.j[i];                                            // (launch_sum_rows' choice)
-      const bool wide = q.mode == 0 && q.nb < 64 && q.ncols >= 4096 && q.ncols % 4 == 0 && q.stride % 4 == 0
-                        && (!q.out_b || q.split % 4 == 0) && ((uintptr_t)q.in & 15) == 0;
-      b.cw[i] = wide ? sum_rows_wide_cols() : (q.nb >= 64 && q.ncols <= 8192) ? 16 : 64;
+      b.cw[i] = plan_sum_rows(b.j[i]).cw;
       b.first[i] = blocks;
       blocks += (b.j[i].ncols + b.cw[i] - 1) / b.cw[i];
     }
@@ -1044,8 +1026,6 @@ extern "C" int npvp_posfuse_bwd_fused(int N, int T, int per_frame) {
   const long long blocks = (long long)T * (per_frame / 1024);
   return (blocks >= 128 || N <= 16) ? 1 : 0;
 }
-
-int npvp_reduce_mid_launch(const float* in, float* out, int A, int B, long long Cc, float scale, hipStream_t stream, int accumulate = 0);   // elementwise.hip
 
 // du [N*T, per_frame]; dbeta / dgamma [T, per_frame] (nullable) = sum over the batch of dy / dy*uhat; dyxh (nullable) = scratch
 // for dy*uhat, needed only when npvp_posfuse_bwd_fused(N, T, per_frame) == 0 and dgamma is wanted; ws = 2*N*T floats
@@ -1127,21 +1107,35 @@ extern "C" int npvp_frameln_act_fwd_parts(const float* h, const float* part, int
   return NPVP_OK;
 }
 
-// frame chunks (grid.y) of the one-pass backward: 32 x 128 = 4096 workgroups.  With 8 (1024 workgroups, each walking 224 frames
-// at c2) the kernel was as fast stand-alone (921 vs 923 us for statistics + apply) but lost CU slots to the co-resident
-// weight-gradient GEMM: c2 step 342.7 -> 338.3 ms (three A/B pairs on one box; 64 chunks: 338.1).
-// frame chunks of the backward kernels' parameter-gradient partials ([chunks][2 * per_frame] floats, summed later).  32 for the
-// large workloads (with 8 the kernels lost their CU share to a co-resident weight-gradient GEMM); for fewer
-// than 512 frames at most 16 chunks of at least two frames: an 8-clip shard's 160 frames in 32 chunks left partials 40 % the size
-// of the tensor itself behind every frame LayerNorm (33 MB per site, written and read again: 1.2 ms of a 33 ms step).
+// frame chunks (grid.y) of the backward kernels and of their parameter-gradient partials ([chunks][2 * per_frame] floats, summed
+// later).  32 for the large workloads: 32 x 128 = 4096 workgroups.  With 8 (1024 workgroups, each walking 224 frames at c2) the
+// kernel was as fast stand-alone (921 vs 923 us for statistics + apply) but lost CU slots to the co-resident weight-gradient GEMM
+// (DESIGN.md section 4): c2 step 342.7 -> 338.3 ms (three A/B pairs on one box; 64 chunks: 338.1).  For fewer than 512 frames at
+// most 16 chunks of at least two frames: an 8-clip shard's 160 frames in 32 chunks left partials 40 % the size of the tensor
+// itself behind every frame LayerNorm (33 MB per site, written and read again: 1.2 ms of a 33 ms step).
 static int fln_chunks(int frames) {
   if (frames >= 512) return 32;
   const int c = frames / 2 < 16 ? frames / 2 : 16;
   return c < 1 ? 1 : c;
 }
 
+// workspace of the three producers: psum [frames][FLN_PARTS][2] (unused by _apply and _pgrad), then the partial rows
+// [chunks][dw(per_frame) | db(per_frame)]
+static Partials fln_partials(const void* ws, float* dw, float* db, int frames, int per_frame, int accumulate) {
+  return make_partials(ws, (long long)frames * 2 * FLN_PARTS, frames, fln_chunks(frames), 2 * per_frame, dw, accumulate, db, per_frame);
+}
+
 extern "C" long long npvp_frameln_act_bwd_workspace_bytes(int frames, int per_frame) {
-  return ((long long)frames * 2 * FLN_PARTS + (long long)fln_chunks(frames) * 2 * per_frame) * 4;
+  return fln_partials(nullptr, nullptr, nullptr, frames, per_frame, 0).bytes;
+}
+
+// the one-pass backward from the statistics psum [frames][nparts][2], and its parameter-gradient tail
+static int fln_bwd_fused(const FlnParams& p, const float* dout, const float* psum, int nparts, float* dh, const Partials& P, int frames,
+                         int accumulate, float* amax, hipStream_t stream, const char* error) {
+  NPVP_LAUNCH(frameln_act_bwd_fused_kernel, dim3((p.per_frame / 4 + 255) / 256, P.job.nb), dim3(256), 0, stream, p,
+                     dout, psum, dh, P.part(), frames, P.per, nparts, amax);
+  NPVP_CHECK_LAUNCH();
+  return finish_partials(P.job, accumulate, stream, error);      // (2: npvp_frameln_act_bwd_reduce / _reduce_job)
 }
 
 // dh [frames, per_frame]; dw, db [per_frame]
@@ -1151,25 +1145,14 @@ extern "C" int npvp_frameln_act_bwd(const float* dout, const float* h, const flo
                                     int frames_per_sample, const unsigned long long* seed, int accumulate, float* amax,
                                     void* workspace, long long ws_bytes, hipStream_t stream) {
   NPVP_CHECK_ARG(frames > 0 && per_frame % 4 == 0, "frameln_act_bwd: bad shape");
-  NPVP_CHECK_ARG(workspace && ws_bytes >= npvp_frameln_act_bwd_workspace_bytes(frames, per_frame),
-                 "frameln_act_bwd: workspace too small");
+  const Partials P = fln_partials(workspace, dw, db, frames, per_frame, accumulate);
+  NPVP_CHECK_ARG(workspace && ws_bytes >= P.bytes, "frameln_act_bwd: workspace too small");
   FlnParams p;
   fill_fln(p, h, mean, rstd, w, b, nullptr, frames, per_frame, drop_p, salt, dp_p, dp_salt, frames_per_sample, seed);
   NPVP_CHECK_ARG(per_frame % (4 * FLN_PARTS) == 0, "frameln_act_bwd: per_frame must be a multiple of 16");
-  float* psum = (float*)workspace; float* part = psum + (long long)frames * 2 * FLN_PARTS;
-  NPVP_LAUNCH(frameln_act_bwd_stats_kernel, dim3(frames, FLN_PARTS), dim3(512), 0, stream, p, dout, psum);
+  NPVP_LAUNCH(frameln_act_bwd_stats_kernel, dim3(frames, FLN_PARTS), dim3(512), 0, stream, p, dout, (float*)workspace);
   NPVP_CHECK_LAUNCH();
-  const int chunks = fln_chunks(frames), fpc = (frames + chunks - 1) / chunks;
-  const int nchunks = (frames + fpc - 1) / fpc;
-  NPVP_LAUNCH(frameln_act_bwd_fused_kernel, dim3((per_frame / 4 + 255) / 256, nchunks), dim3(256), 0, stream, p,
-                     dout, (const float*)psum, dh, part, frames, fpc, FLN_PARTS, amax);
-  NPVP_CHECK_LAUNCH();
-  if (accumulate == 2) return NPVP_OK;      // the caller reduces the partials itself (npvp_frameln_act_bwd_reduce)
-  if (launch_sum_rows((const float*)part, dw, nchunks, 2 * per_frame, 2 * per_frame, stream, accumulate, db, per_frame)) {
-    npvp_set_error("frameln_act_bwd: reduce launch failed");
-    return NPVP_ERR_LAUNCH;
-  }
-  return NPVP_OK;
+  return fln_bwd_fused(p, dout, (const float*)workspace, FLN_PARTS, dh, P, frames, accumulate, amax, stream, "frameln_act_bwd: reduce launch failed");
 }
 
 // The same with the statistics supplied by the producer of dout: psum [frames][nparts][2] = partial (sum g, sum g*hhat)
@@ -1180,22 +1163,11 @@ extern "C" int npvp_frameln_act_bwd_apply(const float* dout, const float* h, con
                                           int frames, int per_frame, int accumulate, float* amax, void* workspace,
                                           long long ws_bytes, hipStream_t stream) {
   NPVP_CHECK_ARG(frames > 0 && per_frame % 4 == 0 && psum && nparts > 0, "frameln_act_bwd_apply: bad arguments");
-  NPVP_CHECK_ARG(workspace && ws_bytes >= npvp_frameln_act_bwd_workspace_bytes(frames, per_frame),
-                 "frameln_act_bwd_apply: workspace too small");
+  const Partials P = fln_partials(workspace, dw, db, frames, per_frame, accumulate);
+  NPVP_CHECK_ARG(workspace && ws_bytes >= P.bytes, "frameln_act_bwd_apply: workspace too small");
   FlnParams p;
   fill_fln(p, h, mean, rstd, w, b, nullptr, frames, per_frame, 0.f, 0u, 0.f, 0u, 1, nullptr);
-  float* part = (float*)workspace + (long long)frames * 2 * FLN_PARTS;
-  const int chunks = fln_chunks(frames), fpc = (frames + chunks - 1) / chunks;
-  const int nchunks = (frames + fpc - 1) / fpc;
-  NPVP_LAUNCH(frameln_act_bwd_fused_kernel, dim3((per_frame / 4 + 255) / 256, nchunks), dim3(256), 0, stream, p,
-                     dout, psum, dh, part, frames, fpc, nparts, amax);
-  NPVP_CHECK_LAUNCH();
-  if (accumulate == 2) return NPVP_OK;
-  if (launch_sum_rows((const float*)part, dw, nchunks, 2 * per_frame, 2 * per_frame, stream, accumulate, db, per_frame)) {
-    npvp_set_error("frameln_act_bwd_apply: reduce launch failed");
-    return NPVP_ERR_LAUNCH;
-  }
-  return NPVP_OK;
+  return fln_bwd_fused(p, dout, psum, nparts, dh, P, frames, accumulate, amax, stream, "frameln_act_bwd_apply: reduce launch failed");
 }
 
 // Statistics and parameter gradients only (see frameln_act_bwd_pgrad_kernel): psum [frames][per_frame / 1024][2] receives the
@@ -1206,41 +1178,24 @@ extern "C" int npvp_frameln_act_bwd_pgrad(const float* dout, const float* h, con
                                           const unsigned long long* seed, int accumulate, void* workspace, long long ws_bytes,
                                           hipStream_t stream) {
   NPVP_CHECK_ARG(frames > 0 && per_frame % 1024 == 0 && psum, "frameln_act_bwd_pgrad: per_frame must be a multiple of 1024");
-  NPVP_CHECK_ARG(workspace && ws_bytes >= npvp_frameln_act_bwd_workspace_bytes(frames, per_frame),
-                 "frameln_act_bwd_pgrad: workspace too small");
+  const Partials P = fln_partials(workspace, dw, db, frames, per_frame, accumulate);
+  NPVP_CHECK_ARG(workspace && ws_bytes >= P.bytes, "frameln_act_bwd_pgrad: workspace too small");
   FlnParams p;
   fill_fln(p, h, mean, rstd, w, b, nullptr, frames, per_frame, drop_p, salt, dp_p, dp_salt, frames_per_sample, seed);
-  float* part = (float*)workspace + (long long)frames * 2 * FLN_PARTS;
-  const int chunks = fln_chunks(frames), fpc = (frames + chunks - 1) / chunks;
-  const int nchunks = (frames + fpc - 1) / fpc;
-  NPVP_LAUNCH(frameln_act_bwd_pgrad_kernel, dim3(per_frame / 1024, nchunks), dim3(256), 0, stream, p, dout, psum, part,
-                     frames, fpc);
+  NPVP_LAUNCH(frameln_act_bwd_pgrad_kernel, dim3(per_frame / 1024, P.job.nb), dim3(256), 0, stream, p, dout, psum,
+                     P.part(), frames, P.per);
   NPVP_CHECK_LAUNCH();
-  if (accumulate == 2) return NPVP_OK;
-  if (launch_sum_rows((const float*)part, dw, nchunks, 2 * per_frame, 2 * per_frame, stream, accumulate, db, per_frame)) {
-    npvp_set_error("frameln_act_bwd_pgrad: reduce launch failed");
-    return NPVP_ERR_LAUNCH;
-  }
-  return NPVP_OK;
+  return finish_partials(P.job, accumulate, stream, "frameln_act_bwd_pgrad: reduce launch failed");
 }
 
 extern "C" int npvp_frameln_act_bwd_reduce_job(const void* workspace, float* dw, float* db, int frames, int per_frame, int accumulate,
                                                void* job) {
   NPVP_CHECK_ARG(workspace && dw && db && frames > 0 && job, "frameln_act_bwd_reduce_job: bad arguments");
-  const int chunks = fln_chunks(frames), fpc = (frames + chunks - 1) / chunks, nchunks = (frames + fpc - 1) / fpc;
-  const float* part = (const float*)workspace + 2 * FLN_PARTS * (long long)frames;
-  fill_job(job, part, dw, db, nchunks, 2 * per_frame, 2 * per_frame, per_frame, accumulate ? 1 : 0, 0);
-  return NPVP_OK;
+  return put_job(job, fln_partials(workspace, dw, db, frames, per_frame, accumulate).job);
 }
 
 extern "C" int npvp_frameln_act_bwd_reduce(const void* workspace, float* dw, float* db, int frames, int per_frame,
                                            int accumulate, hipStream_t stream) {
   NPVP_CHECK_ARG(workspace && dw && db && frames > 0, "frameln_act_bwd_reduce: bad arguments");
-  const int chunks = fln_chunks(frames), fpc = (frames + chunks - 1) / chunks, nchunks = (frames + fpc - 1) / fpc;
-  const float* part = (const float*)workspace + 2 * FLN_PARTS * (long long)frames;
-  if (launch_sum_rows(part, dw, nchunks, 2 * per_frame, 2 * per_frame, stream, accumulate ? 1 : 0, db, per_frame)) {
-    npvp_set_error("frameln_act_bwd_reduce: launch failed");
-    return NPVP_ERR_LAUNCH;
-  }
-  return NPVP_OK;
+  return finish_partials(fln_partials(workspace, dw, db, frames, per_frame, accumulate).job, 0, stream, "frameln_act_bwd_reduce: launch failed");
 }

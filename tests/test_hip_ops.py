@@ -524,6 +524,53 @@ def test_frame_ln_parameter_gradient_reduction_wide_sets(K, frames):
         assert torch.equal(dw, dw2) and torch.equal(db, db2), "queued form differs from the single launch"
 
 
+@pytest.mark.parametrize("family,shape", [("layernorm", (2048, 512)), ("layernorm", (253, 1024)), ("layernorm", (20480, 256)),
+                                          ("middle", (160, 512)), ("middle", (64, 512)),
+                                          ("middle", (160, 1024)), ("middle", (160, 2048)), ("middle", (3584, 2048))])
+def test_parameter_gradient_reduction_queued_equals_direct(K, family, shape):
+    """The sibling of the test above for the sets the float4 path does not take, in the classes where the sum-rows plan
+    (csrc/norm.hip plan_sum_rows) gives the direct and the queued form the same split of the partial rows over row lanes: 64 or more
+    partial rows on 16-column blocks (LayerNorm from 253 token rows; the MlpDWBN middle at Ch 512, 10 Ch <= 8192 columns) and on
+    64-column blocks of 1024 threads (the middle at Ch >= 1024).  Direct = npvp_layernorm_bwd_reduce / npvp_mlpdw_mid_bwd_reduce,
+    queued = *_reduce_job + npvp_sum_rows_multi: bit-identical, accumulate on and off; the middle's job writes the Conv2d layout
+    (gw [Ch][9], gb [Ch], always accumulating), the same sums as the direct [10][Ch] form transposed.  Below 64 partial rows the
+    direct launch has 4 row lanes and the queued one 16, and npvp_mlpdw_mid_bwd_reduce_into walks the chunks serially: equal to
+    rounding, not asserted here.  Every sum is also within the worst-case bound of an fp32 sum of nb terms (nb 2^-24 sum |x|) of
+    the fp64 sum."""
+    import ctypes
+    from npvp_amd import ops
+    from npvp_amd.sched import _ptr, _stream
+    L = ops.lib()
+    n, c = shape
+    job = ctypes.create_string_buffer(48)
+    if family == "layernorm":
+        nbytes, ncols = L.npvp_layernorm_bwd_workspace_bytes(n, c), 2 * c
+    else:
+        nbytes, ncols = L.npvp_mlpdw_mid_bwd_workspace_bytes(n, c), 10 * c
+    ws = O.seeded_randn((nbytes // 4,), 411 + n + c).to(DEV)
+    base = O.seeded_randn((ncols,), 7).to(DEV)
+    for accumulate in ((0, 1) if family == "layernorm" else (1,)):
+        d, q = base.clone(), base.clone()
+        if family == "layernorm":
+            assert L.npvp_layernorm_bwd_reduce(_ptr(ws), _ptr(d), _ptr(d) + 4 * c, n, c, accumulate, _stream()) == 0
+            assert L.npvp_layernorm_bwd_reduce_job(_ptr(ws), _ptr(q), _ptr(q) + 4 * c, n, c, accumulate, ctypes.addressof(job)) == 0
+        else:
+            q = torch.cat([base[:9 * c].view(9, c).t().reshape(-1), base[9 * c:]])               # gw [Ch][9] | gb [Ch]
+            assert L.npvp_mlpdw_mid_bwd_reduce(_ptr(ws), _ptr(d), n, c, accumulate, _stream()) == 0
+            assert L.npvp_mlpdw_mid_bwd_reduce_job(_ptr(ws), _ptr(q), _ptr(q) + 4 * 9 * c, n, c, ctypes.addressof(job)) == 0
+        nb = int.from_bytes(job.raw[24:28], "little")
+        assert nb >= 64 and int.from_bytes(job.raw[32:36], "little") == ncols and nb * ncols * 4 <= nbytes
+        assert L.npvp_sum_rows_multi(ctypes.addressof(job), 1, _stream()) == 0
+        torch.cuda.synchronize()
+        if family == "middle":
+            q = torch.cat([q[:9 * c].view(c, 9).t().reshape(-1), q[9 * c:]])
+        assert torch.equal(d, q), f"queued form differs from the single launch (accumulate {accumulate})"
+        part = ws[:nb * ncols].view(nb, ncols).double()
+        want = part.sum(0) + (base.double() if accumulate else 0)
+        bound = (nb + 1) * 2.0 ** -24 * (part.abs().sum(0) + base.double().abs())
+        assert bool(((d.double() - want).abs() <= bound).all())
+
+
 def test_library_exchange_entry_points(K):
     """include/npvp_hip.h npvp_dp_*: a communicator of ONE rank on this card (all a one-GPU box allows): id, init, an in-place
     all-reduce(mean) on a side stream, the compute stream ordered behind it by npvp_dp_wait, finalize - and the error returns

@@ -1,5 +1,6 @@
 """Kernel launch ORDER of a rocprofv3 --kernel-trace run (rocpd sqlite), compact: python tools/rocpd_order.py <db> [first] [count]
-prints `count` consecutive dispatches starting at index `first` (default: the last 400) as  stream  name  duration_us"""
+prints `count` consecutive dispatches starting at index `first` (default: the last 400) as  stream  name  duration_us;
+python tools/rocpd_order.py <db> --geometry prints every dispatch as  name  grid  workgroup size, without times"""
 import re
 import sqlite3
 import sys
@@ -10,6 +11,11 @@ cols = [r[1] for r in db.execute(f"pragma table_info({view})")]
 name_c = "name" if "name" in cols else "kernel_name"
 rows = list(db.execute(f"select {name_c}, start, end, stream_id from {view} order by start")) if "stream_id" in cols else \
     [r + (0,) for r in db.execute(f"select {name_c}, start, end from {view} order by start")]
+if len(sys.argv) > 2 and sys.argv[2] == "--geometry":      # every dispatch as  name  grid  workgroup: no times, for a diff of two runs
+    geo = [c for c in cols if re.match(r"(grid|workgroup)(_size)?_?[xyz]$", c)]
+    for r in db.execute(f"select {name_c}, {', '.join(geo)} from {view} order by start"):
+        print(re.sub(r"^void ", "", r[0]).replace("npvp::", ""), *r[1:])
+    sys.exit(0)
 first = int(sys.argv[2]) if len(sys.argv) > 2 else max(0, len(rows) - 400)
 count = int(sys.argv[3]) if len(sys.argv) > 3 else 400
 for n, s, e, st in rows[first:first + count]:
