@@ -463,6 +463,27 @@ int npvp_bn_act_apply(const float* x, const float* w, const float* b, const floa
 int npvp_bn_act_bwd(const float* g, const float* x, const float* mean, const float* rstd, const float* w, const float* b, long long outer,
                     long long inner, int C, int layout, int act, int train, float* dx, float* dw, float* db, void* workspace,
                     long long ws_bytes, npvp_stream_t stream);
+/* Synchronised BatchNorm for data-parallel Stage-1 training - what Lightning's `sync_batchnorm=True` beside the DDP strategy
+ * (ref/train_AutoEncoder_lightning.py:40-42) makes of the BatchNorm2d layers of ref/models/ResNetAutoEncoder.py:76-130,168-175,239-249:
+ * the two passes above, cut where the per-channel sums cross the ranks.  The caller all-reduces (sum) the double buffers in between.
+ * bn_act_apply_sync: bn_act_apply in training mode from stat[2C+1] (device, double) = [sum x (C), sum x^2 (C), n]: bn_stats' sums
+ *   followed by the element count per channel, all three summed over the ranks.  n is read on the device (shards may be uneven);
+ *   mean, rstd, the running-statistic update (unbiased variance with the TOTAL n) and the apply pass follow from it.
+ * bn_bwd_sums: the first half of bn_act_bwd over this rank's rows: sums[2C] (device, double) = [sum g' (C), sum g' xhat (C)], and
+ *   dw / db (float) from these LOCAL sums - the gradient all-reduce (mean over ranks) completes them as it does every other parameter's.
+ * bn_act_bwd_apply: the second half: dx = w rstd (g' - sum g'/n - xhat sum g' xhat / n) from the all-reduced sums[2C] and the device
+ *   count n (one double: stat + 2C kept from the forward).
+ * Given this rank's own sums and count, the three calls produce the same bits as bn_act_apply / bn_act_bwd (y, mean, rstd, running
+ * statistics, dx, dw, db).  Same layouts, shape rules, alignment and workspace as above; deterministic, no zero-filled buffer. */
+int npvp_bn_act_apply_sync(const float* x, const float* w, const float* b, const float* residual, const double* stat, float eps,
+                           float momentum, float* running_mean, float* running_var, long long outer, long long inner, int C, int layout,
+                           int act, float* y, float* mean, float* rstd, npvp_stream_t stream);
+int npvp_bn_bwd_sums(const float* g, const float* x, const float* mean, const float* rstd, const float* w, const float* b, long long outer,
+                     long long inner, int C, int layout, int act, double* sums, float* dw, float* db, void* workspace, long long ws_bytes,
+                     npvp_stream_t stream);
+int npvp_bn_act_bwd_apply(const float* g, const float* x, const float* mean, const float* rstd, const float* w, const float* b,
+                          const double* sums, const double* count, long long outer, long long inner, int C, int layout, int act, float* dx,
+                          npvp_stream_t stream);
 /* ReflectionPad2d(P) (ref/models/ResNetAutoEncoder.py:72, :187, :234-236): layout 1 x [planes = N*C][H][W] -> y [planes][H+2P][W+2P];
  * layout 0 x [planes = N][H][W][C] -> y [N][H+2P][W+2P][C].  backward = 1: x is the padded gradient, y the input gradient, each
  * input pixel the fixed-order sum of the padded pixels that read it (no atomics).  1 <= P < H, W. */

@@ -36,7 +36,7 @@ from .models import (Predictor, VidHRFormerEncoder, VidHRformerDecoderNAR, VidHR
 from .trainer import (FlatAdamW, predictor_train_step, full_train_step, predictor_val_step, full_val_step, cosine_warm_restarts_lr, build_predictor_from_cfg,
                       context_lists, rand_context_collate, rand_context_batch_process, vfi_batch_process,
                       save_lightning_checkpoint, load_lightning_checkpoint, GraphedTrainStep,
-                      AEPair, ae_optimizer, ae_train_step, ae_val_step, save_ae_checkpoint, load_ae_checkpoint)
+                      AEPair, ae_optimizer, ae_train_step, ae_data_parallel, ae_val_step, save_ae_checkpoint, load_ae_checkpoint)
 from . import ops
 from . import metrics, data
 
@@ -46,5 +46,5 @@ __all__ = ["Predictor", "VidHRFormerEncoder", "VidHRformerDecoderNAR", "VidHRFor
            "rand_context_collate", "rand_context_batch_process", "vfi_batch_process",
            "save_lightning_checkpoint", "load_lightning_checkpoint", "GraphedTrainStep",
            "cosine_warm_restarts_lr", "build_predictor_from_cfg", "ops", "metrics", "data",
-           "build_autoencoder", "prepare_trainable_autoencoder", "AEPair", "ae_optimizer", "ae_train_step", "ae_val_step",
+           "build_autoencoder", "prepare_trainable_autoencoder", "AEPair", "ae_optimizer", "ae_train_step", "ae_data_parallel", "ae_val_step",
            "save_ae_checkpoint", "load_ae_checkpoint"]

@@ -116,6 +116,9 @@ SIGNATURES = {
     "npvp_bn_stats": (c_int, [c_p, c_ll, c_ll, c_int, c_int, c_p, c_p, c_ll, c_p]),
     "npvp_bn_act_apply": (c_int, [c_p, c_p, c_p, c_p, c_p, c_ll, c_f, c_f, c_p, c_p, c_ll, c_ll, c_int, c_int, c_int, c_p, c_p, c_p, c_p]),
     "npvp_bn_act_bwd": (c_int, [c_p, c_p, c_p, c_p, c_p, c_p, c_ll, c_ll, c_int, c_int, c_int, c_int, c_p, c_p, c_p, c_p, c_ll, c_p]),
+    "npvp_bn_act_apply_sync": (c_int, [c_p, c_p, c_p, c_p, c_p, c_f, c_f, c_p, c_p, c_ll, c_ll, c_int, c_int, c_int, c_p, c_p, c_p, c_p]),
+    "npvp_bn_bwd_sums": (c_int, [c_p, c_p, c_p, c_p, c_p, c_p, c_ll, c_ll, c_int, c_int, c_int, c_p, c_p, c_p, c_p, c_ll, c_p]),
+    "npvp_bn_act_bwd_apply": (c_int, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_ll, c_ll, c_int, c_int, c_int, c_p, c_p]),
     "npvp_reflect_pad": (c_int, [c_p, c_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_p]),
     "npvp_nonlocal_attn_fwd": (c_int, [c_p, c_ll, c_p, c_ll, c_p, c_ll, c_p, c_ll, c_p, c_int, c_int, c_int, c_int, c_int, c_p]),
     "npvp_nonlocal_attn_bwd": (c_int, [c_p, c_ll, c_p, c_ll, c_p, c_ll, c_p, c_ll, c_p, c_p, c_p, c_ll, c_p, c_ll, c_p, c_ll, c_int, c_int,

@@ -3,6 +3,9 @@
 //   - training-mode BatchNorm2d fused with its ReLU and skip-add: statistics (fixed-order two-level sums in double, no atomics, no
 //     memset) and apply are separate entry points, so that a data-parallel caller can all-reduce [sum x, sum x^2] in between;
 //   - its backward: fixed-order sums of g' and g' * xhat, then one pass dx = w rstd (g' - sum g'/n - xhat sum g' xhat / n);
+//   - the same two passes cut where synchronised BatchNorm exchanges (Lightning's sync_batchnorm=True,
+//     ref/train_AutoEncoder_lightning.py:40-42): the forward from stat[2C+1] = [sum x, sum x^2, n] and the backward's dx from
+//     sums[2C] = [sum g', sum g' xhat], both all-reduced by the caller, the element count n read on the device (uneven shards);
 //   - the non-local attention core softmax(q k^T) v (unscaled scores) with the 2x2 max-pool of K / V fused into the loads, flash
 //     style: online softmax forward, recomputation backward, the HW x HW/4 score matrix never leaves LDS; each pooled K / V gradient
 //     goes to its window's arg-max (first maximum in row-major window order, as torch's max_pool2d);
@@ -125,12 +128,14 @@ __global__ void __launch_bounds__(64) bn_part_reduce_kernel(const double* __rest
 }
 
 // mean / rstd per channel: from the sums (training: batch statistics, running statistics updated as torch does - momentum,
-// unbiased variance) or, with sums == null, from the running statistics (eval)
-__global__ void bn_finalize_kernel(const double* __restrict__ sums, double count, float eps, float momentum,
-                                   float* __restrict__ running_mean, float* __restrict__ running_var, int C, float* __restrict__ mean,
-                                   float* __restrict__ rstd) {
+// unbiased variance) or, with sums == null, from the running statistics (eval).  The element count per channel is `count`, or
+// *count_dev when given (synchronised BatchNorm: the all-reduced total, known on the device only)
+__global__ void bn_finalize_kernel(const double* __restrict__ sums, double count, const double* __restrict__ count_dev, float eps,
+                                   float momentum, float* __restrict__ running_mean, float* __restrict__ running_var, int C,
+                                   float* __restrict__ mean, float* __restrict__ rstd) {
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= C) return;
+  if (count_dev) count = *count_dev;
   if (sums) {
     const double m = sums[c] / count;
     double var = sums[C + c] / count - m * m;
@@ -171,13 +176,25 @@ __device__ __forceinline__ float bn_dx(float x, float g, float mu, float rs, flo
 
 // elementwise passes (forward apply / backward dx).  layout 0: C4 = C/4 divides 256, each thread keeps its 4 channels' coefficients
 // and strides over rows; layout 1: one block per plane (n, c), float4 over H*W.
+// BWD 0: forward; 1: dx from this call's own dw / db (float) and the host's 1/n; 2: dx from all-reduced rsums[2][C] (double) and the
+// device count *rcount, rounded to float exactly as BWD 1 rounds them (the same bits when the sums are this rank's own)
+template <int BWD>
+__device__ __forceinline__ void bn_k(const float* __restrict__ dw, const float* __restrict__ db, const double* __restrict__ rsums,
+                                     float inv_n, int c, int C, float& k1, float& k2) {
+  if (BWD == 2) { k1 = (float)rsums[c] * inv_n; k2 = (float)rsums[C + c] * inv_n; }
+  else if (BWD == 1) { k1 = db[c] * inv_n; k2 = dw[c] * inv_n; }
+  else { k1 = 0.f; k2 = 0.f; }
+}
+
 template <int BWD>
 __global__ void __launch_bounds__(256) bn_elem_rows_kernel(const float* __restrict__ x, const float* __restrict__ g,
                                                            const float* __restrict__ res, const float* __restrict__ mean,
                                                            const float* __restrict__ rstd, const float* __restrict__ w,
                                                            const float* __restrict__ b, const float* __restrict__ dw,
-                                                           const float* __restrict__ db, float inv_n, int act, int train, long long R,
-                                                           int C, float* __restrict__ out) {
+                                                           const float* __restrict__ db, const double* __restrict__ rsums,
+                                                           const double* __restrict__ rcount, float inv_n, int act, int train,
+                                                           long long R, int C, float* __restrict__ out) {
+  if (BWD == 2) inv_n = (float)(1.0 / *rcount);
   const int C4 = C >> 2;
   const int rpb = 256 / C4;
   const int c = (threadIdx.x % C4) * 4;
@@ -186,8 +203,7 @@ __global__ void __launch_bounds__(256) bn_elem_rows_kernel(const float* __restri
   for (int u = 0; u < 4; ++u) {
     bn_coef(mean, rstd, w, b, c + u, sc[u], sh[u]);
     mu[u] = mean[c + u]; rs[u] = rstd[c + u];
-    k1[u] = BWD ? db[c + u] * inv_n : 0.f;
-    k2[u] = BWD ? dw[c + u] * inv_n : 0.f;
+    bn_k<BWD>(dw, db, rsums, inv_n, c + u, C, k1[u], k2[u]);
   }
   for (long long r = (long long)blockIdx.x * rpb + threadIdx.x / C4; r < R; r += (long long)gridDim.x * rpb) {
     const long long e = r * C + c;
@@ -212,14 +228,17 @@ __global__ void __launch_bounds__(256) bn_elem_planes_kernel(const float* __rest
                                                              const float* __restrict__ res, const float* __restrict__ mean,
                                                              const float* __restrict__ rstd, const float* __restrict__ w,
                                                              const float* __restrict__ b, const float* __restrict__ dw,
-                                                             const float* __restrict__ db, float inv_n, int act, int train, int C,
-                                                             int HW, float* __restrict__ out) {
+                                                             const float* __restrict__ db, const double* __restrict__ rsums,
+                                                             const double* __restrict__ rcount, float inv_n, int act, int train,
+                                                             int C, int HW, float* __restrict__ out) {
+  if (BWD == 2) inv_n = (float)(1.0 / *rcount);
   const int plane = blockIdx.x;
   const int c = plane % C;
   float sc, sh;
   bn_coef(mean, rstd, w, b, c, sc, sh);
   const float mu = mean[c], rs = rstd[c];
-  const float k1 = BWD ? db[c] * inv_n : 0.f, k2 = BWD ? dw[c] * inv_n : 0.f;
+  float k1, k2;
+  bn_k<BWD>(dw, db, rsums, inv_n, c, C, k1, k2);
   const long long base = (long long)plane * HW;
   for (int i = threadIdx.x * 4; i < HW; i += 1024) {
     const float4 v = ld4(x + base + i);
@@ -652,14 +671,14 @@ extern "C" int npvp_bn_act_apply(const float* x, const float* w, const float* b,
   NPVP_CHECK_ARG(sums ? count >= 1 : (running_mean && running_var), "bn_act_apply: sums + count, or running statistics (eval)");
   NPVP_CHECK_ARG((running_mean == nullptr) == (running_var == nullptr), "bn_act_apply: running_mean and running_var together");
   NPVP_CHECK_ARG((((uintptr_t)x | (uintptr_t)y | (uintptr_t)residual) & 15) == 0, "bn_act_apply: buffers must be 16-byte aligned");
-  NPVP_LAUNCH(bn_finalize_kernel, dim3((C + 255) / 256), dim3(256), 0, stream, sums, (double)count, eps, momentum, running_mean, running_var, C,
-              mean, rstd);
+  NPVP_LAUNCH(bn_finalize_kernel, dim3((C + 255) / 256), dim3(256), 0, stream, sums, (double)count, nullptr, eps, momentum, running_mean,
+              running_var, C, mean, rstd);
   if (layout == 0)
     NPVP_LAUNCH(bn_elem_rows_kernel<0>, dim3(clampi((outer * C / 4 + 255) / 256, 1, 8192)), dim3(256), 0, stream, x, nullptr, residual,
-                mean, rstd, w, b, nullptr, nullptr, 0.f, act, 1, outer, C, y);
+                mean, rstd, w, b, nullptr, nullptr, nullptr, nullptr, 0.f, act, 1, outer, C, y);
   else
     NPVP_LAUNCH(bn_elem_planes_kernel<0>, dim3((unsigned)outer), dim3(256), 0, stream, x, nullptr, residual, mean, rstd, w, b, nullptr,
-                nullptr, 0.f, act, 1, C, (int)inner, y);
+                nullptr, nullptr, nullptr, 0.f, act, 1, C, (int)inner, y);
   NPVP_CHECK_LAUNCH();
   return NPVP_OK;
 }
@@ -678,10 +697,71 @@ extern "C" int npvp_bn_act_bwd(const float* g, const float* x, const float* mean
   const float inv_n = (float)(1.0 / (double)(outer * inner / C));
   if (layout == 0)
     NPVP_LAUNCH(bn_elem_rows_kernel<1>, dim3(clampi((outer * C / 4 + 255) / 256, 1, 8192)), dim3(256), 0, stream, x, g, nullptr, mean,
-                rstd, w, b, dw, db, inv_n, act, train, outer, C, dx);
+                rstd, w, b, dw, db, nullptr, nullptr, inv_n, act, train, outer, C, dx);
   else
-    NPVP_LAUNCH(bn_elem_planes_kernel<1>, dim3((unsigned)outer), dim3(256), 0, stream, x, g, nullptr, mean, rstd, w, b, dw, db, inv_n, act,
-                train, C, (int)inner, dx);
+    NPVP_LAUNCH(bn_elem_planes_kernel<1>, dim3((unsigned)outer), dim3(256), 0, stream, x, g, nullptr, mean, rstd, w, b, dw, db, nullptr,
+                nullptr, inv_n, act, train, C, (int)inner, dx);
+  NPVP_CHECK_LAUNCH();
+  return NPVP_OK;
+}
+
+// ---- synchronised BatchNorm (Lightning's sync_batchnorm=True, ref/train_AutoEncoder_lightning.py:40-42): the two passes above cut at
+// the point where the per-channel sums cross the ranks.  With this rank's own sums and count they give the bits of the calls above.
+
+extern "C" int npvp_bn_act_apply_sync(const float* x, const float* w, const float* b, const float* residual, const double* stat, float eps,
+                                      float momentum, float* running_mean, float* running_var, long long outer, long long inner, int C,
+                                      int layout, int act, float* y, float* mean, float* rstd, hipStream_t stream) {
+  NPVP_CHECK_ARG(stat, "bn_act_apply_sync: null stat (device [sum x, sum x^2, n], 2C+1 doubles)");
+  NPVP_CHECK_ARG(x && w && b && y && mean && rstd, "bn_act_apply_sync: null buffer");
+  if (int rc = bn_check_shape(outer, inner, C, layout)) return rc;
+  NPVP_CHECK_ARG(act == 0 || act == 1, "bn_act_apply_sync: act 0 (none) or 1 (ReLU)");
+  NPVP_CHECK_ARG((running_mean == nullptr) == (running_var == nullptr), "bn_act_apply_sync: running_mean and running_var together");
+  NPVP_CHECK_ARG((((uintptr_t)x | (uintptr_t)y | (uintptr_t)residual) & 15) == 0, "bn_act_apply_sync: buffers must be 16-byte aligned");
+  NPVP_CHECK_ARG(((uintptr_t)stat & 7) == 0, "bn_act_apply_sync: stat must be 8-byte aligned");
+  NPVP_LAUNCH(bn_finalize_kernel, dim3((C + 255) / 256), dim3(256), 0, stream, stat, 0.0, stat + 2 * C, eps, momentum, running_mean,
+              running_var, C, mean, rstd);
+  if (layout == 0)
+    NPVP_LAUNCH(bn_elem_rows_kernel<0>, dim3(clampi((outer * C / 4 + 255) / 256, 1, 8192)), dim3(256), 0, stream, x, nullptr, residual,
+                mean, rstd, w, b, nullptr, nullptr, nullptr, nullptr, 0.f, act, 1, outer, C, y);
+  else
+    NPVP_LAUNCH(bn_elem_planes_kernel<0>, dim3((unsigned)outer), dim3(256), 0, stream, x, nullptr, residual, mean, rstd, w, b, nullptr,
+                nullptr, nullptr, nullptr, 0.f, act, 1, C, (int)inner, y);
+  NPVP_CHECK_LAUNCH();
+  return NPVP_OK;
+}
+
+extern "C" int npvp_bn_bwd_sums(const float* g, const float* x, const float* mean, const float* rstd, const float* w, const float* b,
+                                long long outer, long long inner, int C, int layout, int act, double* sums, float* dw, float* db,
+                                void* workspace, long long ws_bytes, hipStream_t stream) {
+  NPVP_CHECK_ARG(sums, "bn_bwd_sums: null sums (device [sum g', sum g' xhat], 2C doubles)");
+  NPVP_CHECK_ARG(g && x && mean && rstd && w && b && dw && db && workspace, "bn_bwd_sums: null buffer");
+  if (int rc = bn_check_shape(outer, inner, C, layout)) return rc;
+  NPVP_CHECK_ARG(act == 0 || act == 1, "bn_bwd_sums: act 0 (none) or 1 (ReLU)");
+  NPVP_CHECK_ARG((((uintptr_t)x | (uintptr_t)g) & 15) == 0, "bn_bwd_sums: buffers must be 16-byte aligned");
+  NPVP_CHECK_ARG(((uintptr_t)sums & 7) == 0, "bn_bwd_sums: sums must be 8-byte aligned");
+  NPVP_CHECK_ARG(ws_bytes >= npvp_bn_workspace_bytes(C), "bn_bwd_sums: workspace too small (npvp_bn_workspace_bytes)");
+  if (int rc = bn_sums<1>(x, g, mean, rstd, w, b, act, outer, inner, C, layout, sums, workspace, ws_bytes, stream)) return rc;
+  NPVP_LAUNCH(bn_bwd_finalize_kernel, dim3((C + 255) / 256), dim3(256), 0, stream, sums, C, dw, db);
+  NPVP_CHECK_LAUNCH();
+  return NPVP_OK;
+}
+
+extern "C" int npvp_bn_act_bwd_apply(const float* g, const float* x, const float* mean, const float* rstd, const float* w, const float* b,
+                                     const double* sums, const double* count, long long outer, long long inner, int C, int layout,
+                                     int act, float* dx, hipStream_t stream) {
+  NPVP_CHECK_ARG(sums, "bn_act_bwd_apply: null sums (device [sum g', sum g' xhat], 2C doubles, all-reduced)");
+  NPVP_CHECK_ARG(count, "bn_act_bwd_apply: null count (device double: the elements per channel over all ranks)");
+  NPVP_CHECK_ARG(g && x && mean && rstd && w && b && dx, "bn_act_bwd_apply: null buffer");
+  if (int rc = bn_check_shape(outer, inner, C, layout)) return rc;
+  NPVP_CHECK_ARG(act == 0 || act == 1, "bn_act_bwd_apply: act 0 (none) or 1 (ReLU)");
+  NPVP_CHECK_ARG((((uintptr_t)x | (uintptr_t)g | (uintptr_t)dx) & 15) == 0, "bn_act_bwd_apply: buffers must be 16-byte aligned");
+  NPVP_CHECK_ARG((((uintptr_t)sums | (uintptr_t)count) & 7) == 0, "bn_act_bwd_apply: sums / count must be 8-byte aligned");
+  if (layout == 0)
+    NPVP_LAUNCH(bn_elem_rows_kernel<2>, dim3(clampi((outer * C / 4 + 255) / 256, 1, 8192)), dim3(256), 0, stream, x, g, nullptr, mean,
+                rstd, w, b, nullptr, nullptr, sums, count, 0.f, act, 1, outer, C, dx);
+  else
+    NPVP_LAUNCH(bn_elem_planes_kernel<2>, dim3((unsigned)outer), dim3(256), 0, stream, x, g, nullptr, mean, rstd, w, b, nullptr, nullptr,
+                sums, count, 0.f, act, 1, C, (int)inner, dx);
   NPVP_CHECK_LAUNCH();
   return NPVP_OK;
 }

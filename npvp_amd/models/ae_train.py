@@ -12,7 +12,7 @@ import types
 import torch
 import torch.nn as nn
 
-from .. import ops
+from .. import dp, ops
 from .ResNetAutoEncoder import ResnetEncoder, ResnetDecoder, Factorized3DConvAttn, NonLocalAttenion2D, ResnetBlock
 
 
@@ -27,13 +27,16 @@ def build_autoencoder(AE, img_channels):
 
 
 def _bn(bn, x, act, residual=None):
-    """BatchNorm2d (+ ReLU) (+ residual) with nn.BatchNorm2d's own mode logic (ref: torch.nn.modules.batchnorm._BatchNorm.forward)"""
+    """BatchNorm2d (+ ReLU) (+ residual) with nn.BatchNorm2d's own mode logic (ref: torch.nn.modules.batchnorm._BatchNorm.forward).
+    A dp.SyncBatchNorm2d in training mode under data parallelism takes its statistics over every rank (Lightning's
+    sync_batchnorm=True, ref/train_AutoEncoder_lightning.py:40-42); a plain BatchNorm2d keeps this rank's own, as torch does."""
     if bn.training and bn.track_running_stats and bn.num_batches_tracked is not None:
         bn.num_batches_tracked.add_(1)
     train = bn.training or bn.running_mean is None
     w = bn.weight if bn.weight is not None else torch.ones(bn.num_features, device=x.device)
     b = bn.bias if bn.bias is not None else torch.zeros(bn.num_features, device=x.device)
-    return ops.bn_act_train(x, w, b, bn.running_mean, bn.running_var, bn.momentum, bn.eps, act, train, residual)
+    group = dp.syncbn_group() if isinstance(bn, dp.SyncBatchNorm2d) and bn.training and dp.active() else None
+    return ops.bn_act_train(x, w, b, bn.running_mean, bn.running_var, bn.momentum, bn.eps, act, train, residual, group=group)
 
 
 def _pad_size(m):
@@ -130,7 +133,8 @@ def _decoder_forward(dec, x):
 
 def prepare_trainable_autoencoder(enc, dec, channels_last=True):
     """Route the pair's forward through the HIP training ops (in place, on these two instances); state-dict keys are unchanged.
-    Train mode: batch statistics (running statistics updated); eval mode: running statistics.  channels_last: the encoder's
+    Train mode: batch statistics (running statistics updated; over all ranks for layers converted by dp.convert_sync_batchnorm /
+    ae_data_parallel); eval mode: running statistics.  channels_last: the encoder's
     activations run in torch.channels_last memory (BatchNorm layout 0; the attention's token matrix is then a view), the decoder's
     stay NCHW (layout 1), as in the frozen path (to_device_layout).  Returns (enc, dec)."""
     if not isinstance(enc, ResnetEncoder) or not isinstance(dec, ResnetDecoder):

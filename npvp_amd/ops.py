@@ -1889,10 +1889,14 @@ def _like_layout(t, layout):
 
 class _BnActTrain(torch.autograd.Function):
     """BatchNorm2d (batch statistics in training, running statistics in eval) -> act (0 none, 1 ReLU) [-> + residual] as one
-    statistics pass and one apply pass forward, one sum pass and one dx pass backward (npvp_bn_*)."""
+    statistics pass and one apply pass forward, one sum pass and one dx pass backward (npvp_bn_*).
+    group (training mode only; synchronised BatchNorm, Lightning's sync_batchnorm=True, ref/train_AutoEncoder_lightning.py:40-42):
+    the statistics span the ranks of that process group - ONE all-reduce of [sum x, sum x^2, n] (double) between the statistics pass
+    and the apply pass, one of [sum g', sum g' xhat] between the backward's two passes (npvp_bn_act_apply_sync / npvp_bn_bwd_sums /
+    npvp_bn_act_bwd_apply).  dw / db stay this rank's own sums: the gradient all-reduce finishes them."""
 
     @staticmethod
-    def forward(ctx, x, w, b, residual, running_mean, running_var, momentum, eps, act, train):
+    def forward(ctx, x, w, b, residual, running_mean, running_var, momentum, eps, act, train, group=None):
         remember(ctx)
         _chk(x, w, b, residual, running_mean, running_var)
         if x.dim() != 4:
@@ -1914,12 +1918,27 @@ class _BnActTrain(torch.autograd.Function):
         mean = torch.empty(C, dtype=torch.float32, device=x.device)
         rstd = torch.empty_like(mean)
         sums, count = None, 0
+        upd = train and running_mean is not None
+        ctx.group = group if train else None
+        if ctx.group is not None:
+            from . import dp
+            import torch.distributed as dist
+            stat = torch.empty(2 * C + 1, dtype=torch.float64, device=x.device)
+            ws, wsn = _ws(L.npvp_bn_workspace_bytes(C), x.device)
+            check(L.npvp_bn_stats(_ptr(x), outer, inner, C, layout, _ptr(stat), _ptr(ws), wsn, _stream()), "npvp_bn_stats")
+            stat[2 * C:].fill_(float(outer * inner // C))            # (a fill kernel, not a host-to-device copy)
+            dp._collective(lambda: dist.all_reduce(stat, group=group))
+            check(L.npvp_bn_act_apply_sync(_ptr(x), _ptr(w), _ptr(b), _ptr(residual), _ptr(stat), float(eps), float(momentum or 0.0),
+                                           _ptr(running_mean) if upd else None, _ptr(running_var) if upd else None, outer, inner, C,
+                                           layout, act, _ptr(y), _ptr(mean), _ptr(rstd), _stream()), "npvp_bn_act_apply_sync")
+            ctx.save_for_backward(x, w, b, mean, rstd, stat)
+            ctx.act, ctx.train, ctx.layout, ctx.has_res = act, True, layout, residual is not None
+            return y
         if train:
             sums = torch.empty(2 * C, dtype=torch.float64, device=x.device)
             ws, wsn = _ws(L.npvp_bn_workspace_bytes(C), x.device)
             check(L.npvp_bn_stats(_ptr(x), outer, inner, C, layout, _ptr(sums), _ptr(ws), wsn, _stream()), "npvp_bn_stats")
             count = outer * inner // C
-        upd = train and running_mean is not None
         check(L.npvp_bn_act_apply(_ptr(x), _ptr(w), _ptr(b), _ptr(residual), _ptr(sums), count, float(eps), float(momentum or 0.0),
                                   _ptr(running_mean) if upd or not train else None, _ptr(running_var) if upd or not train else None,
                                   outer, inner, C, layout, act, _ptr(y), _ptr(mean), _ptr(rstd), _stream()), "npvp_bn_act_apply")
@@ -1929,7 +1948,7 @@ class _BnActTrain(torch.autograd.Function):
 
     @scoped
     def backward(ctx, g):
-        x, w, b, mean, rstd = ctx.saved_tensors
+        x, w, b, mean, rstd = ctx.saved_tensors[:5]
         _chk(g)
         g = _like_layout(g, ctx.layout)
         outer, inner, layout = _nchw_layout(x, "bn_act_train")
@@ -1939,21 +1958,35 @@ class _BnActTrain(torch.autograd.Function):
         dw = torch.empty(C, dtype=torch.float32, device=x.device)
         db = torch.empty_like(dw)
         ws, wsn = _ws(L.npvp_bn_workspace_bytes(C), x.device)
+        if ctx.group is not None:
+            from . import dp
+            import torch.distributed as dist
+            stat, group = ctx.saved_tensors[5], ctx.group
+            sums = torch.empty(2 * C, dtype=torch.float64, device=x.device)
+            check(L.npvp_bn_bwd_sums(_ptr(g), _ptr(x), _ptr(mean), _ptr(rstd), _ptr(w), _ptr(b), outer, inner, C, layout, ctx.act,
+                                     _ptr(sums), _ptr(dw), _ptr(db), _ptr(ws), wsn, _stream()), "npvp_bn_bwd_sums")
+            dp._collective(lambda: dist.all_reduce(sums, group=group))
+            check(L.npvp_bn_act_bwd_apply(_ptr(g), _ptr(x), _ptr(mean), _ptr(rstd), _ptr(w), _ptr(b), _ptr(sums),
+                                          stat.data_ptr() + 2 * C * 8, outer, inner, C, layout, ctx.act, _ptr(dx), _stream()),
+                  "npvp_bn_act_bwd_apply")
+            return dx, dw, db, (g if ctx.has_res else None), None, None, None, None, None, None, None
         check(L.npvp_bn_act_bwd(_ptr(g), _ptr(x), _ptr(mean), _ptr(rstd), _ptr(w), _ptr(b), outer, inner, C, layout, ctx.act,
                                 int(ctx.train), _ptr(dx), _ptr(dw), _ptr(db), _ptr(ws), wsn, _stream()), "npvp_bn_act_bwd")
-        return dx, dw, db, (g if ctx.has_res else None), None, None, None, None, None, None
+        return dx, dw, db, (g if ctx.has_res else None), None, None, None, None, None, None, None
 
 
-def bn_act_train(x, w, b, running_mean=None, running_var=None, momentum=0.1, eps=1e-5, act=0, train=True, residual=None):
+def bn_act_train(x, w, b, running_mean=None, running_var=None, momentum=0.1, eps=1e-5, act=0, train=True, residual=None, group=None):
     """act(batch_norm(x)) (+ residual) for an (N,C,H,W) fp32 tensor, contiguous (NCHW planes) or channels_last (rows); running
-    statistics are updated in place in training mode (torch's momentum rule, unbiased variance)"""
+    statistics are updated in place in training mode (torch's momentum rule, unbiased variance).  group: a torch.distributed process
+    group whose ranks share the batch statistics in training mode (synchronised BatchNorm; shards may be uneven); None, or eval
+    mode: this rank's own, the launch sequence unchanged"""
     if act not in (0, 1):
         raise RuntimeError("bn_act_train: act must be 0 (none) or 1 (ReLU)")
     if train and running_mean is not None and momentum is None:
         raise RuntimeError("bn_act_train: momentum=None (cumulative average) is not supported")
     if (running_mean is None) != (running_var is None):
         raise RuntimeError("bn_act_train: running_mean and running_var go together")
-    return _BnActTrain.apply(x, w, b, residual, running_mean, running_var, momentum, eps, act, bool(train))
+    return _BnActTrain.apply(x, w, b, residual, running_mean, running_var, momentum, eps, act, bool(train), group if train else None)
 
 
 _NL_SHAPES = {(8, 32), (16, 64), (32, 128), (64, 256)}

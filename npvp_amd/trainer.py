@@ -769,18 +769,40 @@ def ae_optimizer(enc, dec, lr=1e-4):
     return opt
 
 
-def ae_train_step(enc, dec, opt, past_frames, future_frames):
+def ae_data_parallel(enc, dec, opt, **gradsync_kw):
+    """What the reference's Stage-1 trainer gets from `devices=world_size`, the DDP strategy and `sync_batchnorm=True`
+    (ref/train_AutoEncoder_lightning.py:40-42), for a prepared pair and its ae_optimizer: the pair (parameters and buffers) broadcast
+    from rank 0, every BatchNorm2d swapped for dp.SyncBatchNorm2d (same state-dict keys; statistics over all ranks in training mode)
+    and a dp.GradSync over the optimiser's flat gradient buffer to pass to ae_train_step.  Collective: every rank calls it, after
+    dp.init_distributed().  Without a process group (dp.active() false) nothing is converted and None is returned."""
+    from . import dp
+    if not dp.active():
+        return None
+    dp.broadcast_module(opt.ae_pair)
+    dp.convert_sync_batchnorm(enc)
+    dp.convert_sync_batchnorm(dec)
+    return dp.GradSync(opt, **gradsync_kw)
+
+
+def ae_train_step(enc, dec, opt, past_frames, future_frames, grad_sync=None):
     """LitAE.training_step / shared_step (ref/models/ResNetAutoEncoder.py:27-44): x = cat(past, future, dim=1),
     loss = L1(dec(enc(x)), x), backward, optimiser step.  `opt` from ae_optimizer; the pair prepared with
-    prepare_trainable_autoencoder.  Returns the loss as a device scalar."""
+    prepare_trainable_autoencoder.  grad_sync (from ae_data_parallel): the gradients are averaged over the ranks before the
+    optimiser step.  Returns the loss - this rank's own - as a device scalar."""
     if not getattr(enc, "_npvp_trainable", False) or not getattr(dec, "_npvp_trainable", False):
         raise RuntimeError("ae_train_step: call prepare_trainable_autoencoder(enc, dec) first")
+    if grad_sync is not None and grad_sync.on and grad_sync.ctx is not opt.ctx:
+        # (its listener would sit on another context's gradient sink: buckets would be all-reduced before their last write)
+        raise RuntimeError("ae_train_step: grad_sync listens on another scheduling context than the optimiser's; build it with "
+                           "ae_data_parallel(enc, dec, opt) (or dp.GradSync(opt))")
     with ops.use(opt.ctx):
         ops.WgradStream.join()
         opt.zero_grad()
         x = torch.cat([past_frames, future_frames], dim=1).contiguous()
         loss = ops.l1_mean(dec(enc(x)), x)
         loss.backward()
+        if grad_sync is not None:
+            grad_sync.finish()        # every bucket reduced (side stream) before the optimiser reads the gradients
         opt.step()
     return loss.detach()
 

@@ -3,7 +3,11 @@ ae_train_step + FlatAdamW) against the stock path (the same modules in train mod
 real batch, on the same seeded weights and frames.  One JSON line: ms per step, peak allocated memory, loss of each path and their
 relative difference, and the algorithmic bytes of the new BatchNorm / attention kernels per step (for a share of the HBM peak from a
 separate `rocprofv3 --kernel-trace --stats` run).
-Usage: python tools/ae_train_bench.py --config {BAIR,KTH,KITTI} [--steps 10] [--warmup 3] [--batch B]"""
+--dp adds two paths on a forced group of ONE rank over RCCL, where every collective is a real RCCL call that leaves the values
+unchanged - what the data-parallel machinery costs a step beyond its transfers: "hip_gs" = GradSync's bucket all-reduces alone
+(plain BatchNorm), "hip_dp" = ae_data_parallel (GradSync + synchronised BatchNorm's two small all-reduces per layer).  With --repeats R the paths are timed R times in
+alternation and every window is reported.
+Usage: python tools/ae_train_bench.py --config {BAIR,KTH,KITTI} [--steps 10] [--warmup 3] [--batch B] [--dp] [--repeats R] [--paths hip,hip_gs,hip_dp]"""
 import argparse
 import copy
 import json
@@ -59,8 +63,19 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=None)
-    ap.add_argument("--paths", default="stock,hip")
+    ap.add_argument("--paths", default=None, help="comma list of stock, hip, hip_gs, hip_dp (default: stock,hip; with --dp also hip_gs,hip_dp)")
+    ap.add_argument("--one-context", action="store_true",
+                    help="build every trainer on the process's default scheduling context instead of one context per path")
+    ap.add_argument("--dp", action="store_true", help="also time the HIP step on a forced one-rank RCCL group (paths hip_gs, hip_dp)")
+    ap.add_argument("--repeats", type=int, default=1, help="timed windows per path, the paths alternating")
     a = ap.parse_args()
+    paths = a.paths.split(",") if a.paths else ["stock", "hip"] + (["hip_gs", "hip_dp"] if a.dp else [])
+    if not a.dp and any(p in ("hip_gs", "hip_dp") for p in paths):
+        raise SystemExit("paths hip_gs / hip_dp need --dp")
+    if a.dp:        # (read when npvp_amd.dp is imported / the process group is made)
+        os.environ.setdefault("NPVP_DP_FORCE", "1")
+        os.environ.setdefault("NPVP_DIST_BACKEND", "nccl")
+        os.environ.setdefault("MASTER_PORT", "29541")
     import npvp_amd
     from oracle import ops as O
     if not torch.cuda.is_available():
@@ -74,8 +89,8 @@ def main():
     past, fut = x[:, : T // 2].contiguous(), x[:, T // 2:].contiguous()
     out = {"config": a.config, "batch": B, "frames_per_step": B * T, "res": S}
     out["bn_bytes_per_step"], out["attn_bytes_per_step"] = algorithmic_bytes(enc0, dec0, B * T, S)
-    losses = {}
-    for path in a.paths.split(","):
+    losses, steps = {}, {}
+    for path in paths:
         enc, dec = copy.deepcopy(enc0), copy.deepcopy(dec0)
         if path == "stock":
             enc, dec = enc.to(dev), dec.to(dev)
@@ -91,13 +106,31 @@ def main():
         else:
             enc, dec = enc.to(dev).to(memory_format=torch.channels_last), dec.to(dev)
             npvp_amd.prepare_trainable_autoencoder(enc, dec)
-            opt = npvp_amd.ae_optimizer(enc, dec, lr=1e-4)
-            step = lambda: npvp_amd.ae_train_step(enc, dec, opt, past, fut)
+            # (a scheduling context per path: each GradSync listens on its own trainer's gradient sink)
+            with npvp_amd.ops.use(None if a.one_context else npvp_amd.ops.StepContext(path)):
+                opt = npvp_amd.ae_optimizer(enc, dec, lr=1e-4)
+            gs = None
+            if path in ("hip_gs", "hip_dp"):
+                from npvp_amd import dp
+                dp.init_distributed()
+                if path == "hip_dp":
+                    gs = npvp_amd.ae_data_parallel(enc, dec, opt)
+                else:
+                    dp.broadcast_module(opt.ae_pair)
+                    gs = dp.GradSync(opt)
+                assert gs is not None and gs.on, "--dp: the one-rank process group did not come up"
+                out["dp"] = {"backend": torch.distributed.get_backend(), "world_size": gs.world, "buckets": len(gs.buckets),
+                             "sync_batchnorm_layers": sum(isinstance(m, dp.SyncBatchNorm2d) for m in opt.ae_pair.modules())}
+            step = lambda enc=enc, dec=dec, opt=opt, gs=gs: npvp_amd.ae_train_step(enc, dec, opt, past, fut, grad_sync=gs)
         first = float(step())
         losses[path] = first
         for _ in range(max(a.warmup - 1, 0)):
             step()
         torch.cuda.synchronize()
+        out[f"{path}_loss_step1"] = first
+        steps[path] = step
+        if a.repeats > 1:
+            continue
         torch.cuda.reset_peak_memory_stats()
         t0 = time.perf_counter()
         for _ in range(a.steps):
@@ -105,12 +138,26 @@ def main():
         torch.cuda.synchronize()
         out[f"{path}_ms_per_step"] = round((time.perf_counter() - t0) * 1e3 / a.steps, 3)
         out[f"{path}_peak_alloc_MiB"] = round(torch.cuda.max_memory_allocated() / 2 ** 20, 1)
-        out[f"{path}_loss_step1"] = first
-        del enc, dec, opt, step
+        del enc, dec, opt, step, steps[path]
         torch.cuda.empty_cache()
+    if a.repeats > 1:       # every path stays resident and warm; the windows alternate so that drift of the host hits all alike
+        windows = {path: [] for path in steps}
+        for _ in range(a.repeats):
+            for path, step in steps.items():
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for _ in range(a.steps):
+                    step()
+                torch.cuda.synchronize()
+                windows[path].append(round((time.perf_counter() - t0) * 1e3 / a.steps, 3))
+        for path, w in windows.items():
+            out[f"{path}_ms_per_step"] = sorted(w)[len(w) // 2]
+            out[f"{path}_ms_per_step_windows"] = w
     if "stock" in losses and "hip" in losses:
         out["loss_rel_diff"] = abs(losses["hip"] - losses["stock"]) / abs(losses["stock"])
     print(json.dumps(out))
+    if a.dp and torch.distributed.is_initialized():
+        torch.distributed.destroy_process_group()
 
 
 if __name__ == "__main__":
