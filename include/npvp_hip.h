@@ -473,8 +473,12 @@ int npvp_bn_act_bwd(const float* g, const float* x, const float* mean, const flo
  *   dw / db (float) from these LOCAL sums - the gradient all-reduce (mean over ranks) completes them as it does every other parameter's.
  * bn_act_bwd_apply: the second half: dx = w rstd (g' - sum g'/n - xhat sum g' xhat / n) from the all-reduced sums[2C] and the device
  *   count n (one double: stat + 2C kept from the forward).
- * Given this rank's own sums and count, the three calls produce the same bits as bn_act_apply / bn_act_bwd (y, mean, rstd, running
- * statistics, dx, dw, db).  Same layouts, shape rules, alignment and workspace as above; deterministic, no zero-filled buffer. */
+ * bn_act_apply / bn_act_bwd are these calls composed, on a host count and on sums in bn_act_bwd's own workspace; their dx pass reads
+ * the float dw / db and a host 1/n where bn_act_bwd_apply rounds the double sums and 1 / n itself, to the same floats.  So given this
+ * rank's own sums and count, the three calls produce the bits of bn_act_apply / bn_act_bwd (y, mean, rstd, running statistics, dx, dw,
+ * db).  Same layouts, shape rules and alignment as above;
+ * bn_bwd_sums needs the whole npvp_bn_workspace_bytes(C), bn_stats / bn_act_bwd accept what their problem's parts take; deterministic,
+ * no zero-filled buffer. */
 int npvp_bn_act_apply_sync(const float* x, const float* w, const float* b, const float* residual, const double* stat, float eps,
                            float momentum, float* running_mean, float* running_var, long long outer, long long inner, int C, int layout,
                            int act, float* y, float* mean, float* rstd, npvp_stream_t stream);

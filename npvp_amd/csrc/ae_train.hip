@@ -613,96 +613,122 @@ using namespace npvp;
 
 // ------------------------------------------------------------------------------------------------------------ C entry points
 
-extern "C" int npvp_bn_workspace_bytes(int C) {
-  return C > 0 && C <= 4096 ? (BN_MAX_PARTS + 1) * 2 * C * (int)sizeof(double) : -1;
-}
+// BatchNorm: one problem record with one check, one part plan, one launcher per pass.  The six entry points compose them: a fused
+// call and its synchronised halves differ in where the count (host / device) and the sums (workspace / caller's buffer) come from.
+extern "C" int npvp_bn_workspace_bytes(int C) { return C > 0 && C <= 4096 ? (BN_MAX_PARTS + 1) * 2 * C * (int)sizeof(double) : -1; }
 
-static int bn_check_shape(long long outer, long long inner, int C, int layout) {
-  NPVP_CHECK_ARG(outer > 0 && inner > 0 && C > 0, "bn: empty problem");
-  NPVP_CHECK_ARG(layout == 0 || layout == 1, "bn: layout 0 (rows [outer][C]) or 1 (planes [N*C][H*W])");
-  if (layout == 0) {
-    NPVP_CHECK_ARG(inner == C && C % 4 == 0 && C <= 1024 && 256 % (C / 4) == 0, "bn: layout 0 needs inner == C, C a power of two in [4, 1024]");
-  } else {
-    NPVP_CHECK_ARG(outer % C == 0 && inner % 4 == 0 && inner <= (1ll << 30), "bn: layout 1 needs outer = N*C planes of H*W % 4 == 0");
-  }
+struct BnProblem { long long outer, inner; int C, layout, act; };
+
+static int bn_fail(const char* name, const char* what) {
+  char msg[256];
+  snprintf(msg, sizeof(msg), "%s: %s", name, what);
+  npvp_set_error(msg);
+  return NPVP_ERR_ARG;
+}
+#define BN_REQUIRE(cond, what) do { if (!(cond)) return bn_fail(name, what); } while (0)
+
+// shape, act and the 16-byte alignment of the element buffers a0 | a1 | a2 (null: not one of this call's), under the entry point's name
+static int bn_check(const BnProblem& p, const char* name, const void* a0, const void* a1, const void* a2) {
+  BN_REQUIRE(p.outer > 0 && p.inner > 0 && p.C > 0, "empty problem");
+  BN_REQUIRE(p.layout == 0 || p.layout == 1, "layout 0 (rows [outer][C]) or 1 (planes [N*C][H*W])");
+  if (p.layout == 0)
+    BN_REQUIRE(p.inner == p.C && p.C % 4 == 0 && p.C <= 1024 && 256 % (p.C / 4) == 0, "layout 0 needs inner == C, C a power of two in [4, 1024]");
+  else
+    BN_REQUIRE(p.outer % p.C == 0 && p.inner % 4 == 0 && p.inner <= (1ll << 30), "layout 1 needs outer = N*C planes of H*W % 4 == 0");
+  BN_REQUIRE(p.act == 0 || p.act == 1, "act 0 (none) or 1 (ReLU)");
+  BN_REQUIRE((((uintptr_t)a0 | (uintptr_t)a1 | (uintptr_t)a2) & 15) == 0, "buffers must be 16-byte aligned");
   return NPVP_OK;
 }
 
-// partial sums (MODE 0: x / MODE 1: backward pair) -> sums[2][C] (double) in workspace order
+// first level of the per-channel sums: P parts of `per` rows (layout 0) or planes of one channel (layout 1) each
+struct BnParts { int P; long long per; };
+static BnParts bn_parts(const BnProblem& p) {
+  const long long n = p.layout == 0 ? p.outer : p.outer / p.C;
+  const int blocks = p.layout == 0 ? (p.C + 63) / 64 : p.C;      // grid.x of the part kernel: about 2048 blocks in all
+  const int P = clampi(p.layout == 0 ? (n + 255) / 256 : n, 1, clampi(2048 / blocks, 1, BN_MAX_PARTS));
+  const long long per = (n + P - 1) / P;
+  return {(int)((n + per - 1) / per), per};
+}
+
+// The workspace holds `lead` doubles the call keeps in front (npvp_bn_act_bwd: its 2C sums; else 0), then part[P][2][C].  Two rules:
+//   parts (npvp_bn_stats, npvp_bn_act_bwd): what this problem's P parts take, no more;
+//   whole (npvp_bn_bwd_sums): npvp_bn_workspace_bytes(C) as well, whatever the shape.
+static int bn_check_ws(const BnProblem& p, const char* name, long long ws_bytes, int lead, bool whole) {
+  const long long need = (lead + (long long)bn_parts(p).P * 2 * p.C) * (long long)sizeof(double);
+  BN_REQUIRE(ws_bytes >= need && (!whole || ws_bytes >= npvp_bn_workspace_bytes(p.C)), "workspace too small (npvp_bn_workspace_bytes)");
+  return NPVP_OK;
+}
+
+// partial sums (MODE 0: x / MODE 1: backward pair) through part -> sums[2][C] (double); MODE 1: and dw / db (float) from them
 template <int MODE>
-static int bn_sums(const float* x, const float* g, const float* mean, const float* rstd, const float* w, const float* b, int act,
-                   long long outer, long long inner, int C, int layout, double* sums, void* ws, long long ws_bytes, hipStream_t stream) {
-  double* part = reinterpret_cast<double*>(ws);
-  int P;
-  if (layout == 0) {
-    const int cb = (C + 63) / 64;
-    P = clampi((outer + 255) / 256, 1, clampi(2048 / cb, 1, BN_MAX_PARTS));
-    const long long rpp = (outer + P - 1) / P;
-    P = (int)((outer + rpp - 1) / rpp);
-    NPVP_CHECK_ARG(ws_bytes >= (long long)P * 2 * C * 8, "bn: workspace too small (npvp_bn_workspace_bytes)");
-    NPVP_LAUNCH(bn_part_rows_kernel<MODE>, dim3(cb, P), dim3(256), 0, stream, x, g, mean, rstd, w, b, act, outer, C, rpp, part);
-  } else {
-    const int N = (int)(outer / C);
-    P = clampi(N, 1, clampi(2048 / C, 1, BN_MAX_PARTS));
-    const int ppp = (N + P - 1) / P;
-    P = (N + ppp - 1) / ppp;
-    NPVP_CHECK_ARG(ws_bytes >= (long long)P * 2 * C * 8, "bn: workspace too small (npvp_bn_workspace_bytes)");
-    NPVP_LAUNCH(bn_part_planes_kernel<MODE>, dim3(C, P), dim3(256), 0, stream, x, g, mean, rstd, w, b, act, N, C, (int)inner, ppp, part);
-  }
-  NPVP_LAUNCH(bn_part_reduce_kernel, dim3(2 * C), dim3(64), 0, stream, part, P, C, sums);
+static int bn_sums(const BnProblem& p, const float* x, const float* g, const float* mean, const float* rstd, const float* w,
+                    const float* b, double* sums, double* part, float* dw, float* db, hipStream_t stream) {
+  const BnParts pp = bn_parts(p);
+  if (p.layout == 0)
+    NPVP_LAUNCH(bn_part_rows_kernel<MODE>, dim3((p.C + 63) / 64, pp.P), dim3(256), 0, stream, x, g, mean, rstd, w, b, p.act, p.outer, p.C,
+                pp.per, part);
+  else
+    NPVP_LAUNCH(bn_part_planes_kernel<MODE>, dim3(p.C, pp.P), dim3(256), 0, stream, x, g, mean, rstd, w, b, p.act, (int)(p.outer / p.C),
+                p.C, (int)p.inner, (int)pp.per, part);
+  NPVP_LAUNCH(bn_part_reduce_kernel, dim3(2 * p.C), dim3(64), 0, stream, part, pp.P, p.C, sums);
+  if (MODE == 1) NPVP_LAUNCH(bn_bwd_finalize_kernel, dim3((p.C + 255) / 256), dim3(256), 0, stream, sums, p.C, dw, db);
   NPVP_CHECK_LAUNCH();
   return NPVP_OK;
+}
+
+// the elementwise pass.  BWD 0: out = y; 1: out = dx from this call's dw / db and the host's count; 2: dx from sums and *count_dev
+template <int BWD>
+static int bn_elem(const BnProblem& p, const float* x, const float* g, const float* residual, const float* mean, const float* rstd,
+                   const float* w, const float* b, const float* dw, const float* db, const double* sums, const double* count_dev,
+                   int train, float* out, hipStream_t stream) {
+  const float inv_n = (float)(1.0 / (double)(p.outer * p.inner / p.C));
+  if (p.layout == 0)
+    NPVP_LAUNCH(bn_elem_rows_kernel<BWD>, dim3(clampi((p.outer * p.C / 4 + 255) / 256, 1, 8192)), dim3(256), 0, stream, x, g, residual, mean,
+                rstd, w, b, dw, db, sums, count_dev, inv_n, p.act, train, p.outer, p.C, out);
+  else
+    NPVP_LAUNCH(bn_elem_planes_kernel<BWD>, dim3((unsigned)p.outer), dim3(256), 0, stream, x, g, residual, mean, rstd, w, b, dw, db, sums,
+                count_dev, inv_n, p.act, train, p.C, (int)p.inner, out);
+  NPVP_CHECK_LAUNCH();
+  return NPVP_OK;
+}
+
+// forward from the sums (null: eval): checks, mean / rstd and running statistics from `count` or *count_dev elements per channel, apply
+static int bn_forward(const char* name, const BnProblem& p, const float* x, const float* w, const float* b, const float* residual,
+                      const double* sums, double count, const double* count_dev, float eps, float momentum, float* running_mean,
+                      float* running_var, float* y, float* mean, float* rstd, hipStream_t stream) {
+  BN_REQUIRE(x && w && b && y && mean && rstd, "null buffer");
+  if (int rc = bn_check(p, name, x, y, residual)) return rc;
+  BN_REQUIRE((running_mean == nullptr) == (running_var == nullptr), "running_mean and running_var together");
+  NPVP_LAUNCH(bn_finalize_kernel, dim3((p.C + 255) / 256), dim3(256), 0, stream, sums, count, count_dev, eps, momentum, running_mean,
+              running_var, p.C, mean, rstd);
+  return bn_elem<0>(p, x, nullptr, residual, mean, rstd, w, b, nullptr, nullptr, nullptr, nullptr, 1, y, stream);
 }
 
 extern "C" int npvp_bn_stats(const float* x, long long outer, long long inner, int C, int layout, double* sums, void* workspace,
                              long long ws_bytes, hipStream_t stream) {
   NPVP_CHECK_ARG(x && sums && workspace, "bn_stats: null buffer");
-  if (int rc = bn_check_shape(outer, inner, C, layout)) return rc;
-  NPVP_CHECK_ARG(((uintptr_t)x & 15) == 0, "bn_stats: x must be 16-byte aligned");
-  return bn_sums<0>(x, nullptr, nullptr, nullptr, nullptr, nullptr, 0, outer, inner, C, layout, sums, workspace, ws_bytes, stream);
+  const BnProblem p{outer, inner, C, layout, 0};
+  if (bn_check(p, "bn_stats", x, nullptr, nullptr) || bn_check_ws(p, "bn_stats", ws_bytes, 0, false)) return NPVP_ERR_ARG;
+  return bn_sums<0>(p, x, nullptr, nullptr, nullptr, nullptr, nullptr, sums, reinterpret_cast<double*>(workspace), nullptr, nullptr, stream);
 }
 
 extern "C" int npvp_bn_act_apply(const float* x, const float* w, const float* b, const float* residual, const double* sums, long long count,
                                  float eps, float momentum, float* running_mean, float* running_var, long long outer, long long inner,
                                  int C, int layout, int act, float* y, float* mean, float* rstd, hipStream_t stream) {
-  NPVP_CHECK_ARG(x && w && b && y && mean && rstd, "bn_act_apply: null buffer");
-  if (int rc = bn_check_shape(outer, inner, C, layout)) return rc;
-  NPVP_CHECK_ARG(act == 0 || act == 1, "bn_act_apply: act 0 (none) or 1 (ReLU)");
   NPVP_CHECK_ARG(sums ? count >= 1 : (running_mean && running_var), "bn_act_apply: sums + count, or running statistics (eval)");
-  NPVP_CHECK_ARG((running_mean == nullptr) == (running_var == nullptr), "bn_act_apply: running_mean and running_var together");
-  NPVP_CHECK_ARG((((uintptr_t)x | (uintptr_t)y | (uintptr_t)residual) & 15) == 0, "bn_act_apply: buffers must be 16-byte aligned");
-  NPVP_LAUNCH(bn_finalize_kernel, dim3((C + 255) / 256), dim3(256), 0, stream, sums, (double)count, nullptr, eps, momentum, running_mean,
-              running_var, C, mean, rstd);
-  if (layout == 0)
-    NPVP_LAUNCH(bn_elem_rows_kernel<0>, dim3(clampi((outer * C / 4 + 255) / 256, 1, 8192)), dim3(256), 0, stream, x, nullptr, residual,
-                mean, rstd, w, b, nullptr, nullptr, nullptr, nullptr, 0.f, act, 1, outer, C, y);
-  else
-    NPVP_LAUNCH(bn_elem_planes_kernel<0>, dim3((unsigned)outer), dim3(256), 0, stream, x, nullptr, residual, mean, rstd, w, b, nullptr,
-                nullptr, nullptr, nullptr, 0.f, act, 1, C, (int)inner, y);
-  NPVP_CHECK_LAUNCH();
-  return NPVP_OK;
+  return bn_forward("bn_act_apply", {outer, inner, C, layout, act}, x, w, b, residual, sums, (double)count, nullptr, eps, momentum,
+                    running_mean, running_var, y, mean, rstd, stream);
 }
 
 extern "C" int npvp_bn_act_bwd(const float* g, const float* x, const float* mean, const float* rstd, const float* w, const float* b,
                                long long outer, long long inner, int C, int layout, int act, int train, float* dx, float* dw, float* db,
                                void* workspace, long long ws_bytes, hipStream_t stream) {
   NPVP_CHECK_ARG(g && x && mean && rstd && w && b && dx && dw && db && workspace, "bn_act_bwd: null buffer");
-  if (int rc = bn_check_shape(outer, inner, C, layout)) return rc;
-  NPVP_CHECK_ARG(act == 0 || act == 1, "bn_act_bwd: act 0 (none) or 1 (ReLU)");
-  NPVP_CHECK_ARG((((uintptr_t)x | (uintptr_t)g | (uintptr_t)dx) & 15) == 0, "bn_act_bwd: buffers must be 16-byte aligned");
-  NPVP_CHECK_ARG(ws_bytes >= (long long)(2 * C) * 8, "bn_act_bwd: workspace too small (npvp_bn_workspace_bytes)");
+  const BnProblem p{outer, inner, C, layout, act};
+  if (bn_check(p, "bn_act_bwd", x, g, dx) || bn_check_ws(p, "bn_act_bwd", ws_bytes, 2 * C, false)) return NPVP_ERR_ARG;
   double* sums = reinterpret_cast<double*>(workspace);
-  if (int rc = bn_sums<1>(x, g, mean, rstd, w, b, act, outer, inner, C, layout, sums, sums + 2 * C, ws_bytes - 2 * C * 8, stream)) return rc;
-  NPVP_LAUNCH(bn_bwd_finalize_kernel, dim3((C + 255) / 256), dim3(256), 0, stream, sums, C, dw, db);
-  const float inv_n = (float)(1.0 / (double)(outer * inner / C));
-  if (layout == 0)
-    NPVP_LAUNCH(bn_elem_rows_kernel<1>, dim3(clampi((outer * C / 4 + 255) / 256, 1, 8192)), dim3(256), 0, stream, x, g, nullptr, mean,
-                rstd, w, b, dw, db, nullptr, nullptr, inv_n, act, train, outer, C, dx);
-  else
-    NPVP_LAUNCH(bn_elem_planes_kernel<1>, dim3((unsigned)outer), dim3(256), 0, stream, x, g, nullptr, mean, rstd, w, b, dw, db, nullptr,
-                nullptr, inv_n, act, train, C, (int)inner, dx);
-  NPVP_CHECK_LAUNCH();
-  return NPVP_OK;
+  if (int rc = bn_sums<1>(p, x, g, mean, rstd, w, b, sums, sums + 2 * C, dw, db, stream)) return rc;
+  return bn_elem<1>(p, x, g, nullptr, mean, rstd, w, b, dw, db, nullptr, nullptr, train, dx, stream);
 }
 
 // ---- synchronised BatchNorm (Lightning's sync_batchnorm=True, ref/train_AutoEncoder_lightning.py:40-42): the two passes above cut at
@@ -711,60 +737,33 @@ extern "C" int npvp_bn_act_bwd(const float* g, const float* x, const float* mean
 extern "C" int npvp_bn_act_apply_sync(const float* x, const float* w, const float* b, const float* residual, const double* stat, float eps,
                                       float momentum, float* running_mean, float* running_var, long long outer, long long inner, int C,
                                       int layout, int act, float* y, float* mean, float* rstd, hipStream_t stream) {
-  NPVP_CHECK_ARG(stat, "bn_act_apply_sync: null stat (device [sum x, sum x^2, n], 2C+1 doubles)");
-  NPVP_CHECK_ARG(x && w && b && y && mean && rstd, "bn_act_apply_sync: null buffer");
-  if (int rc = bn_check_shape(outer, inner, C, layout)) return rc;
-  NPVP_CHECK_ARG(act == 0 || act == 1, "bn_act_apply_sync: act 0 (none) or 1 (ReLU)");
-  NPVP_CHECK_ARG((running_mean == nullptr) == (running_var == nullptr), "bn_act_apply_sync: running_mean and running_var together");
-  NPVP_CHECK_ARG((((uintptr_t)x | (uintptr_t)y | (uintptr_t)residual) & 15) == 0, "bn_act_apply_sync: buffers must be 16-byte aligned");
-  NPVP_CHECK_ARG(((uintptr_t)stat & 7) == 0, "bn_act_apply_sync: stat must be 8-byte aligned");
-  NPVP_LAUNCH(bn_finalize_kernel, dim3((C + 255) / 256), dim3(256), 0, stream, stat, 0.0, stat + 2 * C, eps, momentum, running_mean,
-              running_var, C, mean, rstd);
-  if (layout == 0)
-    NPVP_LAUNCH(bn_elem_rows_kernel<0>, dim3(clampi((outer * C / 4 + 255) / 256, 1, 8192)), dim3(256), 0, stream, x, nullptr, residual,
-                mean, rstd, w, b, nullptr, nullptr, nullptr, nullptr, 0.f, act, 1, outer, C, y);
-  else
-    NPVP_LAUNCH(bn_elem_planes_kernel<0>, dim3((unsigned)outer), dim3(256), 0, stream, x, nullptr, residual, mean, rstd, w, b, nullptr,
-                nullptr, nullptr, nullptr, 0.f, act, 1, C, (int)inner, y);
-  NPVP_CHECK_LAUNCH();
-  return NPVP_OK;
+  NPVP_CHECK_ARG(stat && ((uintptr_t)stat & 7) == 0,
+                 "bn_act_apply_sync: null stat / not 8-byte aligned (device [sum x, sum x^2, n], 2C+1 doubles)");
+  return bn_forward("bn_act_apply_sync", {outer, inner, C, layout, act}, x, w, b, residual, stat, 0.0, stat + 2 * (long long)C, eps,
+                    momentum, running_mean, running_var, y, mean, rstd, stream);
 }
 
 extern "C" int npvp_bn_bwd_sums(const float* g, const float* x, const float* mean, const float* rstd, const float* w, const float* b,
                                 long long outer, long long inner, int C, int layout, int act, double* sums, float* dw, float* db,
                                 void* workspace, long long ws_bytes, hipStream_t stream) {
-  NPVP_CHECK_ARG(sums, "bn_bwd_sums: null sums (device [sum g', sum g' xhat], 2C doubles)");
+  NPVP_CHECK_ARG(sums && ((uintptr_t)sums & 7) == 0, "bn_bwd_sums: null sums / not 8-byte aligned (device [sum g', sum g' xhat], 2C doubles)");
   NPVP_CHECK_ARG(g && x && mean && rstd && w && b && dw && db && workspace, "bn_bwd_sums: null buffer");
-  if (int rc = bn_check_shape(outer, inner, C, layout)) return rc;
-  NPVP_CHECK_ARG(act == 0 || act == 1, "bn_bwd_sums: act 0 (none) or 1 (ReLU)");
-  NPVP_CHECK_ARG((((uintptr_t)x | (uintptr_t)g) & 15) == 0, "bn_bwd_sums: buffers must be 16-byte aligned");
-  NPVP_CHECK_ARG(((uintptr_t)sums & 7) == 0, "bn_bwd_sums: sums must be 8-byte aligned");
-  NPVP_CHECK_ARG(ws_bytes >= npvp_bn_workspace_bytes(C), "bn_bwd_sums: workspace too small (npvp_bn_workspace_bytes)");
-  if (int rc = bn_sums<1>(x, g, mean, rstd, w, b, act, outer, inner, C, layout, sums, workspace, ws_bytes, stream)) return rc;
-  NPVP_LAUNCH(bn_bwd_finalize_kernel, dim3((C + 255) / 256), dim3(256), 0, stream, sums, C, dw, db);
-  NPVP_CHECK_LAUNCH();
-  return NPVP_OK;
+  const BnProblem p{outer, inner, C, layout, act};
+  if (bn_check(p, "bn_bwd_sums", x, g, nullptr) || bn_check_ws(p, "bn_bwd_sums", ws_bytes, 0, true)) return NPVP_ERR_ARG;
+  return bn_sums<1>(p, x, g, mean, rstd, w, b, sums, reinterpret_cast<double*>(workspace), dw, db, stream);
 }
 
 extern "C" int npvp_bn_act_bwd_apply(const float* g, const float* x, const float* mean, const float* rstd, const float* w, const float* b,
                                      const double* sums, const double* count, long long outer, long long inner, int C, int layout,
                                      int act, float* dx, hipStream_t stream) {
-  NPVP_CHECK_ARG(sums, "bn_act_bwd_apply: null sums (device [sum g', sum g' xhat], 2C doubles, all-reduced)");
-  NPVP_CHECK_ARG(count, "bn_act_bwd_apply: null count (device double: the elements per channel over all ranks)");
+  NPVP_CHECK_ARG(sums && ((uintptr_t)sums & 7) == 0, "bn_act_bwd_apply: null sums / not 8-byte aligned (device [sum g', sum g' xhat], summed)");
+  NPVP_CHECK_ARG(count && ((uintptr_t)count & 7) == 0, "bn_act_bwd_apply: null count / not 8-byte aligned (device double: elements per channel)");
   NPVP_CHECK_ARG(g && x && mean && rstd && w && b && dx, "bn_act_bwd_apply: null buffer");
-  if (int rc = bn_check_shape(outer, inner, C, layout)) return rc;
-  NPVP_CHECK_ARG(act == 0 || act == 1, "bn_act_bwd_apply: act 0 (none) or 1 (ReLU)");
-  NPVP_CHECK_ARG((((uintptr_t)x | (uintptr_t)g | (uintptr_t)dx) & 15) == 0, "bn_act_bwd_apply: buffers must be 16-byte aligned");
-  NPVP_CHECK_ARG((((uintptr_t)sums | (uintptr_t)count) & 7) == 0, "bn_act_bwd_apply: sums / count must be 8-byte aligned");
-  if (layout == 0)
-    NPVP_LAUNCH(bn_elem_rows_kernel<2>, dim3(clampi((outer * C / 4 + 255) / 256, 1, 8192)), dim3(256), 0, stream, x, g, nullptr, mean,
-                rstd, w, b, nullptr, nullptr, sums, count, 0.f, act, 1, outer, C, dx);
-  else
-    NPVP_LAUNCH(bn_elem_planes_kernel<2>, dim3((unsigned)outer), dim3(256), 0, stream, x, g, nullptr, mean, rstd, w, b, nullptr, nullptr,
-                sums, count, 0.f, act, 1, C, (int)inner, dx);
-  NPVP_CHECK_LAUNCH();
-  return NPVP_OK;
+  const BnProblem p{outer, inner, C, layout, act};
+  if (int rc = bn_check(p, "bn_act_bwd_apply", x, g, dx)) return rc;
+  return bn_elem<2>(p, x, g, nullptr, mean, rstd, w, b, nullptr, nullptr, sums, count, 1, dx, stream);
 }
+#undef BN_REQUIRE
 
 extern "C" int npvp_reflect_pad(const float* x, float* y, int planes, int H, int W, int C, int P, int layout, int backward,
                                 hipStream_t stream) {

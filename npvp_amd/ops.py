@@ -1873,18 +1873,18 @@ def bias_act(x, bias, act=0, residual=None):
 
 # --------------------------------------------------------------------------- Stage-1 autoencoder training (csrc/ae_train.hip)
 def _nchw_layout(x, what):
-    """(outer, inner, layout) of an (N,C,H,W) tensor in channels_last (layout 0: rows [N*H*W][C]) or contiguous (layout 1: planes)
-    memory; anything else is made contiguous first by the caller"""
+    """(x, outer, inner, layout) of an (N,C,H,W) tensor as the layout kernels read it: channels_last memory is layout 0 (rows
+    [N*H*W][C]), contiguous memory layout 1 (planes [N*C][H*W]); anything else is made contiguous first"""
+    if x.dim() != 4:
+        raise RuntimeError(f"{what}: x must be (N, C, H, W)")
     N, C, H, W = x.shape
     if x.is_contiguous(memory_format=torch.channels_last) and not x.is_contiguous():
-        return N * H * W, C, 0
-    if x.is_contiguous():
-        return N * C, H * W, 1
-    raise RuntimeError(f"{what}: x must be contiguous or channels_last")
+        return x, N * H * W, C, 0
+    return x.contiguous(), N * C, H * W, 1
 
 
-def _like_layout(t, layout):
-    return t.contiguous(memory_format=torch.channels_last if layout == 0 else torch.contiguous_format)
+def _memory_format(layout):
+    return torch.channels_last if layout == 0 else torch.contiguous_format
 
 
 class _BnActTrain(torch.autograd.Function):
@@ -1899,79 +1899,66 @@ class _BnActTrain(torch.autograd.Function):
     def forward(ctx, x, w, b, residual, running_mean, running_var, momentum, eps, act, train, group=None):
         remember(ctx)
         _chk(x, w, b, residual, running_mean, running_var)
-        if x.dim() != 4:
-            raise RuntimeError("bn_act_train: x must be (N, C, H, W)")
-        if not (x.is_contiguous() or x.is_contiguous(memory_format=torch.channels_last)):
-            x = x.contiguous()
-        outer, inner, layout = _nchw_layout(x, "bn_act_train")
+        x, outer, inner, layout = _nchw_layout(x, "bn_act_train")
         C = x.shape[1]
         if w.shape != (C,) or b.shape != (C,):
             raise RuntimeError(f"bn_act_train: weight / bias must be ({C},)")
         if residual is not None:
             if residual.shape != x.shape:
                 raise RuntimeError("bn_act_train: residual shape differs from x")
-            residual = _like_layout(residual, layout)
+            residual = residual.contiguous(memory_format=_memory_format(layout))
         if not train and running_mean is None:
             raise RuntimeError("bn_act_train: eval mode needs running statistics")
         L = lib()
         y = torch.empty_like(x)
         mean = torch.empty(C, dtype=torch.float32, device=x.device)
         rstd = torch.empty_like(mean)
-        sums, count = None, 0
-        upd = train and running_mean is not None
-        ctx.group = group if train else None
-        if ctx.group is not None:
-            from . import dp
-            import torch.distributed as dist
-            stat = torch.empty(2 * C + 1, dtype=torch.float64, device=x.device)
+        group = group if train else None
+        stat, count = None, 0                           # [sum x, sum x^2] in double; with a group: followed by n
+        if train:
+            stat = torch.empty(2 * C + (group is not None), dtype=torch.float64, device=x.device)
             ws, wsn = _ws(L.npvp_bn_workspace_bytes(C), x.device)
             check(L.npvp_bn_stats(_ptr(x), outer, inner, C, layout, _ptr(stat), _ptr(ws), wsn, _stream()), "npvp_bn_stats")
-            stat[2 * C:].fill_(float(outer * inner // C))            # (a fill kernel, not a host-to-device copy)
-            dp._collective(lambda: dist.all_reduce(stat, group=group))
-            check(L.npvp_bn_act_apply_sync(_ptr(x), _ptr(w), _ptr(b), _ptr(residual), _ptr(stat), float(eps), float(momentum or 0.0),
-                                           _ptr(running_mean) if upd else None, _ptr(running_var) if upd else None, outer, inner, C,
-                                           layout, act, _ptr(y), _ptr(mean), _ptr(rstd), _stream()), "npvp_bn_act_apply_sync")
-            ctx.save_for_backward(x, w, b, mean, rstd, stat)
-            ctx.act, ctx.train, ctx.layout, ctx.has_res = act, True, layout, residual is not None
-            return y
-        if train:
-            sums = torch.empty(2 * C, dtype=torch.float64, device=x.device)
-            ws, wsn = _ws(L.npvp_bn_workspace_bytes(C), x.device)
-            check(L.npvp_bn_stats(_ptr(x), outer, inner, C, layout, _ptr(sums), _ptr(ws), wsn, _stream()), "npvp_bn_stats")
             count = outer * inner // C
-        check(L.npvp_bn_act_apply(_ptr(x), _ptr(w), _ptr(b), _ptr(residual), _ptr(sums), count, float(eps), float(momentum or 0.0),
-                                  _ptr(running_mean) if upd or not train else None, _ptr(running_var) if upd or not train else None,
-                                  outer, inner, C, layout, act, _ptr(y), _ptr(mean), _ptr(rstd), _stream()), "npvp_bn_act_apply")
-        ctx.save_for_backward(x, w, b, mean, rstd)
-        ctx.act, ctx.train, ctx.layout, ctx.has_res = act, bool(train), layout, residual is not None
+        rm, rv = _ptr(running_mean), _ptr(running_var)  # (updated in training mode, read in eval mode; None: not tracked)
+        if group is None:
+            check(L.npvp_bn_act_apply(_ptr(x), _ptr(w), _ptr(b), _ptr(residual), _ptr(stat), count, float(eps), float(momentum or 0.0), rm, rv,
+                                      outer, inner, C, layout, act, _ptr(y), _ptr(mean), _ptr(rstd), _stream()), "npvp_bn_act_apply")
+        else:
+            from . import dp
+            import torch.distributed as dist
+            stat[2 * C:].fill_(float(count))            # (a fill kernel, not a host-to-device copy)
+            dp._collective(lambda: dist.all_reduce(stat, group=group))
+            check(L.npvp_bn_act_apply_sync(_ptr(x), _ptr(w), _ptr(b), _ptr(residual), _ptr(stat), float(eps), float(momentum or 0.0), rm, rv,
+                                           outer, inner, C, layout, act, _ptr(y), _ptr(mean), _ptr(rstd), _stream()), "npvp_bn_act_apply_sync")
+        ctx.save_for_backward(x, w, b, mean, rstd, stat if group is not None else None)
+        ctx.act, ctx.train, ctx.group, ctx.has_res = act, bool(train), group, residual is not None
         return y
 
     @scoped
     def backward(ctx, g):
-        x, w, b, mean, rstd = ctx.saved_tensors[:5]
+        x, w, b, mean, rstd, stat = ctx.saved_tensors
         _chk(g)
-        g = _like_layout(g, ctx.layout)
-        outer, inner, layout = _nchw_layout(x, "bn_act_train")
-        C = x.shape[1]
+        x, outer, inner, layout = _nchw_layout(x, "bn_act_train")
+        g = g.contiguous(memory_format=_memory_format(layout))
+        C, group = x.shape[1], ctx.group
         L = lib()
         dx = torch.empty_like(x)
         dw = torch.empty(C, dtype=torch.float32, device=x.device)
         db = torch.empty_like(dw)
         ws, wsn = _ws(L.npvp_bn_workspace_bytes(C), x.device)
-        if ctx.group is not None:
+        saved, shape = (_ptr(g), _ptr(x), _ptr(mean), _ptr(rstd), _ptr(w), _ptr(b)), (outer, inner, C, layout, ctx.act)
+        if group is None:
+            check(L.npvp_bn_act_bwd(*saved, *shape, int(ctx.train), _ptr(dx), _ptr(dw), _ptr(db), _ptr(ws), wsn, _stream()),
+                  "npvp_bn_act_bwd")
+        else:
             from . import dp
             import torch.distributed as dist
-            stat, group = ctx.saved_tensors[5], ctx.group
             sums = torch.empty(2 * C, dtype=torch.float64, device=x.device)
-            check(L.npvp_bn_bwd_sums(_ptr(g), _ptr(x), _ptr(mean), _ptr(rstd), _ptr(w), _ptr(b), outer, inner, C, layout, ctx.act,
-                                     _ptr(sums), _ptr(dw), _ptr(db), _ptr(ws), wsn, _stream()), "npvp_bn_bwd_sums")
+            check(L.npvp_bn_bwd_sums(*saved, *shape, _ptr(sums), _ptr(dw), _ptr(db), _ptr(ws), wsn, _stream()), "npvp_bn_bwd_sums")
             dp._collective(lambda: dist.all_reduce(sums, group=group))
-            check(L.npvp_bn_act_bwd_apply(_ptr(g), _ptr(x), _ptr(mean), _ptr(rstd), _ptr(w), _ptr(b), _ptr(sums),
-                                          stat.data_ptr() + 2 * C * 8, outer, inner, C, layout, ctx.act, _ptr(dx), _stream()),
+            check(L.npvp_bn_act_bwd_apply(*saved, _ptr(sums), stat.data_ptr() + 2 * C * 8, *shape, _ptr(dx), _stream()),
                   "npvp_bn_act_bwd_apply")
-            return dx, dw, db, (g if ctx.has_res else None), None, None, None, None, None, None, None
-        check(L.npvp_bn_act_bwd(_ptr(g), _ptr(x), _ptr(mean), _ptr(rstd), _ptr(w), _ptr(b), outer, inner, C, layout, ctx.act,
-                                int(ctx.train), _ptr(dx), _ptr(dw), _ptr(db), _ptr(ws), wsn, _stream()), "npvp_bn_act_bwd")
         return dx, dw, db, (g if ctx.has_res else None), None, None, None, None, None, None, None
 
 
@@ -1989,7 +1976,7 @@ def bn_act_train(x, w, b, running_mean=None, running_var=None, momentum=0.1, eps
     return _BnActTrain.apply(x, w, b, residual, running_mean, running_var, momentum, eps, act, bool(train), group if train else None)
 
 
-_NL_SHAPES = {(8, 32), (16, 64), (32, 128), (64, 256)}
+_NL_GRID = {8: 64, 16: 32, 32: 16, 64: 8}        # attention dim A -> side of the AE configs' square grid at C = 8 A; value dim = 4 A
 
 
 class _NonLocalAttn(torch.autograd.Function):
@@ -2030,11 +2017,11 @@ class _NonLocalAttn(torch.autograd.Function):
 
 def nonlocal_attn_packed(qkv, F, H, W, A, V):
     """qkv [F*H*W, ld >= 2A+V] (columns q | k | v, k and v UNPOOLED) -> softmax(q pool(k)^T) pool(v)  [F*H*W, V]"""
-    if (A, V) not in _NL_SHAPES:
-        raise RuntimeError(f"nonlocal_attn: (attn dim, value dim) = ({A}, {V}) is not one of the AE configs' {sorted(_NL_SHAPES)}")
-    if H * W != {8: 4096, 16: 1024, 32: 256, 64: 64}[A] or H % 2 or W & (W - 1):
-        raise RuntimeError(f"nonlocal_attn: a {H}x{W} grid at C = {8 * A} is not one of the AE configs' (64x64 @ 64, 32x32 @ 128, "
-                           "16x16 @ 256, 8x8 @ 512)")
+    if A not in _NL_GRID or V != 4 * A:
+        raise RuntimeError(f"nonlocal_attn: (attn dim, value dim) = ({A}, {V}) is not one of the AE configs' {[(a, 4 * a) for a in _NL_GRID]}")
+    if H * W != _NL_GRID[A] ** 2 or H % 2 or W & (W - 1):
+        raise RuntimeError(f"nonlocal_attn: a {H}x{W} grid at C = {8 * A} is not one of the AE configs' "
+                           f"({', '.join(f'{s}x{s} @ {8 * a}' for a, s in _NL_GRID.items())})")
     if qkv.dim() != 2 or qkv.shape[0] != F * H * W or qkv.shape[1] < 2 * A + V:
         raise RuntimeError(f"nonlocal_attn: qkv must be [F*H*W, >= {2 * A + V}]")
     return _NonLocalAttn.apply(qkv, F, H, W, A, V)
@@ -2057,16 +2044,11 @@ class _ReflectPad(torch.autograd.Function):
     def forward(ctx, x, P):
         remember(ctx)
         _chk(x)
-        if x.dim() != 4:
-            raise RuntimeError("reflect_pad: x must be (N, C, H, W)")
-        if not (x.is_contiguous() or x.is_contiguous(memory_format=torch.channels_last)):
-            x = x.contiguous()
+        x, _, _, layout = _nchw_layout(x, "reflect_pad")
         N, C, H, W = x.shape
         if not (1 <= P < H and P < W):
             raise RuntimeError(f"reflect_pad: padding {P} must be >= 1 and < the input's H, W ({H}, {W})")
-        layout = _nchw_layout(x, "reflect_pad")[2]
-        y = torch.empty((N, C, H + 2 * P, W + 2 * P), dtype=torch.float32, device=x.device,
-                        memory_format=torch.channels_last if layout == 0 else torch.contiguous_format)
+        y = torch.empty((N, C, H + 2 * P, W + 2 * P), dtype=torch.float32, device=x.device, memory_format=_memory_format(layout))
         planes = N if layout == 0 else N * C
         check(lib().npvp_reflect_pad(_ptr(x), _ptr(y), planes, H, W, C, P, layout, 0, _stream()), "npvp_reflect_pad")
         ctx.geo = (N, C, H, W, P, layout)
@@ -2076,9 +2058,8 @@ class _ReflectPad(torch.autograd.Function):
     def backward(ctx, g):
         N, C, H, W, P, layout = ctx.geo
         _chk(g)
-        g = _like_layout(g, layout)
-        dx = torch.empty((N, C, H, W), dtype=torch.float32, device=g.device,
-                         memory_format=torch.channels_last if layout == 0 else torch.contiguous_format)
+        g = g.contiguous(memory_format=_memory_format(layout))
+        dx = torch.empty((N, C, H, W), dtype=torch.float32, device=g.device, memory_format=_memory_format(layout))
         check(lib().npvp_reflect_pad(_ptr(g), _ptr(dx), N if layout == 0 else N * C, H, W, C, P, layout, 1, _stream()), "npvp_reflect_pad")
         return dx, None
 

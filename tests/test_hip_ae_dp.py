@@ -128,11 +128,13 @@ class _Shard:
                                              self.inner, self.C, self.layout, act, p(y), p(mean), p(rstd), None) == 0, self.L.npvp_last_error()
         return y, mean, rstd, rm, rv
 
-    def bwd_fused(self, act, mean, rstd):
+    def bwd_fused(self, act, mean, rstd, ws=None):
+        """ws: a workspace of the caller's (a byte tensor) instead of the shard's own"""
         dx, dw, db = torch.empty_like(self.x), torch.empty_like(mean), torch.empty_like(mean)
+        ws, wsn = (self.ws, self.wsn) if ws is None else (ws, ws.numel())
         assert self.L.npvp_bn_act_bwd(self.g.data_ptr(), self.x.data_ptr(), mean.data_ptr(), rstd.data_ptr(), self.w.data_ptr(),
                                       self.b.data_ptr(), self.outer, self.inner, self.C, self.layout, act, 1, dx.data_ptr(), dw.data_ptr(),
-                                      db.data_ptr(), self.ws.data_ptr(), self.wsn, None) == 0, self.L.npvp_last_error()
+                                      db.data_ptr(), ws.data_ptr(), wsn, None) == 0, self.L.npvp_last_error()
         return dx, dw, db
 
     def bwd_sums(self, act, mean, rstd):
@@ -160,7 +162,9 @@ def _shards(L, shape, with_res):
 @pytest.mark.parametrize("act", [0, 1])
 @pytest.mark.parametrize("with_res", [False, True])
 def test_split_calls_equal_fused_bit_for_bit(L, shape, act, with_res):
-    """each shard alone, with its own sums and count: stats + apply_sync == bn_act_apply, bwd_sums + bwd_apply == bn_act_bwd"""
+    """each shard alone, with its own sums and count: stats + apply_sync == bn_act_apply, bwd_sums + bwd_apply == bn_act_bwd.
+    At (0, 32, 12, 12, 2, 3) - 288 and 432 rows: two parts per shard - the fused backward is also run in a fresh workspace of exactly
+    npvp_bn_workspace_bytes(C) bytes, every double in it a NaN: its sums and its partials share that buffer and must not overlap."""
     for sh in _shards(L, shape, with_res):
         fused = sh.apply_fused(act)
         st = sh.stat()
@@ -173,6 +177,10 @@ def test_split_calls_equal_fused_bit_for_bit(L, shape, act, with_res):
         dx2 = sh.bwd_apply(act, mean, rstd, sums, st)
         assert torch.equal(dx2, dx), "dx"
         assert torch.equal(dw2, dw) and torch.equal(db2, db), "dw / db"
+        if shape == (0, 32, 12, 12, 2, 3):
+            tight = torch.full((L.npvp_bn_workspace_bytes(sh.C),), 0xFF, dtype=torch.uint8, device=DEV)
+            for name, a, b in zip(("dx", "dw", "db"), sh.bwd_fused(act, mean, rstd, tight), (dx2, dw2, db2)):
+                assert torch.equal(a, b), f"{name}, workspace of exactly npvp_bn_workspace_bytes(C)"
         assert not torch.equal(split[3], sh.rm0)                      # (the running statistics were updated, not left alone)
 
 
