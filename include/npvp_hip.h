@@ -362,9 +362,13 @@ int npvp_dwconv3x3_wgrad(const float* a, const float* dout, float* dwt_db, int f
  * :298-300 (spatial window; window gather = ref :447-475 as index math)).
  *   mode 0 spatial: dim0 = N*T frames, groups = frames x windows, L = S = ws*ws
  *   mode 1 temporal: dim0 = N, groups = N x P pixels, L = Tq, S = Tk (rows (n*T + t)*P + p)
- *   mask_mode 1 = encoder quirk ref :100-102.  q NOT pre-scaled; head_dim must be 64; L, S <= 128 (up to 32: the MFMA kernels every shipped
- *   configuration runs on; 33 .. 128: generic kernels - one workgroup per (group, head), operands in LDS, scalar fp32 arithmetic:
- *   the reference's nn.MultiheadAttention has no length limit, ref VidHRFormer.py:94-107). */
+ *   mask_mode 1 = encoder quirk ref :100-102.  q NOT pre-scaled; head_dim must be 64.
+ *   Sequence lengths: npvp_attn_fwd / npvp_attn_bwd take L, S <= 128 (up to 32: the MFMA kernels every shipped configuration runs
+ *   on; 33 .. 128: generic kernels - one workgroup per (group, head), operands in LDS, scalar fp32 arithmetic); the
+ *   npvp_attn_long_* pair below takes EVERY L, S >= 1 (streaming MFMA kernels, LDS and registers independent of the length;
+ *   npvp_amd.ops uses them above 128), so the only bounds left are that token rows and (group, head, tile) indices fit 32 bits and,
+ *   in spatial mode, ws <= 1024 (a window of 2^20 tokens: the window-local row arithmetic) - the reference's
+ *   nn.MultiheadAttention has no length limit, ref VidHRFormer.py:94-107. */
 int npvp_attn_fwd(const float* q, long long ld_q, const float* k, long long ld_k, const float* v, long long ld_v, float* o,
                   long long ld_o, int mode, int dim0, int P, int W, int ws, int Tq, int Tk, int heads, int head_dim,
                   int mask_mode, float drop_p, const unsigned long long* seed, unsigned int salt, float* o_amax,
@@ -375,6 +379,22 @@ int npvp_attn_bwd(const float* q, long long ld_q, const float* k, long long ld_k
                   int mask_mode, float drop_p, const unsigned long long* seed, unsigned int salt, float* dq_amax,
                   float* dk_amax /* may equal dq_amax: one slot for a packed q|k gradient */, float* dv_amax,
                   npvp_stream_t stream);
+/* The same function, arguments and conventions (dropout keys, mask, amax slots) for any sequence length: one workgroup per
+ * (group, head, tile of 64 query rows) streams K / V through LDS in tiles of 64 keys with an online softmax; backward recomputes
+ * the softmax statistics (m, 1 / sum, delta per query row) into `workspace` ([3][groups * heads * L] floats: nothing is saved by
+ * forward), then dQ per query tile and dK / dV per key tile.  Deterministic: no floating-point atomics, every output element
+ * written once. */
+int npvp_attn_long_fwd(const float* q, long long ld_q, const float* k, long long ld_k, const float* v, long long ld_v, float* o,
+                       long long ld_o, int mode, int dim0, int P, int W, int ws, int Tq, int Tk, int heads, int head_dim,
+                       int mask_mode, float drop_p, const unsigned long long* seed, unsigned int salt, float* o_amax,
+                       npvp_stream_t stream);
+long long npvp_attn_long_bwd_workspace_bytes(int mode, int dim0, int P, int W, int ws, int Tq, int Tk, int heads);
+int npvp_attn_long_bwd(const float* q, long long ld_q, const float* k, long long ld_k, const float* v, long long ld_v,
+                       const float* go, long long ld_o, float* dq, long long ld_dq, float* dk, long long ld_dk, float* dv,
+                       long long ld_dv, int mode, int dim0, int P, int W, int ws, int Tq, int Tk, int heads, int head_dim,
+                       int mask_mode, float drop_p, const unsigned long long* seed, unsigned int salt, float* dq_amax,
+                       float* dk_amax /* may equal dq_amax */, float* dv_amax, void* workspace, long long ws_bytes,
+                       npvp_stream_t stream);
 
 /* ---- layout / reductions / masks */
 int npvp_drop_apply(const float* x, float* out, long long rows, int ncols, float p, int mode, int g1, int g2,

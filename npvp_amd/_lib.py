@@ -93,6 +93,11 @@ SIGNATURES = {
                               c_int, c_int, c_int, c_f, c_p, c_u, c_p, c_p]),
     "npvp_attn_bwd": (c_int, [c_p, c_ll, c_p, c_ll, c_p, c_ll, c_p, c_ll, c_p, c_ll, c_p, c_ll, c_p, c_ll, c_int, c_int,
                               c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_f, c_p, c_u, c_p, c_p, c_p, c_p]),
+    "npvp_attn_long_fwd": (c_int, [c_p, c_ll, c_p, c_ll, c_p, c_ll, c_p, c_ll, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                   c_int, c_int, c_int, c_f, c_p, c_u, c_p, c_p]),
+    "npvp_attn_long_bwd_workspace_bytes": (c_ll, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
+    "npvp_attn_long_bwd": (c_int, [c_p, c_ll, c_p, c_ll, c_p, c_ll, c_p, c_ll, c_p, c_ll, c_p, c_ll, c_p, c_ll, c_int, c_int,
+                                   c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_f, c_p, c_u, c_p, c_p, c_p, c_p, c_ll, c_p]),
     "npvp_drop_apply": (c_int, [c_p, c_p, c_ll, c_int, c_f, c_int, c_int, c_int, c_p, c_u, c_p, c_p]),
     "npvp_transpose": (c_int, [c_p, c_p, c_int, c_int, c_int, c_p]),
     "npvp_dwtb_accumulate": (c_int, [c_p, c_p, c_p, c_int, c_p]),

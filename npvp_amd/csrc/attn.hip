@@ -644,8 +644,278 @@ __global__ __launch_bounds__(GEN_THREADS) void attn_bwd_generic_kernel(AttnParam
   amax_slot_commit(p.dv_amax, am_v, pk_v);
 }
 
+// =====================================================================================================
+// Streaming form: any sequence length (npvp_attn_long_*; ops.py takes it above 128).  The generic kernels above park whole
+// K / V (backward: Q, dO, K, V) of a head in LDS, so their footprint grows with the sequence and ends at 128.  Here one
+// workgroup of four waves owns a tile of 64 rows of one side (16 rows per wave, held as "R" tiles in registers) and STREAMS the
+// other side through LDS in tiles of 64 rows (two [64][LDT] tiles = 34 KB, whatever L and S are; the next tile's global loads
+// are in flight while the current one is consumed).  Every 16 x 16 product runs on v_mfma_f32_16x16x4_f32 in the operand
+// layouts of the MFMA kernels above (attn_lds_r / attn_lds_g / attn_mm_d / attn_mm_rows), one 16-row block of the streamed
+// side at a time:
+//   forward        per query tile: online softmax (running maximum and sum per query, the output accumulator rescaled when the
+//                  maximum moves), the dropout mask on the probabilities that feed P V but not on the normaliser.
+//   backward (q)   per query tile, two passes over the keys: pass 1 = the softmax statistics m, 1 / sum and
+//                  delta = sum_j P mask (dO . V_j), kept in registers and written to the workspace [3][groups * heads * L];
+//                  pass 2 = dQ = scale * sum_j dS K_j with dS = P (mask (dO . V_j) - delta).
+//   backward (kv)  per key tile: streams the query tiles (Q, dO and their statistics from the workspace):
+//                  dV = sum_q (P mask) dO_q, dK = scale * sum_q dS Q_q, scores in the query-in-registers orientation.
+// Nothing is accumulated across workgroups, every output element is written once, the order of every sum is fixed.  Rows past the
+// end of a ragged tile are clamped loads whose scores are masked (as in attn_load_r); 16-row blocks of the streamed side that lie
+// wholly past the end are skipped.  Same mask function, dropout keys and amax slots as every kernel above; one amax commit per
+// workgroup and output (every thread reaches the end).
+constexpr int LONG_T = 64;                  // rows per tile, both sides
+constexpr int LONG_THREADS = 256;
+
+struct LongStage { float4 a[4], b[4]; };    // one thread's share of two [64][64] tiles on their way from global memory to LDS
+// rows r0 .. r0 + 63 of two tensors that share their row indices (K | V, Q | dO)
+__device__ __forceinline__ void long_stage_load(LongStage& s, const float* xa, long long lda, const float* xb, long long ldb,
+                                                const AttnRows& g, int nrows, int Tn, int head, int r0) {
+#pragma unroll
+  for (int it = 0; it < 4; ++it) {
+    const long long row = attn_row(g, min(r0 + 16 * it + (int)(threadIdx.x >> 4), nrows - 1), Tn);
+    const int col = head * HD + (threadIdx.x & 15) * 4;
+    s.a[it] = ld4(xa + row * lda + col);
+    s.b[it] = ld4(xb + row * ldb + col);
+  }
+}
+__device__ __forceinline__ void long_stage_store(const LongStage& s, float* As, float* Bs) {
+#pragma unroll
+  for (int it = 0; it < 4; ++it) {
+    const int at = (16 * it + (int)(threadIdx.x >> 4)) * LDT + (threadIdx.x & 15) * 4;
+    st4(As + at, s.a[it]);
+    st4(Bs + at, s.b[it]);
+  }
+}
+// acc rows 4c+i *= f[query 4c+i], f held per query n on the lanes of c = 0
+__device__ __forceinline__ void long_scale_rows(f32x4_t (&acc)[4], float f, int c) {
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const float fi = __shfl(f, 4 * c + i, 64);
+#pragma unroll
+    for (int b = 0; b < 4; ++b) acc[b][i] *= fi;
+  }
+}
+__device__ __forceinline__ bool long_dead(const AttnParams& p, int q, int j) {
+  return j >= p.S || (p.mask_mode == 1 && j == p.S - 1 && q < p.L - 1);
+}
+
+__global__ __launch_bounds__(LONG_THREADS) void attn_long_fwd_kernel(AttnParams p, unsigned int ntile) {
+  __shared__ __attribute__((aligned(16))) float Ks[LONG_T * LDT], Vs[LONG_T * LDT];
+  __shared__ float red[4];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, n = lane & 15, c = lane >> 4;
+  const unsigned int wid = blockIdx.x / ntile, qblk = 4 * (blockIdx.x - wid * ntile) + w;
+  const int head = (int)(wid % (unsigned int)p.heads);
+  const AttnRows g = attn_rows(p, wid / (unsigned int)p.heads);
+  const int L = p.L, S = p.S;
+  const int Tq = p.mode == 1 ? p.Tq : 0, Tk = p.mode == 1 ? p.Tk : 0;
+  const unsigned long long seed = (p.seed && p.drop_thresh) ? *p.seed : 0ull;
+  const unsigned int pk_o = amax_peek_block(p.o_amax);
+  LongStage st;
+  long_stage_load(st, p.k, p.ld_k, p.v, p.ld_v, g, S, Tk, head, 0);
+  AttnTileR qr;
+  attn_load_r(qr, p.q, p.ld_q, p, g, L, Tq, head, n, c, (int)qblk);
+  const int q = 16 * (int)qblk + n, qn = min(q, L - 1);
+  const bool active = 16 * (int)qblk < L;                 // (wave-uniform) a wave past the end of a ragged query tile only stages
+  float mx = -INFINITY, sum = 0.f, am_o = 0.f;
+  f32x4_t o[4];
+  attn_zero(o);
+  for (int k0 = 0; k0 < S; k0 += LONG_T) {
+    __syncthreads();                                      // the previous tile has been consumed
+    long_stage_store(st, Ks, Vs);
+    __syncthreads();
+    if (k0 + LONG_T < S) long_stage_load(st, p.k, p.ld_k, p.v, p.ld_v, g, S, Tk, head, k0 + LONG_T);
+    if (!active) continue;
+    const int nkb = min(LONG_T / 16, (S - k0 + 15) / 16);
+    for (int kb = 0; kb < nkb; ++kb) {
+      AttnTileR kr;
+      AttnTileG vg;
+      attn_lds_r(kr, Ks, LONG_T, n, c, kb);
+      attn_lds_g(vg, Vs, LONG_T, n, c, kb);
+      const f32x4_t sa = attn_mm_d(kr, qr);               // sa[i] = S[query q][key k0 + 16 kb + 4c+i]
+      float s[4], bm = -INFINITY;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        s[i] = long_dead(p, q, k0 + 16 * kb + 4 * c + i) ? -INFINITY : sa[i] * p.scale;
+        bm = fmaxf(bm, s[i]);
+      }
+      const float mn = fmaxf(mx, quad_max(bm));
+      const float al = mx == -INFINITY ? 0.f : __expf(mx - mn);
+      float bs = 0.f;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int j = k0 + 16 * kb + 4 * c + i;
+        float pr = s[i] == -INFINITY ? 0.f : __expf(s[i] - mn);
+        bs += pr;
+        if (p.drop_thresh && j < S)
+          pr *= drop_scale(seed, p.salt, ((unsigned long long)wid * L + qn) * S + j, p.drop_thresh, p.drop_inv_keep);
+        s[i] = pr;
+      }
+      sum = sum * al + quad_sum(bs);
+      mx = mn;
+      long_scale_rows(o, al, c);
+      attn_mm_rows(o, s, vg);                             // O[q][d] += sum_j (P mask)[q][j] V[j][d]
+    }
+  }
+  if (active) {
+    long_scale_rows(o, 1.f / sum, c);
+    attn_store_d(o, p.o, p.ld_o, p, g, L, Tq, head, n, c, (int)qblk, am_o);
+  }
+  amax_slot_commit_block(p.o_amax, am_o, red, pk_o);
+}
+
+// stat [3][nstat]: m, 1 / sum, delta of query q of (group, head) wid at wid * L + q
+__global__ __launch_bounds__(LONG_THREADS) void attn_long_bwd_q_kernel(AttnParams p, unsigned int ntile, float* stat, long long nstat) {
+  __shared__ __attribute__((aligned(16))) float Ks[LONG_T * LDT], Vs[LONG_T * LDT];
+  __shared__ float red[4];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, n = lane & 15, c = lane >> 4;
+  const unsigned int wid = blockIdx.x / ntile, qblk = 4 * (blockIdx.x - wid * ntile) + w;
+  const int head = (int)(wid % (unsigned int)p.heads);
+  const AttnRows g = attn_rows(p, wid / (unsigned int)p.heads);
+  const int L = p.L, S = p.S;
+  const int Tq = p.mode == 1 ? p.Tq : 0, Tk = p.mode == 1 ? p.Tk : 0;
+  const unsigned long long seed = (p.seed && p.drop_thresh) ? *p.seed : 0ull;
+  const unsigned int pk_q = amax_peek_block(p.dq_amax);
+  LongStage st;
+  long_stage_load(st, p.k, p.ld_k, p.v, p.ld_v, g, S, Tk, head, 0);
+  AttnTileR qr, gr;
+  attn_load_r(qr, p.q, p.ld_q, p, g, L, Tq, head, n, c, (int)qblk);
+  attn_load_r(gr, p.go, p.ld_o, p, g, L, Tq, head, n, c, (int)qblk);
+  const int q = 16 * (int)qblk + n, qn = min(q, L - 1);
+  const bool active = 16 * (int)qblk < L;
+  float mx = -INFINITY, sum = 0.f, dl = 0.f, inv = 0.f, am_q = 0.f;
+  f32x4_t dq[4];
+  attn_zero(dq);
+#pragma unroll 1
+  for (int pass = 0; pass < 2; ++pass) {
+    for (int k0 = 0; k0 < S; k0 += LONG_T) {
+      __syncthreads();
+      long_stage_store(st, Ks, Vs);
+      __syncthreads();
+      // the tile after this one; after the last tile of pass 1: the first tile again, for pass 2
+      const int nx = k0 + LONG_T < S ? k0 + LONG_T : 0;
+      if (nx || pass == 0) long_stage_load(st, p.k, p.ld_k, p.v, p.ld_v, g, S, Tk, head, nx);
+      if (!active) continue;
+      const int nkb = min(LONG_T / 16, (S - k0 + 15) / 16);
+      for (int kb = 0; kb < nkb; ++kb) {
+        AttnTileR kr, vr;
+        attn_lds_r(kr, Ks, LONG_T, n, c, kb);
+        attn_lds_r(vr, Vs, LONG_T, n, c, kb);
+        const f32x4_t sa = attn_mm_d(kr, qr), da = attn_mm_d(vr, gr);     // S and dP = dO V^T of [query q][key .. + 4c+i]
+        float s[4], dp[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const int j = k0 + 16 * kb + 4 * c + i;
+          s[i] = long_dead(p, q, j) ? -INFINITY : sa[i] * p.scale;
+          dp[i] = da[i];
+          if (p.drop_thresh && j < S)
+            dp[i] *= drop_scale(seed, p.salt, ((unsigned long long)wid * L + qn) * S + j, p.drop_thresh, p.drop_inv_keep);
+        }
+        if (pass == 0) {
+          const float mn = fmaxf(mx, quad_max(fmaxf(fmaxf(s[0], s[1]), fmaxf(s[2], s[3]))));
+          const float al = mx == -INFINITY ? 0.f : __expf(mx - mn);
+          float bs = 0.f, bd = 0.f;
+#pragma unroll
+          for (int i = 0; i < 4; ++i) {
+            const float pr = s[i] == -INFINITY ? 0.f : __expf(s[i] - mn);
+            bs += pr; bd += pr * dp[i];
+          }
+          sum = sum * al + quad_sum(bs);
+          dl = dl * al + quad_sum(bd);
+          mx = mn;
+        } else {
+          float ds[4];
+#pragma unroll
+          for (int i = 0; i < 4; ++i) ds[i] = s[i] == -INFINITY ? 0.f : __expf(s[i] - mx) * inv * (dp[i] - dl) * p.scale;
+          AttnTileG kg;
+          attn_lds_g(kg, Ks, LONG_T, n, c, kb);
+          attn_mm_rows(dq, ds, kg);                            // dQ[q][d] += sum_j dS[q][j] K[j][d]
+        }
+      }
+    }
+    if (pass == 0) {
+      inv = 1.f / sum;
+      dl *= inv;
+      if (active && c == 0 && q < L) {
+        float* sp = stat + (long long)wid * L + q;
+        sp[0] = mx; sp[nstat] = inv; sp[2 * nstat] = dl;
+      }
+    }
+  }
+  if (active) attn_store_d(dq, p.dq, p.ld_dq, p, g, L, Tq, head, n, c, (int)qblk, am_q);
+  amax_slot_commit_block(p.dq_amax, am_q, red, pk_q);
+}
+
+__global__ __launch_bounds__(LONG_THREADS) void attn_long_bwd_kv_kernel(AttnParams p, unsigned int ntile, const float* stat, long long nstat) {
+  __shared__ __attribute__((aligned(16))) float Qs[LONG_T * LDT], Gs[LONG_T * LDT];
+  __shared__ float Ss[3 * LONG_T], red[8];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, n = lane & 15, c = lane >> 4;
+  const unsigned int wid = blockIdx.x / ntile, kblk = 4 * (blockIdx.x - wid * ntile) + w;
+  const int head = (int)(wid % (unsigned int)p.heads);
+  const AttnRows g = attn_rows(p, wid / (unsigned int)p.heads);
+  const int L = p.L, S = p.S;
+  const int Tq = p.mode == 1 ? p.Tq : 0, Tk = p.mode == 1 ? p.Tk : 0;
+  const unsigned long long seed = (p.seed && p.drop_thresh) ? *p.seed : 0ull;
+  const unsigned int pk_k = amax_peek_block(p.dk_amax), pk_v = amax_peek_block(p.dv_amax);
+  // threads 0 .. 191 also carry the statistics of the query tile: thread 64 a + r the a-th statistic of its row r
+  const float* sp = stat + (threadIdx.x >> 6) * nstat + (long long)wid * L;
+  const int sr = threadIdx.x & 63;
+  LongStage st;
+  float sv = 0.f;
+  long_stage_load(st, p.q, p.ld_q, p.go, p.ld_o, g, L, Tq, head, 0);
+  if (threadIdx.x < 3 * LONG_T) sv = sp[min(sr, L - 1)];
+  AttnTileR kr, vr;
+  attn_load_r(kr, p.k, p.ld_k, p, g, S, Tk, head, n, c, (int)kblk);
+  attn_load_r(vr, p.v, p.ld_v, p, g, S, Tk, head, n, c, (int)kblk);
+  const int key = 16 * (int)kblk + n;
+  const bool active = 16 * (int)kblk < S;
+  float am_k = 0.f, am_v = 0.f;
+  f32x4_t dv[4], dk[4];
+  attn_zero(dv); attn_zero(dk);
+  for (int q0 = 0; q0 < L; q0 += LONG_T) {
+    __syncthreads();
+    long_stage_store(st, Qs, Gs);
+    if (threadIdx.x < 3 * LONG_T) Ss[threadIdx.x] = sv;
+    __syncthreads();
+    if (q0 + LONG_T < L) {
+      long_stage_load(st, p.q, p.ld_q, p.go, p.ld_o, g, L, Tq, head, q0 + LONG_T);
+      if (threadIdx.x < 3 * LONG_T) sv = sp[min(q0 + LONG_T + sr, L - 1)];
+    }
+    if (!active) continue;
+    const int nqb = min(LONG_T / 16, (L - q0 + 15) / 16);
+    for (int qb = 0; qb < nqb; ++qb) {
+      AttnTileR qt, gt;
+      attn_lds_r(qt, Qs, LONG_T, n, c, qb);
+      attn_lds_r(gt, Gs, LONG_T, n, c, qb);
+      const f32x4_t sb = attn_mm_d(qt, kr), db = attn_mm_d(gt, vr);       // S and dP of [query q0 + 16 qb + 4c+i][key]
+      float pd[4], ds[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int ql = 16 * qb + 4 * c + i, q = q0 + ql;
+        const float pr = (q >= L || long_dead(p, q, key)) ? 0.f : __expf(sb[i] * p.scale - Ss[ql]) * Ss[LONG_T + ql];
+        float m = 1.f;
+        if (p.drop_thresh && q < L && key < S)
+          m = drop_scale(seed, p.salt, ((unsigned long long)wid * L + q) * S + key, p.drop_thresh, p.drop_inv_keep);
+        pd[i] = pr * m;
+        ds[i] = pr * (db[i] * m - Ss[2 * LONG_T + ql]) * p.scale;
+      }
+      AttnTileG gg, qg;
+      attn_lds_g(gg, Gs, LONG_T, n, c, qb);
+      attn_lds_g(qg, Qs, LONG_T, n, c, qb);
+      attn_mm_rows(dv, pd, gg);                                  // dV[j][d] += sum_q Pd[q][j] dO[q][d]
+      attn_mm_rows(dk, ds, qg);                                  // dK[j][d] += sum_q dS[q][j] Q[q][d]
+    }
+  }
+  if (active) {
+    attn_store_d(dv, p.dv, p.ld_dv, p, g, S, Tk, head, n, c, (int)kblk, am_v);
+    attn_store_d(dk, p.dk, p.ld_dk, p, g, S, Tk, head, n, c, (int)kblk, am_k);
+  }
+  amax_slot_commit_block(p.dk_amax, am_k, red, pk_k);
+  amax_slot_commit_block(p.dv_amax, am_v, red + 4, pk_v);
+}
+
 static int attn_setup(AttnParams& p, int mode, int heads, int head_dim, int frames_or_N, int P, int W, int ws, int Tq,
-                      int Tk, int mask_mode, float drop_p, const unsigned long long* seed, unsigned int salt, bool bwd) {
+                      int Tk, int mask_mode, float drop_p, const unsigned long long* seed, unsigned int salt, bool bwd,
+                      bool any_length = false) {
   if (head_dim != HD) { npvp_set_error("attn: head_dim must be 64"); return NPVP_ERR_ARG; }
   if (drop_p < 0.f || drop_p >= 1.f || (drop_p > 0.f && !seed)) { npvp_set_error("attn: bad dropout arguments"); return NPVP_ERR_ARG; }
   p.mode = mode; p.heads = heads; p.P = P; p.W = W; p.ws = ws; p.Tq = Tq; p.Tk = Tk; p.mask_mode = mask_mode;
@@ -658,7 +928,10 @@ static int attn_setup(AttnParams& p, int mode, int heads, int head_dim, int fram
     p.nww = p.nwin = 1; p.L = Tq; p.S = Tk;
     groups = (long long)frames_or_N * P;
   }
-  if (p.L < 1 || p.S < 1 || p.L > GEN_MAX || p.S > GEN_MAX) { npvp_set_error("attn: sequence length must be in [1,128]"); return NPVP_ERR_ARG; }
+  if (any_length) {        // the streaming kernels (npvp_attn_long_*)
+    if (p.L < 1 || p.S < 1) { npvp_set_error("attn_long: sequence length must be at least 1"); return NPVP_ERR_ARG; }
+    if (mode == 0 && ws > 1024) { npvp_set_error("attn_long: window size must be at most 1024 (attn_row)"); return NPVP_ERR_ARG; }
+  } else if (p.L < 1 || p.S < 1 || p.L > GEN_MAX || p.S > GEN_MAX) { npvp_set_error("attn: sequence length must be in [1,128]"); return NPVP_ERR_ARG; }
   p.scale = 0.125f;   // 1/sqrt(64)
   p.drop_thresh = drop_p > 0.f ? drop_threshold(drop_p) : 0u;
   p.drop_inv_keep = drop_p > 0.f ? 1.f / (1.f - drop_p) : 1.f;
@@ -739,6 +1012,70 @@ extern "C" int npvp_attn_bwd(const float* q, long long ld_q, const float* k, lon
   else if (nq == 1) NPVP_LAUNCH((attn_bwd_mfma_kernel<1, 2>), mg, mb, 0, stream, p);
   else if (nk == 1) NPVP_LAUNCH((attn_bwd_staged1_kernel<2, 1>), dim3((unsigned)p.total), dim3(64), staged1_lds, stream, p);
   else NPVP_LAUNCH((attn_bwd_staged1_kernel<2, 2>), dim3((unsigned)p.total), dim3(64), staged1_lds, stream, p);
+  NPVP_CHECK_LAUNCH();
+  return NPVP_OK;
+}
+
+// ---- streaming kernels: the same functions for every L, S >= 1
+static int attn_long_grid(const AttnParams& p, int rows_n, unsigned int& ntile, unsigned int& blocks) {
+  ntile = (unsigned int)((rows_n + LONG_T - 1) / LONG_T);
+  const long long nb = p.total * (long long)ntile;
+  if (nb >= (1ll << 31)) { npvp_set_error("attn_long: too many (group, head, tile) workgroups for one launch"); return NPVP_ERR_ARG; }
+  blocks = (unsigned int)nb;
+  return NPVP_OK;
+}
+
+extern "C" int npvp_attn_long_fwd(const float* q, long long ld_q, const float* k, long long ld_k, const float* v, long long ld_v,
+                                  float* o, long long ld_o, int mode, int dim0, int P, int W, int ws, int Tq, int Tk, int heads,
+                                  int head_dim, int mask_mode, float drop_p, const unsigned long long* seed, unsigned int salt,
+                                  float* o_amax, hipStream_t stream) {
+  AttnParams p = {};
+  const int rc = attn_setup(p, mode, heads, head_dim, dim0, P, W, ws, Tq, Tk, mask_mode, drop_p, seed, salt, false, true);
+  if (rc) return rc;
+  p.o_amax = o_amax;
+  NPVP_CHECK_ARG(dim0 > 0, "attn_long: empty batch");
+  NPVP_CHECK_ARG(ld_q % 4 == 0 && ld_k % 4 == 0 && ld_v % 4 == 0 && ld_o % 4 == 0, "attn_long: row strides must be multiples of 4");
+  p.q = q; p.k = k; p.v = v; p.o = o; p.ld_q = ld_q; p.ld_k = ld_k; p.ld_v = ld_v; p.ld_o = ld_o;
+  unsigned int ntile, blocks;
+  if (attn_long_grid(p, p.L, ntile, blocks)) return NPVP_ERR_ARG;
+  NPVP_LAUNCH(attn_long_fwd_kernel, dim3(blocks), dim3(LONG_THREADS), 0, stream, p, ntile);
+  NPVP_CHECK_LAUNCH();
+  return NPVP_OK;
+}
+
+// the softmax statistics of every query row: [3][groups * heads * L] floats
+extern "C" long long npvp_attn_long_bwd_workspace_bytes(int mode, int dim0, int P, int W, int ws, int Tq, int Tk, int heads) {
+  (void)W; (void)Tk;
+  if (dim0 <= 0 || P <= 0 || heads <= 0 || (mode == 0 ? (ws <= 0 || P % (ws * ws) != 0) : Tq <= 0)) return 0;
+  const long long groups = mode == 0 ? (long long)dim0 * (P / (ws * ws)) : (long long)dim0 * P;
+  const long long L = mode == 0 ? (long long)ws * ws : Tq;
+  return 3ll * groups * heads * L * (long long)sizeof(float);
+}
+
+extern "C" int npvp_attn_long_bwd(const float* q, long long ld_q, const float* k, long long ld_k, const float* v, long long ld_v,
+                                  const float* go, long long ld_o, float* dq, long long ld_dq, float* dk, long long ld_dk,
+                                  float* dv, long long ld_dv, int mode, int dim0, int P, int W, int ws, int Tq, int Tk,
+                                  int heads, int head_dim, int mask_mode, float drop_p, const unsigned long long* seed,
+                                  unsigned int salt, float* dq_amax, float* dk_amax, float* dv_amax, void* workspace,
+                                  long long ws_bytes, hipStream_t stream) {
+  AttnParams p = {};
+  const int rc = attn_setup(p, mode, heads, head_dim, dim0, P, W, ws, Tq, Tk, mask_mode, drop_p, seed, salt, true, true);
+  if (rc) return rc;
+  p.dq_amax = dq_amax; p.dk_amax = dk_amax; p.dv_amax = dv_amax;
+  NPVP_CHECK_ARG(dim0 > 0, "attn_long_bwd: empty batch");
+  NPVP_CHECK_ARG(ld_q % 4 == 0 && ld_k % 4 == 0 && ld_v % 4 == 0 && ld_o % 4 == 0 && ld_dq % 4 == 0 && ld_dk % 4 == 0 &&
+                     ld_dv % 4 == 0, "attn_long_bwd: row strides must be multiples of 4");
+  const long long nstat = p.total * p.L;
+  if (!workspace || ws_bytes < 3 * nstat * (long long)sizeof(float)) {
+    npvp_set_error("attn_long_bwd: workspace too small (npvp_attn_long_bwd_workspace_bytes)"); return NPVP_ERR_WORKSPACE;
+  }
+  p.q = q; p.k = k; p.v = v; p.go = go; p.dq = dq; p.dk = dk; p.dv = dv;
+  p.ld_q = ld_q; p.ld_k = ld_k; p.ld_v = ld_v; p.ld_o = ld_o; p.ld_dq = ld_dq; p.ld_dk = ld_dk; p.ld_dv = ld_dv;
+  unsigned int qtile, qblocks, ktile, kblocks;
+  if (attn_long_grid(p, p.L, qtile, qblocks) || attn_long_grid(p, p.S, ktile, kblocks)) return NPVP_ERR_ARG;
+  float* stat = static_cast<float*>(workspace);
+  NPVP_LAUNCH(attn_long_bwd_q_kernel, dim3(qblocks), dim3(LONG_THREADS), 0, stream, p, qtile, stat, nstat);
+  NPVP_LAUNCH(attn_long_bwd_kv_kernel, dim3(kblocks), dim3(LONG_THREADS), 0, stream, p, ktile, (const float*)stat, nstat);
   NPVP_CHECK_LAUNCH();
   return NPVP_OK;
 }

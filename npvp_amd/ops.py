@@ -1157,17 +1157,33 @@ class AttnCfg:
         self.drop = Drop(p_drop)
 
 
+# Sequences of at least this many rows on either side take the streaming kernels (npvp_attn_long_*: any length); shorter ones the
+# kernels of npvp_attn_fwd / npvp_attn_bwd (up to 32: MFMA, 33 .. 128: generic), which end at 128.  A module constant so that
+# tools/attn_bench.py and a test can lower it and compare the two routes on the same shapes.
+ATTN_LONG_MIN = 129
+
+
+def _attn_len(cfg):
+    """(L, S): query and key rows per (group, head)"""
+    return (cfg.ws * cfg.ws, cfg.ws * cfg.ws) if cfg.mode == 0 else (cfg.Tq, cfg.Tk)
+
+
+def _attn_long(cfg):
+    return max(_attn_len(cfg)) >= ATTN_LONG_MIN
+
+
 def _attn_fwd(q, k, v, o, cfg):
     hd = o.shape[1] // cfg.heads
     seed = _S._cur.rng.seed_tensor(q.device) if cfg.drop.on else None
     if DropRecorder.sites is not None and cfg.drop.on:      # weights tensor [groups, heads, L, S]
-        L_, S_ = (cfg.ws * cfg.ws, cfg.ws * cfg.ws) if cfg.mode == 0 else (cfg.Tq, cfg.Tk)
+        L_, S_ = _attn_len(cfg)
         groups = cfg.dim0 * (cfg.P // (cfg.ws * cfg.ws)) if cfg.mode == 0 else cfg.dim0 * cfg.P
         DropRecorder.note(cfg.drop, "elem", groups * cfg.heads * L_ * S_)
     slot = _new_slot(q.device)
-    check(lib().npvp_attn_fwd(_ptr(q), q.stride(0), _ptr(k), k.stride(0), _ptr(v), v.stride(0), _ptr(o), o.stride(0),
-                              cfg.mode, cfg.dim0, cfg.P, cfg.W, cfg.ws, cfg.Tq, cfg.Tk, cfg.heads, hd, cfg.mask_mode,
-                              cfg.drop.p, _ptr(seed), cfg.drop.salt, _ptr(slot), _stream()), "npvp_attn_fwd")
+    fn, what = (lib().npvp_attn_long_fwd, "npvp_attn_long_fwd") if _attn_long(cfg) else (lib().npvp_attn_fwd, "npvp_attn_fwd")
+    check(fn(_ptr(q), q.stride(0), _ptr(k), k.stride(0), _ptr(v), v.stride(0), _ptr(o), o.stride(0),
+             cfg.mode, cfg.dim0, cfg.P, cfg.W, cfg.ws, cfg.Tq, cfg.Tk, cfg.heads, hd, cfg.mask_mode,
+             cfg.drop.p, _ptr(seed), cfg.drop.salt, _ptr(slot), _stream()), what)
     tag_amax(o, slot)
 
 
@@ -1178,10 +1194,16 @@ def _attn_bwd(q, k, v, go, dq, dk, dv, cfg, packed=None):
     sq = _new_slot(q.device)
     sk = sq if packed is not None else _new_slot(q.device)
     sv = _new_slot(q.device)
-    check(lib().npvp_attn_bwd(_ptr(q), q.stride(0), _ptr(k), k.stride(0), _ptr(v), v.stride(0), _ptr(go), go.stride(0),
-                              _ptr(dq), dq.stride(0), _ptr(dk), dk.stride(0), _ptr(dv), dv.stride(0), cfg.mode, cfg.dim0,
-                              cfg.P, cfg.W, cfg.ws, cfg.Tq, cfg.Tk, cfg.heads, hd, cfg.mask_mode, cfg.drop.p, _ptr(seed),
-                              cfg.drop.salt, _ptr(sq), _ptr(sk), _ptr(sv), _stream()), "npvp_attn_bwd")
+    args = (_ptr(q), q.stride(0), _ptr(k), k.stride(0), _ptr(v), v.stride(0), _ptr(go), go.stride(0),
+            _ptr(dq), dq.stride(0), _ptr(dk), dk.stride(0), _ptr(dv), dv.stride(0), cfg.mode, cfg.dim0,
+            cfg.P, cfg.W, cfg.ws, cfg.Tq, cfg.Tk, cfg.heads, hd, cfg.mask_mode, cfg.drop.p, _ptr(seed),
+            cfg.drop.salt, _ptr(sq), _ptr(sk), _ptr(sv))
+    if _attn_long(cfg):      # the streaming kernels recompute the softmax statistics of every query row into a workspace
+        ws, wsn = _ws(lib().npvp_attn_long_bwd_workspace_bytes(cfg.mode, cfg.dim0, cfg.P, cfg.W, cfg.ws, cfg.Tq, cfg.Tk, cfg.heads),
+                      q.device)
+        check(lib().npvp_attn_long_bwd(*args, _ptr(ws), wsn, _stream()), "npvp_attn_long_bwd")
+    else:
+        check(lib().npvp_attn_bwd(*args, _stream()), "npvp_attn_bwd")
     if packed is not None:
         tag_amax(packed, sq)
     else:
