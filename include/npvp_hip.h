@@ -524,6 +524,20 @@ int npvp_nonlocal_attn_fwd(const float* q, long long ldq, const float* k, long l
 int npvp_nonlocal_attn_bwd(const float* q, long long ldq, const float* k, long long ldk, const float* v, long long ldv, const float* go,
                            long long ldgo, const float* lse, float* D, float* dq, long long lddq,
                            float* dk, long long lddk, float* dv, long long lddv, int F, int H, int W, int A, int V, npvp_stream_t stream);
+/* The same core on ANY grid: F >= 1, H >= 2, W >= 2 (odd, rectangular, not a power of two), F*H*W < 2^31, (A, V) from the same
+ * table; same argument lists, same tie rule, same lse, same D [2][F*H*W] scratch.  Pooled grid Hp = H/2, Wp = W/2 (floor, as
+ * nn.MaxPool2d((2,2), stride=2)), Lk = Hp*Wp >= 1 keys; every query row attends.  Rows of an odd last line / column belong to no
+ * window: their dk / dv are exactly 0, written by a kernel (no memset), so every element of dq / dk / dv is written exactly once.
+ * A shape npvp_nonlocal_attn_fwd/bwd accept is passed on to them (the same launches, bit-identical results); every other shape
+ * launches a general form of the same kernels - same tiles, thread maps and summation order, partial last query / key tiles masked
+ * (masked key: score -inf, P = 0; masked query: no store, no contribution to dk / dv).  Deterministic, no atomics, no workspace.
+ * NPVP_NL_GRID_GENERAL=1 in the environment (read once) sends the config shapes to the general form too: a measurement aid. */
+int npvp_nonlocal_attn_grid_fwd(const float* q, long long ldq, const float* k, long long ldk, const float* v, long long ldv, float* o,
+                                long long ldo, float* lse, int F, int H, int W, int A, int V, npvp_stream_t stream);
+int npvp_nonlocal_attn_grid_bwd(const float* q, long long ldq, const float* k, long long ldk, const float* v, long long ldv,
+                                const float* go, long long ldgo, const float* lse, float* D, float* dq, long long lddq,
+                                float* dk, long long lddk, float* dv, long long lddv, int F, int H, int W, int A, int V,
+                                npvp_stream_t stream);
 
 /* ---- the data-parallel exchange: all-reduce(mean) of the parameter gradients, RCCL over xGMI, one process per GPU.
  * Replaces what the reference gets from Lightning's DDP strategy (ref/train_Predictor_lightning.py:40-42: strategy = 'ddp' over

@@ -128,6 +128,9 @@ SIGNATURES = {
     "npvp_nonlocal_attn_fwd": (c_int, [c_p, c_ll, c_p, c_ll, c_p, c_ll, c_p, c_ll, c_p, c_int, c_int, c_int, c_int, c_int, c_p]),
     "npvp_nonlocal_attn_bwd": (c_int, [c_p, c_ll, c_p, c_ll, c_p, c_ll, c_p, c_ll, c_p, c_p, c_p, c_ll, c_p, c_ll, c_p, c_ll, c_int, c_int,
                                        c_int, c_int, c_int, c_p]),
+    "npvp_nonlocal_attn_grid_fwd": (c_int, [c_p, c_ll, c_p, c_ll, c_p, c_ll, c_p, c_ll, c_p, c_int, c_int, c_int, c_int, c_int, c_p]),
+    "npvp_nonlocal_attn_grid_bwd": (c_int, [c_p, c_ll, c_p, c_ll, c_p, c_ll, c_p, c_ll, c_p, c_p, c_p, c_ll, c_p, c_ll, c_p, c_ll, c_int,
+                                            c_int, c_int, c_int, c_int, c_p]),
     "npvp_ssim_per_image": (c_int, [c_p, c_p, c_int, c_int, c_int, c_int, c_p, c_int, c_p, c_p, c_ll, c_p]),
 }
 

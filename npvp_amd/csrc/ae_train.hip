@@ -8,13 +8,17 @@
 //     sums[2C] = [sum g', sum g' xhat], both all-reduced by the caller, the element count n read on the device (uneven shards);
 //   - the non-local attention core softmax(q k^T) v (unscaled scores) with the 2x2 max-pool of K / V fused into the loads, flash
 //     style: online softmax forward, recomputation backward, the HW x HW/4 score matrix never leaves LDS; each pooled K / V gradient
-//     goes to its window's arg-max (first maximum in row-major window order, as torch's max_pool2d);
+//     goes to its window's arg-max (first maximum in row-major window order, as torch's max_pool2d); exact-tile kernels for the
+//     four (C, grid) pairs of the shipped configs, and a masked general form of the same kernels for any other H x W grid (odd,
+//     rectangular, not a power of two; floor pooling, the never-pooled last line / column gets dk = dv = 0 from a kernel);
 //   - ReflectionPad2d forward and a gather-form backward (every input pixel sums its mirror images in a fixed order).
 // Every kernel here is deterministic: no atomics, fixed summation order, bit-identical on repeated runs.
 //   BatchNorm / pad layouts: 0 = channels-last [outer][C] (the encoder), 1 = NCHW planes [N*C][H*W] (the decoder).
 // The attention runs on the f32 VALU (v_fma_f32): exact fp32 products at the same peak rate as the f32 MFMA (cdna_hip_programming §3),
 // and the head dimensions here (8..64) are too narrow to fill an MFMA tile without padding.
 #include "common.h"
+
+#include <stdlib.h>
 
 namespace npvp {
 
@@ -605,6 +609,308 @@ __global__ void __launch_bounds__(256) nl_attn_dkv_kernel(const float* __restric
   }
 }
 
+// ------------------------------------------------------------------------------------- non-local attention on any H x W grid
+// The general form of the three kernels above (same NL<A, V> tiles, same thread maps, same order of every sum): Hp = H/2, Wp = W/2
+// (floor), Lk = Hp Wp pooled keys.  The last query tile and the last key tile may be partial:
+//   - a query past the frame loads the frame's last row (valid memory, finite numbers), stores nothing, and enters dk / dv with P = 0;
+//   - a key past Lk has k = v = 0 in LDS, score -inf in the forward (P = exp(-inf - finite) = 0: tile 0 always holds key 0, so the
+//     running maximum is finite from the first tile on and no exp(-inf + inf) is formed) and P = 0 in the backward.
+// Wr[j] is the first row (2 ph) W + 2 pw of key j's window, -1 past Lk: the one division per key is done once per tile, by one
+// thread per key, not in the element loops.
+
+// the pooled value of pool_load for a window whose first row is r
+__device__ __forceinline__ float pool_at(const float* __restrict__ base, long long ld, int r0, int W, int col, int& am) {
+  const long long r = r0;
+  const float v0 = base[r * ld + col], v1 = base[(r + 1) * ld + col], v2 = base[(r + W) * ld + col], v3 = base[(r + W + 1) * ld + col];
+  float m = v0; am = 0;
+  if (v1 > m) { m = v1; am = 1; }
+  if (v2 > m) { m = v2; am = 2; }
+  if (v3 > m) { m = v3; am = 3; }
+  return m;
+}
+
+// caller syncs before the first read of Wr
+template <int KT>
+__device__ __forceinline__ void nlg_windows(int k0, int Lk, int Wp, int W, int* Wr) {
+  if (threadIdx.x < KT) {
+    const int key = k0 + threadIdx.x, ph = key / Wp;
+    Wr[threadIdx.x] = key < Lk ? 2 * ph * W + 2 * (key - ph * Wp) : -1;
+  }
+}
+
+template <int A, int V, int KT>
+__device__ __forceinline__ void nlg_load_kv(const float* __restrict__ kf, long long ldk, const float* __restrict__ vf, long long ldv,
+                                            const int* Wr, int W, float* Ks, float* Vs) {
+  constexpr int AP = A + 1;
+  for (int e = threadIdx.x; e < KT * A; e += 256) {
+    const int j = e / A, d = e % A, r = Wr[j];
+    int am;
+    Ks[j * AP + d] = r >= 0 ? pool_at(kf, ldk, r, W, d, am) : 0.f;
+  }
+  for (int e = threadIdx.x; e < KT * V; e += 256) {
+    const int j = e / V, c = e % V, r = Wr[j];
+    int am;
+    Vs[j * V + c] = r >= 0 ? pool_at(vf, ldv, r, W, c, am) : 0.f;
+  }
+}
+
+// nl_scores with the key mask: mode 0 stores S (-inf at a masked key), mode 1 exp(S - lse[qi]) (0 at a masked key)
+template <int A, int QT, int KT>
+__device__ __forceinline__ void nlg_scores(const float* Qs, const float* Ks, float* Ss, const float* Ls, const int* Wr, int mode) {
+  constexpr int AP = A + 1;
+  for (int e = threadIdx.x; e < QT * KT; e += 256) {
+    const int qi = e / KT, j = e % KT;
+    float s = 0.f;
+#pragma unroll
+    for (int d = 0; d < A; ++d) s = fmaf(Qs[qi * AP + d], Ks[j * AP + d], s);
+    const bool live = Wr[j] >= 0;
+    Ss[qi * (KT + 1) + j] = mode ? (live ? expf(s - Ls[qi]) : 0.f) : (live ? s : -INFINITY);
+  }
+}
+
+template <int A, int V>
+__global__ void __launch_bounds__(256) nlg_attn_fwd_kernel(const float* __restrict__ q, long long ldq, const float* __restrict__ k,
+                                                           long long ldk, const float* __restrict__ v, long long ldv,
+                                                           float* __restrict__ o, long long ldo, float* __restrict__ lse, int HW, int W,
+                                                           int Wp, int Lk) {
+  using C = NL<A, V>;
+  constexpr int QT = C::QT, KT = C::KT, TPQ = C::TPQ, AP = C::AP;
+  __shared__ float Qs[QT * AP], Ks[KT * AP], Vs[KT * V], Ss[QT * (KT + 1)];
+  __shared__ int Wr[KT];
+  const int tiles = (HW + QT - 1) / QT;
+  const int f = blockIdx.x / tiles, q0 = (blockIdx.x - f * tiles) * QT;
+  const long long fb = (long long)f * HW;
+  for (int e = threadIdx.x; e < QT * A; e += 256) Qs[(e / A) * AP + e % A] = q[(fb + min(q0 + e / A, HW - 1)) * ldq + e % A];
+  const int qi = threadIdx.x / TPQ, j0 = threadIdx.x % TPQ;
+  float acc[16];
+#pragma unroll
+  for (int i = 0; i < 16; ++i) acc[i] = 0.f;
+  float mrun = -INFINITY, l = 0.f;
+  for (int k0 = 0; k0 < Lk; k0 += KT) {
+    __syncthreads();
+    nlg_windows<KT>(k0, Lk, Wp, W, Wr);
+    __syncthreads();
+    nlg_load_kv<A, V, KT>(k + fb * ldk, ldk, v + fb * ldv, ldv, Wr, W, Ks, Vs);
+    __syncthreads();
+    nlg_scores<A, QT, KT>(Qs, Ks, Ss, nullptr, Wr, 0);
+    __syncthreads();
+    const float* srow = Ss + qi * (KT + 1);
+    float mx = mrun;
+    for (int j = 0; j < KT; ++j) mx = fmaxf(mx, srow[j]);
+    const float corr = expf(mrun - mx);
+    l *= corr;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) acc[i] *= corr;
+    for (int j = 0; j < KT; ++j) {
+      const float p = expf(srow[j] - mx);
+      l += p;
+#pragma unroll
+      for (int i = 0; i < 16; ++i) acc[i] = fmaf(p, Vs[j * V + j0 + TPQ * i], acc[i]);
+    }
+    mrun = mx;
+  }
+  if (q0 + qi >= HW) return;
+  const float inv = 1.f / l;
+  const long long row = fb + q0 + qi;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) o[row * ldo + j0 + TPQ * i] = acc[i] * inv;
+  if (j0 == 0) lse[row] = mrun + logf(l);
+}
+
+// rows: F*H*W, the offset of the second half of D
+template <int A, int V>
+__global__ void __launch_bounds__(256) nlg_attn_dq_kernel(const float* __restrict__ q, long long ldq, const float* __restrict__ k,
+                                                          long long ldk, const float* __restrict__ v, long long ldv,
+                                                          const float* __restrict__ go,
+                                                          long long ldgo, const float* __restrict__ lse, float* __restrict__ Dout,
+                                                          float* __restrict__ dq, long long lddq, long long rows, int HW, int W, int Wp,
+                                                          int Lk) {
+  using C = NL<A, V>;
+  constexpr int QT = C::QT, KT = C::KT, TPQ = C::TPQ, AP = C::AP;
+  constexpr int NQ = QT * A / 256;
+  __shared__ float Qs[QT * AP], Ks[KT * AP], Vs[KT * V], Ss[QT * (KT + 1)], Ls[QT];
+  __shared__ int Wr[KT];
+  const int tiles = (HW + QT - 1) / QT;
+  const int f = blockIdx.x / tiles, q0 = (blockIdx.x - f * tiles) * QT;
+  const long long fb = (long long)f * HW;
+  for (int e = threadIdx.x; e < QT * A; e += 256) Qs[(e / A) * AP + e % A] = q[(fb + min(q0 + e / A, HW - 1)) * ldq + e % A];
+  const int qi = threadIdx.x / TPQ, j0 = threadIdx.x % TPQ;
+  const bool live = q0 + qi < HW;
+  const long long row = fb + min(q0 + qi, HW - 1);
+  float g[16];
+#pragma unroll
+  for (int i = 0; i < 16; ++i) g[i] = go[row * ldgo + j0 + TPQ * i];
+  if (j0 == 0) Ls[qi] = lse[row];
+  double dacc = 0.0, pacc = 0.0;
+  for (int k0 = 0; k0 < Lk; k0 += KT) {
+    __syncthreads();
+    nlg_windows<KT>(k0, Lk, Wp, W, Wr);
+    __syncthreads();
+    nlg_load_kv<A, V, KT>(k + fb * ldk, ldk, v + fb * ldv, ldv, Wr, W, Ks, Vs);
+    __syncthreads();
+    nlg_scores<A, QT, KT>(Qs, Ks, Ss, Ls, Wr, 1);            // P
+    __syncthreads();
+    for (int j = 0; j < KT; ++j) {
+      float dp = 0.f;
+#pragma unroll
+      for (int i = 0; i < 16; ++i) dp = fmaf(g[i], Vs[j * V + j0 + TPQ * i], dp);
+      dp = group_sum<TPQ>(dp);
+      const double p = (double)Ss[qi * (KT + 1) + j];
+      dacc += p * (double)dp;
+      pacc += p;
+    }
+  }
+  const float dsum = (float)(dacc / pacc), rinv = (float)(1.0 / pacc);
+  if (j0 == 0 && live) { Dout[row] = dsum; Dout[rows + row] = rinv; }
+  float acc[NQ];
+#pragma unroll
+  for (int m = 0; m < NQ; ++m) acc[m] = 0.f;
+  for (int k0 = 0; k0 < Lk; k0 += KT) {
+    __syncthreads();
+    nlg_windows<KT>(k0, Lk, Wp, W, Wr);
+    __syncthreads();
+    nlg_load_kv<A, V, KT>(k + fb * ldk, ldk, v + fb * ldv, ldv, Wr, W, Ks, Vs);
+    __syncthreads();
+    nlg_scores<A, QT, KT>(Qs, Ks, Ss, Ls, Wr, 1);            // P
+    __syncthreads();
+    for (int j = 0; j < KT; ++j) {
+      float dp = 0.f;
+#pragma unroll
+      for (int i = 0; i < 16; ++i) dp = fmaf(g[i], Vs[j * V + j0 + TPQ * i], dp);
+      dp = group_sum<TPQ>(dp);
+      if (j0 == 0) { float* s = Ss + qi * (KT + 1) + j; *s = (*s * rinv) * (dp - dsum); }       // dS = Phat (dP - D)
+    }
+    __syncthreads();
+#pragma unroll
+    for (int m = 0; m < NQ; ++m) {
+      const int e = threadIdx.x + 256 * m, qq = e / A, d = e % A;
+      float s = acc[m];
+      for (int j = 0; j < KT; ++j) s = fmaf(Ss[qq * (KT + 1) + j], Ks[j * AP + d], s);
+      acc[m] = s;
+    }
+  }
+#pragma unroll
+  for (int m = 0; m < NQ; ++m) {
+    const int e = threadIdx.x + 256 * m, qq = e / A, d = e % A;
+    if (q0 + qq < HW) dq[(fb + q0 + qq) * lddq + d] = acc[m];
+  }
+}
+
+template <int A, int V>
+__global__ void __launch_bounds__(256) nlg_attn_dkv_kernel(const float* __restrict__ q, long long ldq, const float* __restrict__ k,
+                                                           long long ldk, const float* __restrict__ v, long long ldv,
+                                                           const float* __restrict__ go, long long ldgo, const float* __restrict__ lse,
+                                                           const float* __restrict__ Din, float* __restrict__ dk, long long lddk,
+                                                           float* __restrict__ dv, long long lddv, long long rows, int HW, int W, int Wp,
+                                                           int Lk) {
+  using C = NL<A, V>;
+  constexpr int KB = C::KB, QB = C::QB, TPQ = C::TPQ, AP = C::AP;
+  constexpr int NK = KB * A / 256;
+  __shared__ float Ks[KB * AP], Qs[QB * AP], Gs[QB * V], Ps[KB * (QB + 1)], Es[KB * (QB + 1)], Ls[QB], Ds[QB], Rs[QB];
+  __shared__ unsigned char Kam[KB * A], Vam[KB * V];
+  __shared__ int Wr[KB];
+  const int tiles = (Lk + KB - 1) / KB;
+  const int f = blockIdx.x / tiles, kb0 = (blockIdx.x - f * tiles) * KB;
+  const long long fb = (long long)f * HW;
+  nlg_windows<KB>(kb0, Lk, Wp, W, Wr);
+  __syncthreads();
+  for (int e = threadIdx.x; e < KB * A; e += 256) {
+    const int r = Wr[e / A];
+    int am = 0;
+    Ks[(e / A) * AP + e % A] = r >= 0 ? pool_at(k + fb * ldk, ldk, r, W, e % A, am) : 0.f;
+    Kam[e] = (unsigned char)am;
+  }
+  const int jr = threadIdx.x / TPQ, j0 = threadIdx.x % TPQ;
+  const int wr = Wr[jr];
+  float vr[16], dvr[16];
+#pragma unroll
+  for (int i = 0; i < 16; ++i) {
+    int am = 0;
+    vr[i] = wr >= 0 ? pool_at(v + fb * ldv, ldv, wr, W, j0 + TPQ * i, am) : 0.f;
+    Vam[jr * V + j0 + TPQ * i] = (unsigned char)am;
+    dvr[i] = 0.f;
+  }
+  float dkr[NK];
+#pragma unroll
+  for (int m = 0; m < NK; ++m) dkr[m] = 0.f;
+  for (int q0 = 0; q0 < HW; q0 += QB) {
+    __syncthreads();
+    for (int e = threadIdx.x; e < QB * A; e += 256) Qs[(e / A) * AP + e % A] = q[(fb + min(q0 + e / A, HW - 1)) * ldq + e % A];
+    for (int e = threadIdx.x; e < QB * V; e += 256) Gs[e] = go[(fb + min(q0 + e / V, HW - 1)) * ldgo + e % V];
+    if (threadIdx.x < QB) {
+      const long long rw = fb + min(q0 + (int)threadIdx.x, HW - 1);
+      Ls[threadIdx.x] = lse[rw]; Ds[threadIdx.x] = Din[rw];
+      Rs[threadIdx.x] = q0 + (int)threadIdx.x < HW ? Din[rows + rw] : 0.f;     // r = 0: a query past the frame has Phat = 0
+    }
+    __syncthreads();
+    for (int e = threadIdx.x; e < KB * QB; e += 256) {
+      const int jj = e / QB, qi = e % QB;
+      float s = 0.f;
+#pragma unroll
+      for (int d = 0; d < A; ++d) s = fmaf(Qs[qi * AP + d], Ks[jj * AP + d], s);
+      Ps[jj * (QB + 1) + qi] = expf(s - Ls[qi]) * Rs[qi];
+    }
+    __syncthreads();
+    for (int qi = 0; qi < QB; ++qi) {
+      const float p = Ps[jr * (QB + 1) + qi];
+      float dp = 0.f;
+#pragma unroll
+      for (int i = 0; i < 16; ++i) {
+        const float gg = Gs[qi * V + j0 + TPQ * i];
+        dp = fmaf(gg, vr[i], dp);
+        dvr[i] = fmaf(p, gg, dvr[i]);
+      }
+      dp = group_sum<TPQ>(dp);
+      if (j0 == 0) Es[jr * (QB + 1) + qi] = p * (dp - Ds[qi]);
+    }
+    __syncthreads();
+#pragma unroll
+    for (int m = 0; m < NK; ++m) {
+      const int e = threadIdx.x + 256 * m, jj = e / A, d = e % A;
+      float s = dkr[m];
+      for (int qi = 0; qi < QB; ++qi) s = fmaf(Es[jj * (QB + 1) + qi], Qs[qi * AP + d], s);
+      dkr[m] = s;
+    }
+  }
+  __syncthreads();
+  if (wr >= 0) {
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+      const int c = j0 + TPQ * i;
+      const int am = Vam[jr * V + c];
+      const long long r = fb + wr;
+      dv[r * lddv + c] = am == 0 ? dvr[i] : 0.f;
+      dv[(r + 1) * lddv + c] = am == 1 ? dvr[i] : 0.f;
+      dv[(r + W) * lddv + c] = am == 2 ? dvr[i] : 0.f;
+      dv[(r + W + 1) * lddv + c] = am == 3 ? dvr[i] : 0.f;
+    }
+  }
+#pragma unroll
+  for (int m = 0; m < NK; ++m) {
+    const int e = threadIdx.x + 256 * m, jj = e / A, d = e % A;
+    const int w0 = Wr[jj];
+    if (w0 < 0) continue;
+    const int am = Kam[e];
+    const long long r = fb + w0;
+    dk[r * lddk + d] = am == 0 ? dkr[m] : 0.f;
+    dk[(r + 1) * lddk + d] = am == 1 ? dkr[m] : 0.f;
+    dk[(r + W) * lddk + d] = am == 2 ? dkr[m] : 0.f;
+    dk[(r + W + 1) * lddk + d] = am == 3 ? dkr[m] : 0.f;
+  }
+}
+
+// dk = dv = 0 on the rows no window covers: the last line of an odd H (W rows a frame), then the last column of an odd W (the
+// corner belongs to the line): n rows a frame.  One block per such row, so with the dk / dv kernel every element is written exactly
+// once.
+__global__ void __launch_bounds__(64) nlg_attn_edge_kernel(float* __restrict__ dk, long long lddk, float* __restrict__ dv, long long lddv,
+                                                           int H, int W, int n, int A, int V) {
+  const int line = (H & 1) ? W : 0;
+  const int f = blockIdx.x / n, i = blockIdx.x - f * n;
+  const long long r = (long long)f * H * W + (i < line ? (long long)(H - 1) * W + i : (long long)(i - line) * W + W - 1);
+  for (int c = threadIdx.x; c < A; c += 64) dk[r * lddk + c] = 0.f;
+  for (int c = threadIdx.x; c < V; c += 64) dv[r * lddv + c] = 0.f;
+}
+
 static inline int clampi(long long v, int lo, int hi) { return (int)(v < lo ? lo : v > hi ? hi : v); }
 
 }  // namespace npvp
@@ -832,6 +1138,71 @@ extern "C" int npvp_nonlocal_attn_bwd(const float* q, long long ldq, const float
   }
   NL_DISPATCH(NL_BWD)
 #undef NL_BWD
+  NPVP_CHECK_LAUNCH();
+  return NPVP_OK;
+}
+
+// ---- non-local attention on any grid.  A shape the entry points above accept goes to them (the same launches, the same bits);
+// every other H, W >= 2 launches the general kernels.  NPVP_NL_GRID_GENERAL=1 sends the config shapes to the general kernels too
+// (measurements: what the masks cost at a shape both forms can run).
+static bool nl_config_shape(int H, int W, int A) {
+  return H % 2 == 0 && (W & (W - 1)) == 0 && (long long)H * W == (A == 8 ? 4096 : A == 16 ? 1024 : A == 32 ? 256 : 64);
+}
+
+static bool nlg_force_general() {
+  static const bool on = [] { const char* e = getenv("NPVP_NL_GRID_GENERAL"); return e && e[0] == '1'; }();
+  return on;
+}
+
+static int nlg_check(int F, int H, int W, int A, int V) {
+  NPVP_CHECK_ARG(F > 0 && H >= 2 && W >= 2, "nonlocal_attn_grid: F >= 1, H >= 2, W >= 2");
+  const bool shape = (A == 8 && V == 32) || (A == 16 && V == 64) || (A == 32 && V == 128) || (A == 64 && V == 256);
+  NPVP_CHECK_ARG(shape, "nonlocal_attn_grid: (attn dim, value dim) must be (8,32), (16,64), (32,128) or (64,256): C = 64..512 of the AE configs");
+  NPVP_CHECK_ARG((long long)F * H * W < (1ll << 31), "nonlocal_attn_grid: too many rows (F*H*W < 2^31)");
+  return NPVP_OK;
+}
+
+extern "C" int npvp_nonlocal_attn_grid_fwd(const float* q, long long ldq, const float* k, long long ldk, const float* v, long long ldv,
+                                           float* o, long long ldo, float* lse, int F, int H, int W, int A, int V, hipStream_t stream) {
+  NPVP_CHECK_ARG(q && k && v && o && lse, "nonlocal_attn_grid_fwd: null buffer");
+  if (int rc = nlg_check(F, H, W, A, V)) return rc;
+  NPVP_CHECK_ARG(ldq >= A && ldk >= A && ldv >= V && ldo >= V, "nonlocal_attn_grid_fwd: leading dimensions");
+  if (nl_config_shape(H, W, A) && !nlg_force_general())
+    return npvp_nonlocal_attn_fwd(q, ldq, k, ldk, v, ldv, o, ldo, lse, F, H, W, A, V, stream);
+  const int HW = H * W, Wp = W / 2, Lk = (H / 2) * Wp, QT = 4096 / V;
+  const unsigned grid = (unsigned)((long long)F * ((HW + QT - 1) / QT));
+#define NLG_FWD(a, vv) NPVP_LAUNCH((nlg_attn_fwd_kernel<a, vv>), dim3(grid), dim3(256), 0, stream, q, ldq, k, ldk, v, ldv, o, ldo, lse, HW, W, Wp, Lk);
+  NL_DISPATCH(NLG_FWD)
+#undef NLG_FWD
+  NPVP_CHECK_LAUNCH();
+  return NPVP_OK;
+}
+
+extern "C" int npvp_nonlocal_attn_grid_bwd(const float* q, long long ldq, const float* k, long long ldk, const float* v, long long ldv,
+                                           const float* go, long long ldgo, const float* lse, float* D,
+                                           float* dq, long long lddq, float* dk, long long lddk, float* dv, long long lddv, int F, int H,
+                                           int W, int A, int V, hipStream_t stream) {
+  NPVP_CHECK_ARG(q && k && v && go && lse && D && dq && dk && dv, "nonlocal_attn_grid_bwd: null buffer");
+  if (int rc = nlg_check(F, H, W, A, V)) return rc;
+  NPVP_CHECK_ARG(ldq >= A && ldk >= A && ldv >= V && ldgo >= V && lddq >= A && lddk >= A && lddv >= V,
+                 "nonlocal_attn_grid_bwd: leading dimensions");
+  if (nl_config_shape(H, W, A) && !nlg_force_general())
+    return npvp_nonlocal_attn_bwd(q, ldq, k, ldk, v, ldv, go, ldgo, lse, D, dq, lddq, dk, lddk, dv, lddv, F, H, W, A, V, stream);
+  const int HW = H * W, Wp = W / 2, Lk = (H / 2) * Wp, T = 4096 / V;      // T = QT = KB
+  const long long rows = (long long)F * HW;
+  const unsigned gq = (unsigned)((long long)F * ((HW + T - 1) / T)), gk = (unsigned)((long long)F * ((Lk + T - 1) / T));
+  const int edge = ((H & 1) ? W : 0) + ((W & 1) ? H - (H & 1) : 0);       // rows of a frame that no window covers
+#define NLG_BWD(a, vv)                                                                                                             \
+  {                                                                                                                                \
+    NPVP_LAUNCH((nlg_attn_dq_kernel<a, vv>), dim3(gq), dim3(256), 0, stream, q, ldq, k, ldk, v, ldv, go, ldgo, lse, D, dq,         \
+                lddq, rows, HW, W, Wp, Lk);                                                                                        \
+    NPVP_LAUNCH((nlg_attn_dkv_kernel<a, vv>), dim3(gk), dim3(256), 0, stream, q, ldq, k, ldk, v, ldv, go, ldgo, lse, D, dk, lddk,  \
+                dv, lddv, rows, HW, W, Wp, Lk);                                                                                    \
+  }
+  NL_DISPATCH(NLG_BWD)
+#undef NLG_BWD
+  if (edge)
+    NPVP_LAUNCH(nlg_attn_edge_kernel, dim3((unsigned)((long long)F * edge)), dim3(64), 0, stream, dk, lddk, dv, lddv, H, W, edge, A, V);
   NPVP_CHECK_LAUNCH();
   return NPVP_OK;
 }

@@ -2,8 +2,9 @@
 the same state-dict keys, run through the HIP ops of csrc/ae_train.hip instead of stock torch:
   [pad] conv [BatchNorm2d [ReLU]] [+ skip]  ->  ops.reflect_pad, the convolution (MIOpen), ops.bn_act_train (statistics + one apply
                                                pass, skip-add fused)
-  NonLocalAttenion2D                        ->  one GEMM for [Wq | Wk | Wv] (ops.linear), ops.nonlocal_attn_packed (pooling fused, no
-                                               score matrix in HBM), out_proj (ops.linear), ops.bn_act_train + ReLU, x + gamma * h
+  NonLocalAttenion2D                        ->  one GEMM for [Wq | Wk | Wv] (ops.linear), ops.nonlocal_attn_packed at the configs' own grids,
+                                               ops.nonlocal_attn_grid_packed at any other (pooling fused, no score matrix in
+                                               HBM), out_proj (ops.linear), ops.bn_act_train + ReLU, x + gamma * h
 `prepare_trainable_autoencoder` binds these forwards to the two module INSTANCES; the classes, their forward methods and the frozen
 Stage-2 path (build_frozen_autoencoder / fuse_frozen_autoencoder) are untouched.
 """
@@ -85,9 +86,27 @@ def _attn(a, x):
         ws = ws + [torch.zeros(pad, C, device=x.device)]
         if bs is not None:
             bs = bs + [torch.zeros(pad, device=x.device)]
+    # the GEMM's weight gradient sums over the token rows and wants their count % 32 == 0 (every config grid has it; 4 frames of a
+    # 6x10 or 3x5 grid have not): zero rows are appended to the two projections' inputs and cut from their outputs - they add
+    # exact zeros to dW, and the cut hands zero gradient rows back, so db is untouched too
+    R = N * H * W
+    rpad = -R % 32
+    if rpad:
+        tok = nn.functional.pad(tok, (0, 0, 0, rpad))
     qkv = ops.linear(tok, torch.cat(ws, 0), torch.cat(bs, 0) if bs is not None else None)
-    o = ops.nonlocal_attn_packed(qkv, N, H, W, A, V)
-    out = ops.linear(o, a.out_proj.weight, a.out_proj.bias).view(N, H, W, C).permute(0, 3, 1, 2)
+    if rpad:
+        qkv = qkv[:R]
+    # the configs' own (C, grid) pairs keep their exact-tile kernels; any other grid takes the general ones (an (A, V) that no
+    # kernel has is refused by either op: it stays with the first, as before)
+    other_grid = ops.nonlocal_attn_dims(A, V) and not ops.nonlocal_attn_config_shape(A, V, H, W)
+    nl = ops.nonlocal_attn_grid_packed if other_grid else ops.nonlocal_attn_packed
+    o = nl(qkv, N, H, W, A, V)
+    if rpad:
+        o = nn.functional.pad(o, (0, 0, 0, rpad))
+    out = ops.linear(o, a.out_proj.weight, a.out_proj.bias)
+    if rpad:
+        out = out[:R]
+    out = out.view(N, H, W, C).permute(0, 3, 1, 2)
     relu = isinstance(a.activ_func, nn.ReLU)
     if isinstance(a.norm_func, nn.BatchNorm2d):
         h = _bn(a.norm_func, out, 1 if relu else 0)

@@ -2059,6 +2059,75 @@ def nonlocal_attn(q, k, v, H, W):
     return nonlocal_attn_packed(qkv, F, H, W, A, V).view(F, P, V)
 
 
+def nonlocal_attn_dims(A, V):
+    """True where the non-local attention kernels have an instantiation for (attn dim, value dim)"""
+    return A in _NL_GRID and V == 4 * A
+
+
+def nonlocal_attn_config_shape(A, V, H, W):
+    """True where (A, V) and the H x W grid are a pair of the shipped AE configs: what nonlocal_attn_packed accepts (_NL_GRID)"""
+    return nonlocal_attn_dims(A, V) and H * W == _NL_GRID[A] ** 2 and H % 2 == 0 and W & (W - 1) == 0
+
+
+class _NonLocalAttnGrid(torch.autograd.Function):
+    """_NonLocalAttn on any H x W grid (npvp_nonlocal_attn_grid_*): floor pooling, the never-pooled last line / column of an odd grid
+    gets dk = dv = 0 from the backward's own kernels"""
+
+    @staticmethod
+    def forward(ctx, qkv, F, H, W, A, V):
+        remember(ctx)
+        _chk(qkv)
+        qkv = _c(qkv)
+        ld = qkv.shape[1]
+        o = torch.empty(F * H * W, V, dtype=torch.float32, device=qkv.device)
+        lse = torch.empty(F * H * W, dtype=torch.float32, device=qkv.device)
+        p = qkv.data_ptr()
+        check(lib().npvp_nonlocal_attn_grid_fwd(p, ld, p + 4 * A, ld, p + 8 * A, ld, _ptr(o), V, _ptr(lse), F, H, W, A, V, _stream()),
+              "npvp_nonlocal_attn_grid_fwd")
+        ctx.save_for_backward(qkv, lse)
+        ctx.dims = (F, H, W, A, V)
+        return o
+
+    @scoped
+    def backward(ctx, go):
+        qkv, lse = ctx.saved_tensors
+        F, H, W, A, V = ctx.dims
+        _chk(go)
+        go = _c(go)
+        ld = qkv.shape[1]
+        dqkv = torch.empty_like(qkv)
+        if ld > 2 * A + V:
+            dqkv[:, 2 * A + V:].zero_()
+        D = torch.empty(2 * F * H * W, dtype=torch.float32, device=qkv.device)
+        p, d = qkv.data_ptr(), dqkv.data_ptr()
+        check(lib().npvp_nonlocal_attn_grid_bwd(p, ld, p + 4 * A, ld, p + 8 * A, ld, _ptr(go), V, _ptr(lse), _ptr(D),
+                                                d, ld, d + 4 * A, ld, d + 8 * A, ld, F, H, W, A, V, _stream()),
+              "npvp_nonlocal_attn_grid_bwd")
+        return dqkv, None, None, None, None, None
+
+
+def nonlocal_attn_grid_packed(qkv, F, H, W, A, V):
+    """nonlocal_attn_packed on any grid H, W >= 2 (odd, rectangular, not a power of two): the keys / values are the
+    floor(H/2) x floor(W/2) windows of nn.MaxPool2d((2, 2), stride=2); a config shape runs nonlocal_attn_packed's own kernels"""
+    if not nonlocal_attn_dims(A, V):
+        raise RuntimeError(f"nonlocal_attn_grid: (attn dim, value dim) = ({A}, {V}) is not one of {[(a, 4 * a) for a in _NL_GRID]}")
+    if H < 2 or W < 2:
+        raise RuntimeError(f"nonlocal_attn_grid: a {H}x{W} grid has no 2x2 window")
+    if qkv.dim() != 2 or qkv.shape[0] != F * H * W or qkv.shape[1] < 2 * A + V:
+        raise RuntimeError(f"nonlocal_attn_grid: qkv must be [F*H*W, >= {2 * A + V}]")
+    return _NonLocalAttnGrid.apply(qkv, F, H, W, A, V)
+
+
+def nonlocal_attn_grid(q, k, v, H, W):
+    """nonlocal_attn on any grid H, W >= 2"""
+    F, P, A = q.shape
+    V = v.shape[-1]
+    if k.shape != q.shape or v.shape[:2] != q.shape[:2] or P != H * W:
+        raise RuntimeError("nonlocal_attn_grid: q / k (F, H*W, a), v (F, H*W, v)")
+    qkv = torch.cat([q.reshape(F * P, A), k.reshape(F * P, A), v.reshape(F * P, V)], 1)
+    return nonlocal_attn_grid_packed(qkv, F, H, W, A, V).view(F, P, V)
+
+
 class _ReflectPad(torch.autograd.Function):
     """ReflectionPad2d(P) forward, gather-form backward (npvp_reflect_pad)"""
 

@@ -7,7 +7,10 @@ separate `rocprofv3 --kernel-trace --stats` run).
 unchanged - what the data-parallel machinery costs a step beyond its transfers: "hip_gs" = GradSync's bucket all-reduces alone
 (plain BatchNorm), "hip_dp" = ae_data_parallel (GradSync + synchronised BatchNorm's two small all-reduces per layer).  With --repeats R the paths are timed R times in
 alternation and every window is reported.
-Usage: python tools/ae_train_bench.py --config {BAIR,KTH,KITTI} [--steps 10] [--warmup 3] [--batch B] [--dp] [--repeats R] [--paths hip,hip_gs,hip_dp]"""
+--size H W trains at H x W frames (each a multiple of 2**n_downsampling) instead of the config's own: off the configs' sizes the
+HIP path's attention runs the any-grid kernels (ops.nonlocal_attn_grid_packed), the stock path materialises its H W x H W / 4 scores.
+Usage: python tools/ae_train_bench.py --config {BAIR,KTH,KITTI} [--steps 10] [--warmup 3] [--batch B] [--size H W] [--dp] [--repeats R]
+                                      [--paths hip,hip_gs,hip_dp]"""
 import argparse
 import copy
 import json
@@ -29,7 +32,7 @@ CONFIGS = {
 }
 
 
-def algorithmic_bytes(enc, dec, frames, S):
+def algorithmic_bytes(enc, dec, frames, H, W):
     """HBM bytes the new kernels must move per step at minimum (fp32): BatchNorm forward = stats read + apply read / write
     (+ residual read), backward = sum pass (x, g) + dx pass (x, g, dx); attention = q, k, v read + o written forward, q, k, v, o,
     dO read + dq, dk, dv written backward (the score matrix stays on chip).  The shapes come from a one-frame probe of COPIES in
@@ -45,11 +48,11 @@ def algorithmic_bytes(enc, dec, frames, S):
     att = []
 
     def at_hook(m, inp, out):
-        N, C, H, W = inp[0].shape
-        att.append(H * W * (2 * (C // 8) + C // 2 + C // 2))
+        N, C, h, w = inp[0].shape
+        att.append(h * w * (2 * (C // 8) + C // 2 + C // 2))
     hs += [m.register_forward_hook(at_hook) for m in enc.modules() if isinstance(m, NonLocalAttenion2D)]
     with torch.no_grad():
-        dec(enc(torch.zeros(1, 1, enc.block0[1].in_channels, S, S)))
+        dec(enc(torch.zeros(1, 1, enc.block0[1].in_channels, H, W)))
     for h in hs:
         h.remove()
     bn = 4 * frames * sum(n * (1 + 2) + n * 2 + n * 3 for n in counts)           # fwd 3 passes-worth, bwd 5 (residual not counted)
@@ -63,6 +66,8 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=None)
+    ap.add_argument("--size", type=int, nargs=2, default=None, metavar=("H", "W"),
+                    help="frame height and width, each a multiple of 2**n_downsampling (default: the config's own square size)")
     ap.add_argument("--paths", default=None, help="comma list of stock, hip, hip_gs, hip_dp (default: stock,hip; with --dp also hip_gs,hip_dp)")
     ap.add_argument("--one-context", action="store_true",
                     help="build every trainer on the process's default scheduling context instead of one context per path")
@@ -81,14 +86,18 @@ def main():
     if not torch.cuda.is_available():
         raise SystemExit("ae_train_bench needs an MI355X")
     cfg = CONFIGS[a.config]
-    B, T, S, ch = a.batch or cfg["B"], cfg["T"], cfg["S"], cfg["ch"]
+    B, T, ch = a.batch or cfg["B"], cfg["T"], cfg["ch"]
+    H, W = a.size or (cfg["S"], cfg["S"])
+    down = 2 ** cfg["AE"]["n_downsampling"]
+    if H < down or W < down or H % down or W % down:
+        raise SystemExit(f"--size: H and W must be multiples of 2**n_downsampling = {down}")
     dev = "cuda:0"
     enc0, dec0 = npvp_amd.build_autoencoder(cfg["AE"], ch)
     O.key_hashed_fill(npvp_amd.AEPair(enc0, dec0), 1)
-    x = torch.tanh(O.seeded_randn((B, T, ch, S, S), 2)).to(dev)
+    x = torch.tanh(O.seeded_randn((B, T, ch, H, W), 2)).to(dev)
     past, fut = x[:, : T // 2].contiguous(), x[:, T // 2:].contiguous()
-    out = {"config": a.config, "batch": B, "frames_per_step": B * T, "res": S}
-    out["bn_bytes_per_step"], out["attn_bytes_per_step"] = algorithmic_bytes(enc0, dec0, B * T, S)
+    out = {"config": a.config, "batch": B, "frames_per_step": B * T, "res": H if H == W else [H, W]}
+    out["bn_bytes_per_step"], out["attn_bytes_per_step"] = algorithmic_bytes(enc0, dec0, B * T, H, W)
     losses, steps = {}, {}
     for path in paths:
         enc, dec = copy.deepcopy(enc0), copy.deepcopy(dec0)
