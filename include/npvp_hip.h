@@ -528,8 +528,8 @@ int npvp_nonlocal_attn_bwd(const float* q, long long ldq, const float* k, long l
  * table; same argument lists, same tie rule, same lse, same D [2][F*H*W] scratch.  Pooled grid Hp = H/2, Wp = W/2 (floor, as
  * nn.MaxPool2d((2,2), stride=2)), Lk = Hp*Wp >= 1 keys; every query row attends.  Rows of an odd last line / column belong to no
  * window: their dk / dv are exactly 0, written by a kernel (no memset), so every element of dq / dk / dv is written exactly once.
- * A shape npvp_nonlocal_attn_fwd/bwd accept is passed on to them (the same launches, bit-identical results); every other shape
- * launches a general form of the same kernels - same tiles, thread maps and summation order, partial last query / key tiles masked
+ * A shape npvp_nonlocal_attn_fwd/bwd accept launches what they launch (the exact-tile form of the kernels, bit-identical results);
+ * every other shape the general form of the same kernels - same tiles, thread maps and summation order, partial last query / key tiles masked
  * (masked key: score -inf, P = 0; masked query: no store, no contribution to dk / dv).  Deterministic, no atomics, no workspace.
  * NPVP_NL_GRID_GENERAL=1 in the environment (read once) sends the config shapes to the general form too: a measurement aid. */
 int npvp_nonlocal_attn_grid_fwd(const float* q, long long ldq, const float* k, long long ldk, const float* v, long long ldv, float* o,

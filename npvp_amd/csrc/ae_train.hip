@@ -329,8 +329,9 @@ __global__ void __launch_bounds__(256) reflect_pad_bwd_kernel(const float* __res
 }
 
 // -------------------------------------------------------------------------------------------------------- non-local attention
-// q [F*HW][ldq] (cols 0..A-1), k / v: the UNPOOLED projections [F*HW][ldk] / [F*HW][ldv]; pooled key j = (ph, pw), ph = j >> wsh,
-// pw = j & (W/2 - 1): max over rows (2ph)W + 2pw + {0, 1, W, W+1} (that order breaks ties).  o [F*HW][ldo], lse [F*HW].
+// q [F*HW][ldq] (cols 0..A-1), k / v: the UNPOOLED projections [F*HW][ldk] / [F*HW][ldv]; pooled key j = (ph, pw) of the
+// Hp x Wp = H/2 x W/2 (floor) pooled grid: max over rows (2ph)W + 2pw + {0, 1, W, W+1} (that order breaks ties).  o [F*HW][ldo],
+// lse [F*HW].
 template <int A, int V>
 struct NL {
   static constexpr int QT = 4096 / V;             // queries per block (forward, dq)
@@ -341,10 +342,64 @@ struct NL {
   static constexpr int AP = A + 1;                // padded LDS rows
 };
 
-// pooled value and the arg-max (0..3, row-major window order, first maximum wins) of element col of pooled key `key`
-__device__ __forceinline__ float pool_load(const float* __restrict__ base, long long ld, int key, int wsh, int W, int col, int& am) {
-  const int ph = key >> wsh, pw = key & ((1 << wsh) - 1);
-  const long long r = (long long)(2 * ph) * W + 2 * pw;
+// The grid's geometry, the one thing the two forms of each kernel below differ in (same NL<A, V> tiles, same thread maps, same
+// order of every sum).  rows = F*H*W is the offset of the second half of D.
+//   NLGeo<true>, the AE configs' grids: H even, W a power of two, every tile divides HW and Lk = HW/4 exactly.  A key's window is
+//     decoded with a shift and a mask where it is used; no query, key or store is masked.
+//   NLGeo<false>, any H, W >= 2: the last query tile and the last key tile may be partial.
+//     - a query past the frame loads the frame's last row (valid memory, finite numbers), stores nothing, and enters dk / dv with P = 0;
+//     - a key past Lk has k = v = 0 in LDS, score -inf in the forward (P = exp(-inf - finite) = 0: tile 0 always holds key 0, so the
+//       running maximum is finite from the first tile on and no exp(-inf + inf) is formed) and P = 0 in the backward.
+//     Wr[j] is the first row of the window of the tile's key j, -1 past Lk: the one division per key is done once per tile, by one
+//     thread per key, not in the element loops.
+template <bool EXACT>
+struct NLGeo;
+
+template <>
+struct NLGeo<true> {
+  long long rows;
+  int HW, W, wsh;                                 // Wp = 1 << wsh
+  static NLGeo make(int F, int H, int W) {
+    int wsh = 0;
+    while ((1 << wsh) < W / 2) ++wsh;
+    return {(long long)F * H * W, H * W, W, wsh};
+  }
+  __device__ __forceinline__ int tiles(int n, int T) const { return n / T; }
+  __device__ __forceinline__ int keys() const { return HW >> 2; }
+  __device__ __forceinline__ int qrow(int i) const { return i; }
+  __device__ __forceinline__ bool qlive(int) const { return true; }
+  __device__ __forceinline__ void windows(int, int, int*) const {}
+  // first row of the window of key k0 + j
+  __device__ __forceinline__ long long window(const int*, int k0, int j) const {
+    const int key = k0 + j;
+    return (long long)(2 * (key >> wsh)) * W + 2 * (key & ((1 << wsh) - 1));
+  }
+  static __device__ __forceinline__ bool klive(long long) { return true; }
+};
+
+template <>
+struct NLGeo<false> {
+  long long rows;
+  int HW, W, Wp, Lk;
+  static NLGeo make(int F, int H, int W) { return {(long long)F * H * W, H * W, W, W / 2, (H / 2) * (W / 2)}; }
+  __device__ __forceinline__ int tiles(int n, int T) const { return (n + T - 1) / T; }
+  __device__ __forceinline__ int keys() const { return Lk; }
+  __device__ __forceinline__ int qrow(int i) const { return min(i, HW - 1); }
+  __device__ __forceinline__ bool qlive(int i) const { return i < HW; }
+  // fills Wr for the T keys from k0 on; the threads meet before the first read
+  __device__ __forceinline__ void windows(int k0, int T, int* Wr) const {
+    if ((int)threadIdx.x < T) {
+      const int key = k0 + threadIdx.x, ph = key / Wp;
+      Wr[threadIdx.x] = key < Lk ? 2 * ph * W + 2 * (key - ph * Wp) : -1;
+    }
+    __syncthreads();
+  }
+  __device__ __forceinline__ int window(const int* Wr, int, int j) const { return Wr[j]; }
+  static __device__ __forceinline__ bool klive(int r) { return r >= 0; }
+};
+
+// pooled value and the arg-max (0..3, row-major window order, first maximum wins) of element col of the window whose first row is r
+__device__ __forceinline__ float pool_at(const float* __restrict__ base, long long ld, long long r, int W, int col, int& am) {
   const float v0 = base[r * ld + col], v1 = base[(r + 1) * ld + col], v2 = base[(r + W) * ld + col], v3 = base[(r + W + 1) * ld + col];
   float m = v0; am = 0;
   if (v1 > m) { m = v1; am = 1; }
@@ -353,48 +408,58 @@ __device__ __forceinline__ float pool_load(const float* __restrict__ base, long 
   return m;
 }
 
-template <int A, int V, int KT>
-__device__ __forceinline__ void nl_load_kv(const float* __restrict__ kf, long long ldk, const float* __restrict__ vf, long long ldv,
-                                           int k0, int wsh, int W, float* Ks, float* Vs) {
+// pool_at, 0 (and arg-max 0) for a key past Lk
+template <class G, class R>
+__device__ __forceinline__ float pool_key(const G& g, const float* __restrict__ base, long long ld, R r, int col, int& am) {
+  am = 0;
+  return G::klive(r) ? pool_at(base, ld, r, g.W, col, am) : 0.f;
+}
+
+template <int A, int V, int KT, class G>
+__device__ __forceinline__ void nl_load_kv(const G& g, const float* __restrict__ kf, long long ldk, const float* __restrict__ vf,
+                                           long long ldv, int k0, const int* Wr, float* Ks, float* Vs) {
   constexpr int AP = A + 1;
   for (int e = threadIdx.x; e < KT * A; e += 256) {
     const int j = e / A, d = e % A;
     int am;
-    Ks[j * AP + d] = pool_load(kf, ldk, k0 + j, wsh, W, d, am);
+    Ks[j * AP + d] = pool_key(g, kf, ldk, g.window(Wr, k0, j), d, am);
   }
   for (int e = threadIdx.x; e < KT * V; e += 256) {
     const int j = e / V, c = e % V;
     int am;
-    Vs[j * V + c] = pool_load(vf, ldv, k0 + j, wsh, W, c, am);
+    Vs[j * V + c] = pool_key(g, vf, ldv, g.window(Wr, k0, j), c, am);
   }
 }
 
-// S[qi][j] = q_qi . k_j for the block's QT x KT tile; mode 1 stores exp(S - lse[qi]) instead
-template <int A, int QT, int KT>
-__device__ __forceinline__ void nl_scores(const float* Qs, const float* Ks, float* Ss, const float* Ls, int mode) {
+// S[qi][j] = q_qi . k_j for the block's QT x KT tile: mode 0 stores S (-inf at a key past Lk), mode 1 exp(S - lse[qi]) (0 there)
+template <int A, int QT, int KT, class G>
+__device__ __forceinline__ void nl_scores(const G& g, const float* Qs, const float* Ks, float* Ss, const float* Ls, const int* Wr,
+                                          int k0, int mode) {
   constexpr int AP = A + 1;
   for (int e = threadIdx.x; e < QT * KT; e += 256) {
     const int qi = e / KT, j = e % KT;
     float s = 0.f;
 #pragma unroll
     for (int d = 0; d < A; ++d) s = fmaf(Qs[qi * AP + d], Ks[j * AP + d], s);
-    Ss[qi * (KT + 1) + j] = mode ? expf(s - Ls[qi]) : s;
+    const bool live = G::klive(g.window(Wr, k0, j));
+    Ss[qi * (KT + 1) + j] = mode ? (live ? expf(s - Ls[qi]) : 0.f) : (live ? s : -INFINITY);
   }
 }
 
-template <int A, int V>
+template <int A, int V, bool EXACT>
 __global__ void __launch_bounds__(256) nl_attn_fwd_kernel(const float* __restrict__ q, long long ldq, const float* __restrict__ k,
                                                           long long ldk, const float* __restrict__ v, long long ldv,
-                                                          float* __restrict__ o, long long ldo, float* __restrict__ lse, int HW, int W,
-                                                          int wsh) {
+                                                          float* __restrict__ o, long long ldo, float* __restrict__ lse,
+                                                          const NLGeo<EXACT> g) {
   using C = NL<A, V>;
   constexpr int QT = C::QT, KT = C::KT, TPQ = C::TPQ, AP = C::AP;
   __shared__ float Qs[QT * AP], Ks[KT * AP], Vs[KT * V], Ss[QT * (KT + 1)];
-  const int tiles = HW / QT;
+  __shared__ int Wr[KT];
+  const int HW = g.HW, tiles = g.tiles(HW, QT);
   const int f = blockIdx.x / tiles, q0 = (blockIdx.x - f * tiles) * QT;
   const long long fb = (long long)f * HW;
-  const int Lk = HW >> 2;
-  for (int e = threadIdx.x; e < QT * A; e += 256) Qs[(e / A) * AP + e % A] = q[(fb + q0 + e / A) * ldq + e % A];
+  const int Lk = g.keys();
+  for (int e = threadIdx.x; e < QT * A; e += 256) Qs[(e / A) * AP + e % A] = q[(fb + g.qrow(q0 + e / A)) * ldq + e % A];
   const int qi = threadIdx.x / TPQ, j0 = threadIdx.x % TPQ;
   float acc[16];
 #pragma unroll
@@ -402,9 +467,10 @@ __global__ void __launch_bounds__(256) nl_attn_fwd_kernel(const float* __restric
   float mrun = -INFINITY, l = 0.f;
   for (int k0 = 0; k0 < Lk; k0 += KT) {
     __syncthreads();
-    nl_load_kv<A, V, KT>(k + fb * ldk, ldk, v + fb * ldv, ldv, k0, wsh, W, Ks, Vs);
+    g.windows(k0, KT, Wr);
+    nl_load_kv<A, V, KT>(g, k + fb * ldk, ldk, v + fb * ldv, ldv, k0, Wr, Ks, Vs);
     __syncthreads();
-    nl_scores<A, QT, KT>(Qs, Ks, Ss, nullptr, 0);
+    nl_scores<A, QT, KT>(g, Qs, Ks, Ss, nullptr, Wr, k0, 0);
     __syncthreads();
     const float* srow = Ss + qi * (KT + 1);
     float mx = mrun;
@@ -421,6 +487,7 @@ __global__ void __launch_bounds__(256) nl_attn_fwd_kernel(const float* __restric
     }
     mrun = mx;
   }
+  if (!g.qlive(q0 + qi)) return;
   const float inv = 1.f / l;
   const long long row = fb + q0 + qi;
 #pragma unroll
@@ -441,38 +508,41 @@ __device__ __forceinline__ float group_sum(float s) {
 // and so does an error in D taken from the rounded forward output: neither averages out over the keys, and dq, a sum whose terms
 // cancel, showed them (2.1e-5 - 2.5e-5 rel-L2 against float64 over 1024 keys, measured).  So a first sweep over the keys sums
 // sum_j P_ij and sum_j P_ij dP_ij in double, and both backward kernels use Phat = P r, whose row sums to 1.
-template <int A, int V>
+template <int A, int V, bool EXACT>
 __global__ void __launch_bounds__(256) nl_attn_dq_kernel(const float* __restrict__ q, long long ldq, const float* __restrict__ k,
                                                          long long ldk, const float* __restrict__ v, long long ldv,
                                                          const float* __restrict__ go,
                                                          long long ldgo, const float* __restrict__ lse, float* __restrict__ Dout,
-                                                         float* __restrict__ dq, long long lddq, int HW, int W, int wsh) {
+                                                         float* __restrict__ dq, long long lddq, const NLGeo<EXACT> g) {
   using C = NL<A, V>;
   constexpr int QT = C::QT, KT = C::KT, TPQ = C::TPQ, AP = C::AP;
   constexpr int NQ = QT * A / 256;      // dq accumulators per thread (4 at every supported shape: QT A = 1024)
   __shared__ float Qs[QT * AP], Ks[KT * AP], Vs[KT * V], Ss[QT * (KT + 1)], Ls[QT];
-  const int tiles = HW / QT;
+  __shared__ int Wr[KT];
+  const int HW = g.HW, tiles = g.tiles(HW, QT);
   const int f = blockIdx.x / tiles, q0 = (blockIdx.x - f * tiles) * QT;
   const long long fb = (long long)f * HW;
-  const int Lk = HW >> 2;
-  for (int e = threadIdx.x; e < QT * A; e += 256) Qs[(e / A) * AP + e % A] = q[(fb + q0 + e / A) * ldq + e % A];
+  const int Lk = g.keys();
+  for (int e = threadIdx.x; e < QT * A; e += 256) Qs[(e / A) * AP + e % A] = q[(fb + g.qrow(q0 + e / A)) * ldq + e % A];
   const int qi = threadIdx.x / TPQ, j0 = threadIdx.x % TPQ;
-  const long long row = fb + q0 + qi;
-  float g[16];
+  const bool live = g.qlive(q0 + qi);
+  const long long row = fb + g.qrow(q0 + qi);
+  float gr[16];
 #pragma unroll
-  for (int i = 0; i < 16; ++i) g[i] = go[row * ldgo + j0 + TPQ * i];
+  for (int i = 0; i < 16; ++i) gr[i] = go[row * ldgo + j0 + TPQ * i];
   if (j0 == 0) Ls[qi] = lse[row];
   double dacc = 0.0, pacc = 0.0;
   for (int k0 = 0; k0 < Lk; k0 += KT) {
     __syncthreads();
-    nl_load_kv<A, V, KT>(k + fb * ldk, ldk, v + fb * ldv, ldv, k0, wsh, W, Ks, Vs);
+    g.windows(k0, KT, Wr);
+    nl_load_kv<A, V, KT>(g, k + fb * ldk, ldk, v + fb * ldv, ldv, k0, Wr, Ks, Vs);
     __syncthreads();
-    nl_scores<A, QT, KT>(Qs, Ks, Ss, Ls, 1);                 // P
+    nl_scores<A, QT, KT>(g, Qs, Ks, Ss, Ls, Wr, k0, 1);      // P
     __syncthreads();
     for (int j = 0; j < KT; ++j) {
       float dp = 0.f;
 #pragma unroll
-      for (int i = 0; i < 16; ++i) dp = fmaf(g[i], Vs[j * V + j0 + TPQ * i], dp);
+      for (int i = 0; i < 16; ++i) dp = fmaf(gr[i], Vs[j * V + j0 + TPQ * i], dp);
       dp = group_sum<TPQ>(dp);
       const double p = (double)Ss[qi * (KT + 1) + j];
       dacc += p * (double)dp;
@@ -480,20 +550,21 @@ __global__ void __launch_bounds__(256) nl_attn_dq_kernel(const float* __restrict
     }
   }
   const float dsum = (float)(dacc / pacc), rinv = (float)(1.0 / pacc);
-  if (j0 == 0) { Dout[row] = dsum; Dout[(long long)gridDim.x * QT + row] = rinv; }
+  if (j0 == 0 && live) { Dout[row] = dsum; Dout[g.rows + row] = rinv; }
   float acc[NQ];
 #pragma unroll
   for (int m = 0; m < NQ; ++m) acc[m] = 0.f;
   for (int k0 = 0; k0 < Lk; k0 += KT) {
     __syncthreads();
-    nl_load_kv<A, V, KT>(k + fb * ldk, ldk, v + fb * ldv, ldv, k0, wsh, W, Ks, Vs);
+    g.windows(k0, KT, Wr);
+    nl_load_kv<A, V, KT>(g, k + fb * ldk, ldk, v + fb * ldv, ldv, k0, Wr, Ks, Vs);
     __syncthreads();
-    nl_scores<A, QT, KT>(Qs, Ks, Ss, Ls, 1);                 // P
+    nl_scores<A, QT, KT>(g, Qs, Ks, Ss, Ls, Wr, k0, 1);      // P
     __syncthreads();
     for (int j = 0; j < KT; ++j) {
       float dp = 0.f;
 #pragma unroll
-      for (int i = 0; i < 16; ++i) dp = fmaf(g[i], Vs[j * V + j0 + TPQ * i], dp);
+      for (int i = 0; i < 16; ++i) dp = fmaf(gr[i], Vs[j * V + j0 + TPQ * i], dp);
       dp = group_sum<TPQ>(dp);
       if (j0 == 0) { float* s = Ss + qi * (KT + 1) + j; *s = (*s * rinv) * (dp - dsum); }       // dS = Phat (dP - D)
     }
@@ -509,324 +580,47 @@ __global__ void __launch_bounds__(256) nl_attn_dq_kernel(const float* __restrict
 #pragma unroll
   for (int m = 0; m < NQ; ++m) {
     const int e = threadIdx.x + 256 * m, qq = e / A, d = e % A;
-    dq[(fb + q0 + qq) * lddq + d] = acc[m];
+    if (g.qlive(q0 + qq)) dq[(fb + q0 + qq) * lddq + d] = acc[m];
   }
 }
 
-// dk, dv of KB pooled keys, routed to the arg-max of each window (the other three window positions get 0: every element of the
-// unpooled gradient is written exactly once)
-template <int A, int V>
+// one value's gradient to the arg-max of its window (first row r), 0 to the other three positions
+__device__ __forceinline__ void unpool_store(float* __restrict__ base, long long ld, long long r, int W, int col, int am, float val) {
+  base[r * ld + col] = am == 0 ? val : 0.f;
+  base[(r + 1) * ld + col] = am == 1 ? val : 0.f;
+  base[(r + W) * ld + col] = am == 2 ? val : 0.f;
+  base[(r + W + 1) * ld + col] = am == 3 ? val : 0.f;
+}
+
+// dk, dv of KB pooled keys, routed to the arg-max of each window (the other three window positions get 0: with the edge kernel
+// below every element of the unpooled gradient is written exactly once)
+template <int A, int V, bool EXACT>
 __global__ void __launch_bounds__(256) nl_attn_dkv_kernel(const float* __restrict__ q, long long ldq, const float* __restrict__ k,
                                                           long long ldk, const float* __restrict__ v, long long ldv,
                                                           const float* __restrict__ go, long long ldgo, const float* __restrict__ lse,
                                                           const float* __restrict__ Din, float* __restrict__ dk, long long lddk,
-                                                          float* __restrict__ dv, long long lddv, int F, int HW, int W, int wsh) {
+                                                          float* __restrict__ dv, long long lddv, const NLGeo<EXACT> g) {
   using C = NL<A, V>;
   constexpr int KB = C::KB, QB = C::QB, TPQ = C::TPQ, AP = C::AP;
   constexpr int NK = KB * A / 256;      // dk accumulators per thread (4 at every supported shape: KB A = 1024)
   __shared__ float Ks[KB * AP], Qs[QB * AP], Gs[QB * V], Ps[KB * (QB + 1)], Es[KB * (QB + 1)], Ls[QB], Ds[QB], Rs[QB];
   __shared__ unsigned char Kam[KB * A], Vam[KB * V];
-  const int Lk = HW >> 2;
-  const int tiles = Lk / KB;
-  const int f = blockIdx.x / tiles, kb0 = (blockIdx.x - f * tiles) * KB;
-  const long long fb = (long long)f * HW;
-  for (int e = threadIdx.x; e < KB * A; e += 256) {
-    int am;
-    Ks[(e / A) * AP + e % A] = pool_load(k + fb * ldk, ldk, kb0 + e / A, wsh, W, e % A, am);
-    Kam[e] = (unsigned char)am;
-  }
-  const int jr = threadIdx.x / TPQ, j0 = threadIdx.x % TPQ;
-  float vr[16], dvr[16];
-#pragma unroll
-  for (int i = 0; i < 16; ++i) {
-    int am;
-    vr[i] = pool_load(v + fb * ldv, ldv, kb0 + jr, wsh, W, j0 + TPQ * i, am);
-    Vam[jr * V + j0 + TPQ * i] = (unsigned char)am;
-    dvr[i] = 0.f;
-  }
-  float dkr[NK];
-#pragma unroll
-  for (int m = 0; m < NK; ++m) dkr[m] = 0.f;
-  for (int q0 = 0; q0 < HW; q0 += QB) {
-    __syncthreads();
-    for (int e = threadIdx.x; e < QB * A; e += 256) Qs[(e / A) * AP + e % A] = q[(fb + q0 + e / A) * ldq + e % A];
-    for (int e = threadIdx.x; e < QB * V; e += 256) Gs[e] = go[(fb + q0 + e / V) * ldgo + e % V];
-    if (threadIdx.x < QB) {
-      const long long rw = fb + q0 + threadIdx.x;
-      Ls[threadIdx.x] = lse[rw]; Ds[threadIdx.x] = Din[rw]; Rs[threadIdx.x] = Din[(long long)F * HW + rw];
-    }
-    __syncthreads();
-    for (int e = threadIdx.x; e < KB * QB; e += 256) {
-      const int jj = e / QB, qi = e % QB;
-      float s = 0.f;
-#pragma unroll
-      for (int d = 0; d < A; ++d) s = fmaf(Qs[qi * AP + d], Ks[jj * AP + d], s);
-      Ps[jj * (QB + 1) + qi] = expf(s - Ls[qi]) * Rs[qi];
-    }
-    __syncthreads();
-    for (int qi = 0; qi < QB; ++qi) {
-      const float p = Ps[jr * (QB + 1) + qi];
-      float dp = 0.f;
-#pragma unroll
-      for (int i = 0; i < 16; ++i) {
-        const float gg = Gs[qi * V + j0 + TPQ * i];
-        dp = fmaf(gg, vr[i], dp);
-        dvr[i] = fmaf(p, gg, dvr[i]);
-      }
-      dp = group_sum<TPQ>(dp);
-      if (j0 == 0) Es[jr * (QB + 1) + qi] = p * (dp - Ds[qi]);
-    }
-    __syncthreads();
-#pragma unroll
-    for (int m = 0; m < NK; ++m) {
-      const int e = threadIdx.x + 256 * m, jj = e / A, d = e % A;
-      float s = dkr[m];
-      for (int qi = 0; qi < QB; ++qi) s = fmaf(Es[jj * (QB + 1) + qi], Qs[qi * AP + d], s);
-      dkr[m] = s;
-    }
-  }
-  __syncthreads();
-  const int mask = (1 << wsh) - 1;
-#pragma unroll
-  for (int i = 0; i < 16; ++i) {
-    const int c = j0 + TPQ * i, key = kb0 + jr;
-    const int am = Vam[jr * V + c];
-    const long long r = fb + (long long)(2 * (key >> wsh)) * W + 2 * (key & mask);
-    dv[r * lddv + c] = am == 0 ? dvr[i] : 0.f;
-    dv[(r + 1) * lddv + c] = am == 1 ? dvr[i] : 0.f;
-    dv[(r + W) * lddv + c] = am == 2 ? dvr[i] : 0.f;
-    dv[(r + W + 1) * lddv + c] = am == 3 ? dvr[i] : 0.f;
-  }
-#pragma unroll
-  for (int m = 0; m < NK; ++m) {
-    const int e = threadIdx.x + 256 * m, jj = e / A, d = e % A, key = kb0 + jj;
-    const int am = Kam[e];
-    const long long r = fb + (long long)(2 * (key >> wsh)) * W + 2 * (key & mask);
-    dk[r * lddk + d] = am == 0 ? dkr[m] : 0.f;
-    dk[(r + 1) * lddk + d] = am == 1 ? dkr[m] : 0.f;
-    dk[(r + W) * lddk + d] = am == 2 ? dkr[m] : 0.f;
-    dk[(r + W + 1) * lddk + d] = am == 3 ? dkr[m] : 0.f;
-  }
-}
-
-// ------------------------------------------------------------------------------------- non-local attention on any H x W grid
-// The general form of the three kernels above (same NL<A, V> tiles, same thread maps, same order of every sum): Hp = H/2, Wp = W/2
-// (floor), Lk = Hp Wp pooled keys.  The last query tile and the last key tile may be partial:
-//   - a query past the frame loads the frame's last row (valid memory, finite numbers), stores nothing, and enters dk / dv with P = 0;
-//   - a key past Lk has k = v = 0 in LDS, score -inf in the forward (P = exp(-inf - finite) = 0: tile 0 always holds key 0, so the
-//     running maximum is finite from the first tile on and no exp(-inf + inf) is formed) and P = 0 in the backward.
-// Wr[j] is the first row (2 ph) W + 2 pw of key j's window, -1 past Lk: the one division per key is done once per tile, by one
-// thread per key, not in the element loops.
-
-// the pooled value of pool_load for a window whose first row is r
-__device__ __forceinline__ float pool_at(const float* __restrict__ base, long long ld, int r0, int W, int col, int& am) {
-  const long long r = r0;
-  const float v0 = base[r * ld + col], v1 = base[(r + 1) * ld + col], v2 = base[(r + W) * ld + col], v3 = base[(r + W + 1) * ld + col];
-  float m = v0; am = 0;
-  if (v1 > m) { m = v1; am = 1; }
-  if (v2 > m) { m = v2; am = 2; }
-  if (v3 > m) { m = v3; am = 3; }
-  return m;
-}
-
-// caller syncs before the first read of Wr
-template <int KT>
-__device__ __forceinline__ void nlg_windows(int k0, int Lk, int Wp, int W, int* Wr) {
-  if (threadIdx.x < KT) {
-    const int key = k0 + threadIdx.x, ph = key / Wp;
-    Wr[threadIdx.x] = key < Lk ? 2 * ph * W + 2 * (key - ph * Wp) : -1;
-  }
-}
-
-template <int A, int V, int KT>
-__device__ __forceinline__ void nlg_load_kv(const float* __restrict__ kf, long long ldk, const float* __restrict__ vf, long long ldv,
-                                            const int* Wr, int W, float* Ks, float* Vs) {
-  constexpr int AP = A + 1;
-  for (int e = threadIdx.x; e < KT * A; e += 256) {
-    const int j = e / A, d = e % A, r = Wr[j];
-    int am;
-    Ks[j * AP + d] = r >= 0 ? pool_at(kf, ldk, r, W, d, am) : 0.f;
-  }
-  for (int e = threadIdx.x; e < KT * V; e += 256) {
-    const int j = e / V, c = e % V, r = Wr[j];
-    int am;
-    Vs[j * V + c] = r >= 0 ? pool_at(vf, ldv, r, W, c, am) : 0.f;
-  }
-}
-
-// nl_scores with the key mask: mode 0 stores S (-inf at a masked key), mode 1 exp(S - lse[qi]) (0 at a masked key)
-template <int A, int QT, int KT>
-__device__ __forceinline__ void nlg_scores(const float* Qs, const float* Ks, float* Ss, const float* Ls, const int* Wr, int mode) {
-  constexpr int AP = A + 1;
-  for (int e = threadIdx.x; e < QT * KT; e += 256) {
-    const int qi = e / KT, j = e % KT;
-    float s = 0.f;
-#pragma unroll
-    for (int d = 0; d < A; ++d) s = fmaf(Qs[qi * AP + d], Ks[j * AP + d], s);
-    const bool live = Wr[j] >= 0;
-    Ss[qi * (KT + 1) + j] = mode ? (live ? expf(s - Ls[qi]) : 0.f) : (live ? s : -INFINITY);
-  }
-}
-
-template <int A, int V>
-__global__ void __launch_bounds__(256) nlg_attn_fwd_kernel(const float* __restrict__ q, long long ldq, const float* __restrict__ k,
-                                                           long long ldk, const float* __restrict__ v, long long ldv,
-                                                           float* __restrict__ o, long long ldo, float* __restrict__ lse, int HW, int W,
-                                                           int Wp, int Lk) {
-  using C = NL<A, V>;
-  constexpr int QT = C::QT, KT = C::KT, TPQ = C::TPQ, AP = C::AP;
-  __shared__ float Qs[QT * AP], Ks[KT * AP], Vs[KT * V], Ss[QT * (KT + 1)];
-  __shared__ int Wr[KT];
-  const int tiles = (HW + QT - 1) / QT;
-  const int f = blockIdx.x / tiles, q0 = (blockIdx.x - f * tiles) * QT;
-  const long long fb = (long long)f * HW;
-  for (int e = threadIdx.x; e < QT * A; e += 256) Qs[(e / A) * AP + e % A] = q[(fb + min(q0 + e / A, HW - 1)) * ldq + e % A];
-  const int qi = threadIdx.x / TPQ, j0 = threadIdx.x % TPQ;
-  float acc[16];
-#pragma unroll
-  for (int i = 0; i < 16; ++i) acc[i] = 0.f;
-  float mrun = -INFINITY, l = 0.f;
-  for (int k0 = 0; k0 < Lk; k0 += KT) {
-    __syncthreads();
-    nlg_windows<KT>(k0, Lk, Wp, W, Wr);
-    __syncthreads();
-    nlg_load_kv<A, V, KT>(k + fb * ldk, ldk, v + fb * ldv, ldv, Wr, W, Ks, Vs);
-    __syncthreads();
-    nlg_scores<A, QT, KT>(Qs, Ks, Ss, nullptr, Wr, 0);
-    __syncthreads();
-    const float* srow = Ss + qi * (KT + 1);
-    float mx = mrun;
-    for (int j = 0; j < KT; ++j) mx = fmaxf(mx, srow[j]);
-    const float corr = expf(mrun - mx);
-    l *= corr;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) acc[i] *= corr;
-    for (int j = 0; j < KT; ++j) {
-      const float p = expf(srow[j] - mx);
-      l += p;
-#pragma unroll
-      for (int i = 0; i < 16; ++i) acc[i] = fmaf(p, Vs[j * V + j0 + TPQ * i], acc[i]);
-    }
-    mrun = mx;
-  }
-  if (q0 + qi >= HW) return;
-  const float inv = 1.f / l;
-  const long long row = fb + q0 + qi;
-#pragma unroll
-  for (int i = 0; i < 16; ++i) o[row * ldo + j0 + TPQ * i] = acc[i] * inv;
-  if (j0 == 0) lse[row] = mrun + logf(l);
-}
-
-// rows: F*H*W, the offset of the second half of D
-template <int A, int V>
-__global__ void __launch_bounds__(256) nlg_attn_dq_kernel(const float* __restrict__ q, long long ldq, const float* __restrict__ k,
-                                                          long long ldk, const float* __restrict__ v, long long ldv,
-                                                          const float* __restrict__ go,
-                                                          long long ldgo, const float* __restrict__ lse, float* __restrict__ Dout,
-                                                          float* __restrict__ dq, long long lddq, long long rows, int HW, int W, int Wp,
-                                                          int Lk) {
-  using C = NL<A, V>;
-  constexpr int QT = C::QT, KT = C::KT, TPQ = C::TPQ, AP = C::AP;
-  constexpr int NQ = QT * A / 256;
-  __shared__ float Qs[QT * AP], Ks[KT * AP], Vs[KT * V], Ss[QT * (KT + 1)], Ls[QT];
-  __shared__ int Wr[KT];
-  const int tiles = (HW + QT - 1) / QT;
-  const int f = blockIdx.x / tiles, q0 = (blockIdx.x - f * tiles) * QT;
-  const long long fb = (long long)f * HW;
-  for (int e = threadIdx.x; e < QT * A; e += 256) Qs[(e / A) * AP + e % A] = q[(fb + min(q0 + e / A, HW - 1)) * ldq + e % A];
-  const int qi = threadIdx.x / TPQ, j0 = threadIdx.x % TPQ;
-  const bool live = q0 + qi < HW;
-  const long long row = fb + min(q0 + qi, HW - 1);
-  float g[16];
-#pragma unroll
-  for (int i = 0; i < 16; ++i) g[i] = go[row * ldgo + j0 + TPQ * i];
-  if (j0 == 0) Ls[qi] = lse[row];
-  double dacc = 0.0, pacc = 0.0;
-  for (int k0 = 0; k0 < Lk; k0 += KT) {
-    __syncthreads();
-    nlg_windows<KT>(k0, Lk, Wp, W, Wr);
-    __syncthreads();
-    nlg_load_kv<A, V, KT>(k + fb * ldk, ldk, v + fb * ldv, ldv, Wr, W, Ks, Vs);
-    __syncthreads();
-    nlg_scores<A, QT, KT>(Qs, Ks, Ss, Ls, Wr, 1);            // P
-    __syncthreads();
-    for (int j = 0; j < KT; ++j) {
-      float dp = 0.f;
-#pragma unroll
-      for (int i = 0; i < 16; ++i) dp = fmaf(g[i], Vs[j * V + j0 + TPQ * i], dp);
-      dp = group_sum<TPQ>(dp);
-      const double p = (double)Ss[qi * (KT + 1) + j];
-      dacc += p * (double)dp;
-      pacc += p;
-    }
-  }
-  const float dsum = (float)(dacc / pacc), rinv = (float)(1.0 / pacc);
-  if (j0 == 0 && live) { Dout[row] = dsum; Dout[rows + row] = rinv; }
-  float acc[NQ];
-#pragma unroll
-  for (int m = 0; m < NQ; ++m) acc[m] = 0.f;
-  for (int k0 = 0; k0 < Lk; k0 += KT) {
-    __syncthreads();
-    nlg_windows<KT>(k0, Lk, Wp, W, Wr);
-    __syncthreads();
-    nlg_load_kv<A, V, KT>(k + fb * ldk, ldk, v + fb * ldv, ldv, Wr, W, Ks, Vs);
-    __syncthreads();
-    nlg_scores<A, QT, KT>(Qs, Ks, Ss, Ls, Wr, 1);            // P
-    __syncthreads();
-    for (int j = 0; j < KT; ++j) {
-      float dp = 0.f;
-#pragma unroll
-      for (int i = 0; i < 16; ++i) dp = fmaf(g[i], Vs[j * V + j0 + TPQ * i], dp);
-      dp = group_sum<TPQ>(dp);
-      if (j0 == 0) { float* s = Ss + qi * (KT + 1) + j; *s = (*s * rinv) * (dp - dsum); }       // dS = Phat (dP - D)
-    }
-    __syncthreads();
-#pragma unroll
-    for (int m = 0; m < NQ; ++m) {
-      const int e = threadIdx.x + 256 * m, qq = e / A, d = e % A;
-      float s = acc[m];
-      for (int j = 0; j < KT; ++j) s = fmaf(Ss[qq * (KT + 1) + j], Ks[j * AP + d], s);
-      acc[m] = s;
-    }
-  }
-#pragma unroll
-  for (int m = 0; m < NQ; ++m) {
-    const int e = threadIdx.x + 256 * m, qq = e / A, d = e % A;
-    if (q0 + qq < HW) dq[(fb + q0 + qq) * lddq + d] = acc[m];
-  }
-}
-
-template <int A, int V>
-__global__ void __launch_bounds__(256) nlg_attn_dkv_kernel(const float* __restrict__ q, long long ldq, const float* __restrict__ k,
-                                                           long long ldk, const float* __restrict__ v, long long ldv,
-                                                           const float* __restrict__ go, long long ldgo, const float* __restrict__ lse,
-                                                           const float* __restrict__ Din, float* __restrict__ dk, long long lddk,
-                                                           float* __restrict__ dv, long long lddv, long long rows, int HW, int W, int Wp,
-                                                           int Lk) {
-  using C = NL<A, V>;
-  constexpr int KB = C::KB, QB = C::QB, TPQ = C::TPQ, AP = C::AP;
-  constexpr int NK = KB * A / 256;
-  __shared__ float Ks[KB * AP], Qs[QB * AP], Gs[QB * V], Ps[KB * (QB + 1)], Es[KB * (QB + 1)], Ls[QB], Ds[QB], Rs[QB];
-  __shared__ unsigned char Kam[KB * A], Vam[KB * V];
   __shared__ int Wr[KB];
-  const int tiles = (Lk + KB - 1) / KB;
+  const int HW = g.HW, W = g.W, tiles = g.tiles(g.keys(), KB);
   const int f = blockIdx.x / tiles, kb0 = (blockIdx.x - f * tiles) * KB;
   const long long fb = (long long)f * HW;
-  nlg_windows<KB>(kb0, Lk, Wp, W, Wr);
-  __syncthreads();
+  g.windows(kb0, KB, Wr);
   for (int e = threadIdx.x; e < KB * A; e += 256) {
-    const int r = Wr[e / A];
-    int am = 0;
-    Ks[(e / A) * AP + e % A] = r >= 0 ? pool_at(k + fb * ldk, ldk, r, W, e % A, am) : 0.f;
+    int am;
+    Ks[(e / A) * AP + e % A] = pool_key(g, k + fb * ldk, ldk, g.window(Wr, kb0, e / A), e % A, am);
     Kam[e] = (unsigned char)am;
   }
   const int jr = threadIdx.x / TPQ, j0 = threadIdx.x % TPQ;
-  const int wr = Wr[jr];
   float vr[16], dvr[16];
 #pragma unroll
   for (int i = 0; i < 16; ++i) {
-    int am = 0;
-    vr[i] = wr >= 0 ? pool_at(v + fb * ldv, ldv, wr, W, j0 + TPQ * i, am) : 0.f;
+    int am;
+    vr[i] = pool_key(g, v + fb * ldv, ldv, g.window(Wr, kb0, jr), j0 + TPQ * i, am);
     Vam[jr * V + j0 + TPQ * i] = (unsigned char)am;
     dvr[i] = 0.f;
   }
@@ -835,12 +629,12 @@ __global__ void __launch_bounds__(256) nlg_attn_dkv_kernel(const float* __restri
   for (int m = 0; m < NK; ++m) dkr[m] = 0.f;
   for (int q0 = 0; q0 < HW; q0 += QB) {
     __syncthreads();
-    for (int e = threadIdx.x; e < QB * A; e += 256) Qs[(e / A) * AP + e % A] = q[(fb + min(q0 + e / A, HW - 1)) * ldq + e % A];
-    for (int e = threadIdx.x; e < QB * V; e += 256) Gs[e] = go[(fb + min(q0 + e / V, HW - 1)) * ldgo + e % V];
+    for (int e = threadIdx.x; e < QB * A; e += 256) Qs[(e / A) * AP + e % A] = q[(fb + g.qrow(q0 + e / A)) * ldq + e % A];
+    for (int e = threadIdx.x; e < QB * V; e += 256) Gs[e] = go[(fb + g.qrow(q0 + e / V)) * ldgo + e % V];
     if (threadIdx.x < QB) {
-      const long long rw = fb + min(q0 + (int)threadIdx.x, HW - 1);
+      const long long rw = fb + g.qrow(q0 + (int)threadIdx.x);
       Ls[threadIdx.x] = lse[rw]; Ds[threadIdx.x] = Din[rw];
-      Rs[threadIdx.x] = q0 + (int)threadIdx.x < HW ? Din[rows + rw] : 0.f;     // r = 0: a query past the frame has Phat = 0
+      Rs[threadIdx.x] = g.qlive(q0 + (int)threadIdx.x) ? Din[g.rows + rw] : 0.f;      // r = 0: a query past the frame has Phat = 0
     }
     __syncthreads();
     for (int e = threadIdx.x; e < KB * QB; e += 256) {
@@ -873,29 +667,19 @@ __global__ void __launch_bounds__(256) nlg_attn_dkv_kernel(const float* __restri
     }
   }
   __syncthreads();
-  if (wr >= 0) {
+  const auto wv = g.window(Wr, kb0, jr);
+  if (g.klive(wv)) {
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
       const int c = j0 + TPQ * i;
-      const int am = Vam[jr * V + c];
-      const long long r = fb + wr;
-      dv[r * lddv + c] = am == 0 ? dvr[i] : 0.f;
-      dv[(r + 1) * lddv + c] = am == 1 ? dvr[i] : 0.f;
-      dv[(r + W) * lddv + c] = am == 2 ? dvr[i] : 0.f;
-      dv[(r + W + 1) * lddv + c] = am == 3 ? dvr[i] : 0.f;
+      unpool_store(dv, lddv, fb + wv, W, c, Vam[jr * V + c], dvr[i]);
     }
   }
 #pragma unroll
   for (int m = 0; m < NK; ++m) {
     const int e = threadIdx.x + 256 * m, jj = e / A, d = e % A;
-    const int w0 = Wr[jj];
-    if (w0 < 0) continue;
-    const int am = Kam[e];
-    const long long r = fb + w0;
-    dk[r * lddk + d] = am == 0 ? dkr[m] : 0.f;
-    dk[(r + 1) * lddk + d] = am == 1 ? dkr[m] : 0.f;
-    dk[(r + W) * lddk + d] = am == 2 ? dkr[m] : 0.f;
-    dk[(r + W + 1) * lddk + d] = am == 3 ? dkr[m] : 0.f;
+    const auto wk = g.window(Wr, kb0, jj);
+    if (g.klive(wk)) unpool_store(dk, lddk, fb + wk, W, d, Kam[e], dkr[m]);
   }
 }
 
@@ -1086,123 +870,110 @@ extern "C" int npvp_reflect_pad(const float* x, float* y, int planes, int H, int
   return NPVP_OK;
 }
 
-static int nl_check(int F, int H, int W, int A, int V, int& wsh) {
-  NPVP_CHECK_ARG(F > 0 && H >= 2 && W >= 2 && H % 2 == 0 && (W & (W - 1)) == 0, "nonlocal_attn: H even, W a power of two");
-  wsh = 0;
-  while ((1 << wsh) < W / 2) ++wsh;
-  const int HW = H * W;
-  const bool shape = (A == 8 && V == 32) || (A == 16 && V == 64) || (A == 32 && V == 128) || (A == 64 && V == 256);
-  NPVP_CHECK_ARG(shape, "nonlocal_attn: (attn dim, value dim) must be (8,32), (16,64), (32,128) or (64,256): C = 64..512 of the AE configs");
-  // the (C, grid) pairs of the five AE configs: 64x64 @ C=64, 32x32 @ 128, 16x16 @ 256, 8x8 @ 512 (the tiles below divide exactly)
-  NPVP_CHECK_ARG(HW == (A == 8 ? 4096 : A == 16 ? 1024 : A == 32 ? 256 : 64),
-                 "nonlocal_attn: grid not supported (the AE configs' grids: 64x64 @ C=64, 32x32 @ 128, 16x16 @ 256, 8x8 @ 512)");
-  NPVP_CHECK_ARG((long long)F * HW < (1ll << 31), "nonlocal_attn: too many rows");
+// ---- non-local attention.  npvp_nonlocal_attn_* take the AE configs' (C, grid) pairs only and launch the exact-tile kernels;
+// npvp_nonlocal_attn_grid_* take any H, W >= 2: a config shape launches what npvp_nonlocal_attn_* launch (the same bits), every other
+// shape the general kernels.  NPVP_NL_GRID_GENERAL=1 sends the config shapes of the grid entry points to the general kernels too
+// (measurements: what the masks cost at a shape both forms can run).
+static int nl_fail(bool grid, const char* pass, const char* what) {
+  char msg[256];
+  snprintf(msg, sizeof(msg), "nonlocal_attn%s%s: %s", grid ? "_grid" : "", pass, what);
+  npvp_set_error(msg);
+  return NPVP_ERR_ARG;
+}
+#define NL_REQUIRE(cond, pass, what) do { if (!(cond)) return nl_fail(grid, pass, what); } while (0)
+
+// the (C, grid) pairs of the five AE configs: 64x64 @ C=64, 32x32 @ 128, 16x16 @ 256, 8x8 @ 512, or any H x W of as many cells with
+// H even and W a power of two (the tiles of NL<A, V> divide exactly, a key's window decodes with a shift and a mask)
+static bool nl_config_shape(int H, int W, int A) {
+  return H % 2 == 0 && (W & (W - 1)) == 0 && (long long)H * W == (A == 8 ? 4096 : A == 16 ? 1024 : A == 32 ? 256 : 64);
+}
+
+static bool nl_force_general() {
+  static const bool on = [] { const char* e = getenv("NPVP_NL_GRID_GENERAL"); return e && e[0] == '1'; }();
+  return on;
+}
+
+static int nl_check(bool grid, int F, int H, int W, int A, int V) {
+  NL_REQUIRE(F > 0 && H >= 2 && W >= 2, "", grid ? "F >= 1, H >= 2, W >= 2" : "H even, W a power of two");
+  NL_REQUIRE(grid || (H % 2 == 0 && (W & (W - 1)) == 0), "", "H even, W a power of two");
+  NL_REQUIRE((A == 8 && V == 32) || (A == 16 && V == 64) || (A == 32 && V == 128) || (A == 64 && V == 256), "",
+             "(attn dim, value dim) must be (8,32), (16,64), (32,128) or (64,256): C = 64..512 of the AE configs");
+  NL_REQUIRE(grid || nl_config_shape(H, W, A), "",
+             "grid not supported (the AE configs' grids: 64x64 @ C=64, 32x32 @ 128, 16x16 @ 256, 8x8 @ 512)");
+  NL_REQUIRE((long long)F * H * W < (1ll << 31), "", "too many rows (F*H*W < 2^31)");
   return NPVP_OK;
 }
 
-#define NL_DISPATCH(MACRO) \
-  if (A == 8) MACRO(8, 32) else if (A == 16) MACRO(16, 64) else if (A == 32) MACRO(32, 128) else MACRO(64, 256)
+#define NL_DISPATCH(MACRO)                                                                                                         \
+  if (exact) {                                                                                                                     \
+    if (A == 8) MACRO(8, 32, true) else if (A == 16) MACRO(16, 64, true) else if (A == 32) MACRO(32, 128, true) else MACRO(64, 256, true)  \
+  } else {                                                                                                                         \
+    if (A == 8) MACRO(8, 32, false) else if (A == 16) MACRO(16, 64, false) else if (A == 32) MACRO(32, 128, false) else MACRO(64, 256, false) \
+  }
 
-extern "C" int npvp_nonlocal_attn_fwd(const float* q, long long ldq, const float* k, long long ldk, const float* v, long long ldv, float* o,
-                                      long long ldo, float* lse, int F, int H, int W, int A, int V, hipStream_t stream) {
-  NPVP_CHECK_ARG(q && k && v && o && lse, "nonlocal_attn_fwd: null buffer");
-  int wsh;
-  if (int rc = nl_check(F, H, W, A, V, wsh)) return rc;
-  NPVP_CHECK_ARG(ldq >= A && ldk >= A && ldv >= V && ldo >= V, "nonlocal_attn_fwd: leading dimensions");
-  const int HW = H * W;
-  const unsigned grid = (unsigned)((long long)F * HW / (4096 / V));
-#define NL_FWD(a, vv) NPVP_LAUNCH((nl_attn_fwd_kernel<a, vv>), dim3(grid), dim3(256), 0, stream, q, ldq, k, ldk, v, ldv, o, ldo, lse, HW, W, wsh);
+// grid: the any-grid entry point (its name in the error texts, its shapes); the other one refuses what is no config shape
+static int nl_fwd(bool grid, const float* q, long long ldq, const float* k, long long ldk, const float* v, long long ldv, float* o,
+                  long long ldo, float* lse, int F, int H, int W, int A, int V, hipStream_t stream) {
+  NL_REQUIRE(q && k && v && o && lse, "_fwd", "null buffer");
+  if (int rc = nl_check(grid, F, H, W, A, V)) return rc;
+  NL_REQUIRE(ldq >= A && ldk >= A && ldv >= V && ldo >= V, "_fwd", "leading dimensions");
+  const bool exact = !grid || (nl_config_shape(H, W, A) && !nl_force_general());
+  const int QT = 4096 / V;
+  const unsigned gq = (unsigned)((long long)F * ((H * W + QT - 1) / QT));
+#define NL_FWD(a, vv, ex)                                                                                                          \
+  NPVP_LAUNCH((nl_attn_fwd_kernel<a, vv, ex>), dim3(gq), dim3(256), 0, stream, q, ldq, k, ldk, v, ldv, o, ldo, lse,                \
+              NLGeo<ex>::make(F, H, W));
   NL_DISPATCH(NL_FWD)
 #undef NL_FWD
   NPVP_CHECK_LAUNCH();
   return NPVP_OK;
 }
 
+static int nl_bwd(bool grid, const float* q, long long ldq, const float* k, long long ldk, const float* v, long long ldv,
+                  const float* go, long long ldgo, const float* lse, float* D, float* dq, long long lddq, float* dk, long long lddk,
+                  float* dv, long long lddv, int F, int H, int W, int A, int V, hipStream_t stream) {
+  NL_REQUIRE(q && k && v && go && lse && D && dq && dk && dv, "_bwd", "null buffer");
+  if (int rc = nl_check(grid, F, H, W, A, V)) return rc;
+  NL_REQUIRE(ldq >= A && ldk >= A && ldv >= V && ldgo >= V && lddq >= A && lddk >= A && lddv >= V, "_bwd", "leading dimensions");
+  const bool exact = !grid || (nl_config_shape(H, W, A) && !nl_force_general());
+  const int Lk = (H / 2) * (W / 2), T = 4096 / V;                          // T = QT = KB
+  const unsigned gq = (unsigned)((long long)F * ((H * W + T - 1) / T)), gk = (unsigned)((long long)F * ((Lk + T - 1) / T));
+  const int edge = ((H & 1) ? W : 0) + ((W & 1) ? H - (H & 1) : 0);       // rows of a frame that no window covers
+#define NL_BWD(a, vv, ex)                                                                                                          \
+  {                                                                                                                                \
+    NPVP_LAUNCH((nl_attn_dq_kernel<a, vv, ex>), dim3(gq), dim3(256), 0, stream, q, ldq, k, ldk, v, ldv, go, ldgo, lse, D, dq,      \
+                lddq, NLGeo<ex>::make(F, H, W));                                                                                   \
+    NPVP_LAUNCH((nl_attn_dkv_kernel<a, vv, ex>), dim3(gk), dim3(256), 0, stream, q, ldq, k, ldk, v, ldv, go, ldgo, lse, D, dk,     \
+                lddk, dv, lddv, NLGeo<ex>::make(F, H, W));                                                                         \
+  }
+  NL_DISPATCH(NL_BWD)
+#undef NL_BWD
+  if (edge)
+    NPVP_LAUNCH(nlg_attn_edge_kernel, dim3((unsigned)((long long)F * edge)), dim3(64), 0, stream, dk, lddk, dv, lddv, H, W, edge, A, V);
+  NPVP_CHECK_LAUNCH();
+  return NPVP_OK;
+}
+
+extern "C" int npvp_nonlocal_attn_fwd(const float* q, long long ldq, const float* k, long long ldk, const float* v, long long ldv, float* o,
+                                      long long ldo, float* lse, int F, int H, int W, int A, int V, hipStream_t stream) {
+  return nl_fwd(false, q, ldq, k, ldk, v, ldv, o, ldo, lse, F, H, W, A, V, stream);
+}
+
 extern "C" int npvp_nonlocal_attn_bwd(const float* q, long long ldq, const float* k, long long ldk, const float* v, long long ldv,
                                       const float* go, long long ldgo, const float* lse, float* D,
                                       float* dq, long long lddq, float* dk, long long lddk, float* dv, long long lddv, int F, int H, int W,
                                       int A, int V, hipStream_t stream) {
-  NPVP_CHECK_ARG(q && k && v && go && lse && D && dq && dk && dv, "nonlocal_attn_bwd: null buffer");
-  int wsh;
-  if (int rc = nl_check(F, H, W, A, V, wsh)) return rc;
-  NPVP_CHECK_ARG(ldq >= A && ldk >= A && ldv >= V && ldgo >= V && lddq >= A && lddk >= A && lddv >= V,
-                 "nonlocal_attn_bwd: leading dimensions");
-  const int HW = H * W;
-  const unsigned gq = (unsigned)((long long)F * HW / (4096 / V)), gk = (unsigned)((long long)F * (HW / 4) / (4096 / V));
-#define NL_BWD(a, vv)                                                                                                              \
-  {                                                                                                                                \
-    NPVP_LAUNCH((nl_attn_dq_kernel<a, vv>), dim3(gq), dim3(256), 0, stream, q, ldq, k, ldk, v, ldv, go, ldgo, lse, D, dq,     \
-                lddq, HW, W, wsh);                                                                                                 \
-    NPVP_LAUNCH((nl_attn_dkv_kernel<a, vv>), dim3(gk), dim3(256), 0, stream, q, ldq, k, ldk, v, ldv, go, ldgo, lse, D, dk, lddk,   \
-                dv, lddv, F, HW, W, wsh);                                                                                          \
-  }
-  NL_DISPATCH(NL_BWD)
-#undef NL_BWD
-  NPVP_CHECK_LAUNCH();
-  return NPVP_OK;
-}
-
-// ---- non-local attention on any grid.  A shape the entry points above accept goes to them (the same launches, the same bits);
-// every other H, W >= 2 launches the general kernels.  NPVP_NL_GRID_GENERAL=1 sends the config shapes to the general kernels too
-// (measurements: what the masks cost at a shape both forms can run).
-static bool nl_config_shape(int H, int W, int A) {
-  return H % 2 == 0 && (W & (W - 1)) == 0 && (long long)H * W == (A == 8 ? 4096 : A == 16 ? 1024 : A == 32 ? 256 : 64);
-}
-
-static bool nlg_force_general() {
-  static const bool on = [] { const char* e = getenv("NPVP_NL_GRID_GENERAL"); return e && e[0] == '1'; }();
-  return on;
-}
-
-static int nlg_check(int F, int H, int W, int A, int V) {
-  NPVP_CHECK_ARG(F > 0 && H >= 2 && W >= 2, "nonlocal_attn_grid: F >= 1, H >= 2, W >= 2");
-  const bool shape = (A == 8 && V == 32) || (A == 16 && V == 64) || (A == 32 && V == 128) || (A == 64 && V == 256);
-  NPVP_CHECK_ARG(shape, "nonlocal_attn_grid: (attn dim, value dim) must be (8,32), (16,64), (32,128) or (64,256): C = 64..512 of the AE configs");
-  NPVP_CHECK_ARG((long long)F * H * W < (1ll << 31), "nonlocal_attn_grid: too many rows (F*H*W < 2^31)");
-  return NPVP_OK;
+  return nl_bwd(false, q, ldq, k, ldk, v, ldv, go, ldgo, lse, D, dq, lddq, dk, lddk, dv, lddv, F, H, W, A, V, stream);
 }
 
 extern "C" int npvp_nonlocal_attn_grid_fwd(const float* q, long long ldq, const float* k, long long ldk, const float* v, long long ldv,
                                            float* o, long long ldo, float* lse, int F, int H, int W, int A, int V, hipStream_t stream) {
-  NPVP_CHECK_ARG(q && k && v && o && lse, "nonlocal_attn_grid_fwd: null buffer");
-  if (int rc = nlg_check(F, H, W, A, V)) return rc;
-  NPVP_CHECK_ARG(ldq >= A && ldk >= A && ldv >= V && ldo >= V, "nonlocal_attn_grid_fwd: leading dimensions");
-  if (nl_config_shape(H, W, A) && !nlg_force_general())
-    return npvp_nonlocal_attn_fwd(q, ldq, k, ldk, v, ldv, o, ldo, lse, F, H, W, A, V, stream);
-  const int HW = H * W, Wp = W / 2, Lk = (H / 2) * Wp, QT = 4096 / V;
-  const unsigned grid = (unsigned)((long long)F * ((HW + QT - 1) / QT));
-#define NLG_FWD(a, vv) NPVP_LAUNCH((nlg_attn_fwd_kernel<a, vv>), dim3(grid), dim3(256), 0, stream, q, ldq, k, ldk, v, ldv, o, ldo, lse, HW, W, Wp, Lk);
-  NL_DISPATCH(NLG_FWD)
-#undef NLG_FWD
-  NPVP_CHECK_LAUNCH();
-  return NPVP_OK;
+  return nl_fwd(true, q, ldq, k, ldk, v, ldv, o, ldo, lse, F, H, W, A, V, stream);
 }
 
 extern "C" int npvp_nonlocal_attn_grid_bwd(const float* q, long long ldq, const float* k, long long ldk, const float* v, long long ldv,
                                            const float* go, long long ldgo, const float* lse, float* D,
                                            float* dq, long long lddq, float* dk, long long lddk, float* dv, long long lddv, int F, int H,
                                            int W, int A, int V, hipStream_t stream) {
-  NPVP_CHECK_ARG(q && k && v && go && lse && D && dq && dk && dv, "nonlocal_attn_grid_bwd: null buffer");
-  if (int rc = nlg_check(F, H, W, A, V)) return rc;
-  NPVP_CHECK_ARG(ldq >= A && ldk >= A && ldv >= V && ldgo >= V && lddq >= A && lddk >= A && lddv >= V,
-                 "nonlocal_attn_grid_bwd: leading dimensions");
-  if (nl_config_shape(H, W, A) && !nlg_force_general())
-    return npvp_nonlocal_attn_bwd(q, ldq, k, ldk, v, ldv, go, ldgo, lse, D, dq, lddq, dk, lddk, dv, lddv, F, H, W, A, V, stream);
-  const int HW = H * W, Wp = W / 2, Lk = (H / 2) * Wp, T = 4096 / V;      // T = QT = KB
-  const long long rows = (long long)F * HW;
-  const unsigned gq = (unsigned)((long long)F * ((HW + T - 1) / T)), gk = (unsigned)((long long)F * ((Lk + T - 1) / T));
-  const int edge = ((H & 1) ? W : 0) + ((W & 1) ? H - (H & 1) : 0);       // rows of a frame that no window covers
-#define NLG_BWD(a, vv)                                                                                                             \
-  {                                                                                                                                \
-    NPVP_LAUNCH((nlg_attn_dq_kernel<a, vv>), dim3(gq), dim3(256), 0, stream, q, ldq, k, ldk, v, ldv, go, ldgo, lse, D, dq,         \
-                lddq, rows, HW, W, Wp, Lk);                                                                                        \
-    NPVP_LAUNCH((nlg_attn_dkv_kernel<a, vv>), dim3(gk), dim3(256), 0, stream, q, ldq, k, ldk, v, ldv, go, ldgo, lse, D, dk, lddk,  \
-                dv, lddv, rows, HW, W, Wp, Lk);                                                                                    \
-  }
-  NL_DISPATCH(NLG_BWD)
-#undef NLG_BWD
-  if (edge)
-    NPVP_LAUNCH(nlg_attn_edge_kernel, dim3((unsigned)((long long)F * edge)), dim3(64), 0, stream, dk, lddk, dv, lddv, H, W, edge, A, V);
-  NPVP_CHECK_LAUNCH();
-  return NPVP_OK;
+  return nl_bwd(true, q, ldq, k, ldk, v, ldv, go, ldgo, lse, D, dq, lddq, dk, lddk, dv, lddv, F, H, W, A, V, stream);
 }

@@ -2003,10 +2003,12 @@ _NL_GRID = {8: 64, 16: 32, 32: 16, 64: 8}        # attention dim A -> side of th
 
 class _NonLocalAttn(torch.autograd.Function):
     """softmax(q k^T) v of NonLocalAttenion2D (unscaled scores, 2x2 max-pooled keys / values) from ONE projection tensor
-    qkv [F*H*W, ld] = [q | k | v | zero padding]; the gradient comes back in the same layout (npvp_nonlocal_attn_*)."""
+    qkv [F*H*W, ld] = [q | k | v | zero padding]; the gradient comes back in the same layout.  export: "npvp_nonlocal_attn" (the AE
+    configs' grids) or "npvp_nonlocal_attn_grid" (any H x W: floor pooling, the never-pooled last line / column of an odd grid gets
+    dk = dv = 0 from the backward's own kernels); <export>_fwd and <export>_bwd take the same arguments."""
 
     @staticmethod
-    def forward(ctx, qkv, F, H, W, A, V):
+    def forward(ctx, qkv, F, H, W, A, V, export):
         remember(ctx)
         _chk(qkv)
         qkv = _c(qkv)
@@ -2014,16 +2016,16 @@ class _NonLocalAttn(torch.autograd.Function):
         o = torch.empty(F * H * W, V, dtype=torch.float32, device=qkv.device)
         lse = torch.empty(F * H * W, dtype=torch.float32, device=qkv.device)
         p = qkv.data_ptr()
-        check(lib().npvp_nonlocal_attn_fwd(p, ld, p + 4 * A, ld, p + 8 * A, ld, _ptr(o), V, _ptr(lse), F, H, W, A, V, _stream()),
-              "npvp_nonlocal_attn_fwd")
+        check(getattr(lib(), export + "_fwd")(p, ld, p + 4 * A, ld, p + 8 * A, ld, _ptr(o), V, _ptr(lse), F, H, W, A, V, _stream()),
+              export + "_fwd")
         ctx.save_for_backward(qkv, lse)
-        ctx.dims = (F, H, W, A, V)
+        ctx.dims = (F, H, W, A, V, export)
         return o
 
     @scoped
     def backward(ctx, go):
         qkv, lse = ctx.saved_tensors
-        F, H, W, A, V = ctx.dims
+        F, H, W, A, V, export = ctx.dims
         _chk(go)
         go = _c(go)
         ld = qkv.shape[1]
@@ -2032,9 +2034,19 @@ class _NonLocalAttn(torch.autograd.Function):
             dqkv[:, 2 * A + V:].zero_()
         D = torch.empty(2 * F * H * W, dtype=torch.float32, device=qkv.device)
         p, d = qkv.data_ptr(), dqkv.data_ptr()
-        check(lib().npvp_nonlocal_attn_bwd(p, ld, p + 4 * A, ld, p + 8 * A, ld, _ptr(go), V, _ptr(lse), _ptr(D),
-                                           d, ld, d + 4 * A, ld, d + 8 * A, ld, F, H, W, A, V, _stream()), "npvp_nonlocal_attn_bwd")
-        return dqkv, None, None, None, None, None
+        check(getattr(lib(), export + "_bwd")(p, ld, p + 4 * A, ld, p + 8 * A, ld, _ptr(go), V, _ptr(lse), _ptr(D),
+                                              d, ld, d + 4 * A, ld, d + 8 * A, ld, F, H, W, A, V, _stream()), export + "_bwd")
+        return dqkv, None, None, None, None, None, None
+
+
+def _nl_unpacked(packed, name, q, k, v, H, W):
+    """q, k, v (F, H*W, a / a / v) -> packed(q | k | v as one [F*H*W, 2a+v] tensor) as (F, H*W, v)"""
+    F, P, A = q.shape
+    V = v.shape[-1]
+    if k.shape != q.shape or v.shape[:2] != q.shape[:2] or P != H * W:
+        raise RuntimeError(f"{name}: q / k (F, H*W, a), v (F, H*W, v)")
+    qkv = torch.cat([q.reshape(F * P, A), k.reshape(F * P, A), v.reshape(F * P, V)], 1)
+    return packed(qkv, F, H, W, A, V).view(F, P, V)
 
 
 def nonlocal_attn_packed(qkv, F, H, W, A, V):
@@ -2046,17 +2058,12 @@ def nonlocal_attn_packed(qkv, F, H, W, A, V):
                            f"({', '.join(f'{s}x{s} @ {8 * a}' for a, s in _NL_GRID.items())})")
     if qkv.dim() != 2 or qkv.shape[0] != F * H * W or qkv.shape[1] < 2 * A + V:
         raise RuntimeError(f"nonlocal_attn: qkv must be [F*H*W, >= {2 * A + V}]")
-    return _NonLocalAttn.apply(qkv, F, H, W, A, V)
+    return _NonLocalAttn.apply(qkv, F, H, W, A, V, "npvp_nonlocal_attn")
 
 
 def nonlocal_attn(q, k, v, H, W):
     """q, k, v (F, H*W, a / a / v) - k and v the projections BEFORE the 2x2 max-pool - -> (F, H*W, v)"""
-    F, P, A = q.shape
-    V = v.shape[-1]
-    if k.shape != q.shape or v.shape[:2] != q.shape[:2] or P != H * W:
-        raise RuntimeError("nonlocal_attn: q / k (F, H*W, a), v (F, H*W, v)")
-    qkv = torch.cat([q.reshape(F * P, A), k.reshape(F * P, A), v.reshape(F * P, V)], 1)
-    return nonlocal_attn_packed(qkv, F, H, W, A, V).view(F, P, V)
+    return _nl_unpacked(nonlocal_attn_packed, "nonlocal_attn", q, k, v, H, W)
 
 
 def nonlocal_attn_dims(A, V):
@@ -2069,43 +2076,6 @@ def nonlocal_attn_config_shape(A, V, H, W):
     return nonlocal_attn_dims(A, V) and H * W == _NL_GRID[A] ** 2 and H % 2 == 0 and W & (W - 1) == 0
 
 
-class _NonLocalAttnGrid(torch.autograd.Function):
-    """_NonLocalAttn on any H x W grid (npvp_nonlocal_attn_grid_*): floor pooling, the never-pooled last line / column of an odd grid
-    gets dk = dv = 0 from the backward's own kernels"""
-
-    @staticmethod
-    def forward(ctx, qkv, F, H, W, A, V):
-        remember(ctx)
-        _chk(qkv)
-        qkv = _c(qkv)
-        ld = qkv.shape[1]
-        o = torch.empty(F * H * W, V, dtype=torch.float32, device=qkv.device)
-        lse = torch.empty(F * H * W, dtype=torch.float32, device=qkv.device)
-        p = qkv.data_ptr()
-        check(lib().npvp_nonlocal_attn_grid_fwd(p, ld, p + 4 * A, ld, p + 8 * A, ld, _ptr(o), V, _ptr(lse), F, H, W, A, V, _stream()),
-              "npvp_nonlocal_attn_grid_fwd")
-        ctx.save_for_backward(qkv, lse)
-        ctx.dims = (F, H, W, A, V)
-        return o
-
-    @scoped
-    def backward(ctx, go):
-        qkv, lse = ctx.saved_tensors
-        F, H, W, A, V = ctx.dims
-        _chk(go)
-        go = _c(go)
-        ld = qkv.shape[1]
-        dqkv = torch.empty_like(qkv)
-        if ld > 2 * A + V:
-            dqkv[:, 2 * A + V:].zero_()
-        D = torch.empty(2 * F * H * W, dtype=torch.float32, device=qkv.device)
-        p, d = qkv.data_ptr(), dqkv.data_ptr()
-        check(lib().npvp_nonlocal_attn_grid_bwd(p, ld, p + 4 * A, ld, p + 8 * A, ld, _ptr(go), V, _ptr(lse), _ptr(D),
-                                                d, ld, d + 4 * A, ld, d + 8 * A, ld, F, H, W, A, V, _stream()),
-              "npvp_nonlocal_attn_grid_bwd")
-        return dqkv, None, None, None, None, None
-
-
 def nonlocal_attn_grid_packed(qkv, F, H, W, A, V):
     """nonlocal_attn_packed on any grid H, W >= 2 (odd, rectangular, not a power of two): the keys / values are the
     floor(H/2) x floor(W/2) windows of nn.MaxPool2d((2, 2), stride=2); a config shape runs nonlocal_attn_packed's own kernels"""
@@ -2115,17 +2085,12 @@ def nonlocal_attn_grid_packed(qkv, F, H, W, A, V):
         raise RuntimeError(f"nonlocal_attn_grid: a {H}x{W} grid has no 2x2 window")
     if qkv.dim() != 2 or qkv.shape[0] != F * H * W or qkv.shape[1] < 2 * A + V:
         raise RuntimeError(f"nonlocal_attn_grid: qkv must be [F*H*W, >= {2 * A + V}]")
-    return _NonLocalAttnGrid.apply(qkv, F, H, W, A, V)
+    return _NonLocalAttn.apply(qkv, F, H, W, A, V, "npvp_nonlocal_attn_grid")
 
 
 def nonlocal_attn_grid(q, k, v, H, W):
     """nonlocal_attn on any grid H, W >= 2"""
-    F, P, A = q.shape
-    V = v.shape[-1]
-    if k.shape != q.shape or v.shape[:2] != q.shape[:2] or P != H * W:
-        raise RuntimeError("nonlocal_attn_grid: q / k (F, H*W, a), v (F, H*W, v)")
-    qkv = torch.cat([q.reshape(F * P, A), k.reshape(F * P, A), v.reshape(F * P, V)], 1)
-    return nonlocal_attn_grid_packed(qkv, F, H, W, A, V).view(F, P, V)
+    return _nl_unpacked(nonlocal_attn_grid_packed, "nonlocal_attn_grid", q, k, v, H, W)
 
 
 class _ReflectPad(torch.autograd.Function):

@@ -98,30 +98,34 @@ def _attn_ref(q, k, v, H, W):
 
 
 NL_SHAPES = [(64, 64), (128, 32), (256, 16), (512, 8)]       # (C, grid): every (C, grid) pair of the five AE configs
+# (C, H, W) the config kernels also take (H even, W a power of two, the config's cell count) that are not square: the smallest with
+# one pooled row (Hp = 1), with one pooled column (Wp = 1: the window decode's shift is 0), and with W != sqrt(HW)
+NL_RECT = [(512, 2, 32), (512, 32, 2), (128, 16, 64)]
+NL_CASES = [pytest.param(C, S, S, id=f"{C}-{S}") for C, S in NL_SHAPES] + [pytest.param(C, H, W, id=f"{C}-{H}x{W}") for C, H, W in NL_RECT]
 
 
-def _nl_inputs(C, S, Fr, seed, tie=False):
+def _nl_inputs(C, H, W, Fr, seed, tie=False):
     A, V = C // 8, C // 2
-    q = O.seeded_randn((Fr, S * S, A), seed) * (1.5 / A ** 0.5)
-    k = O.seeded_randn((Fr, S * S, A), seed + 1)
-    v = O.seeded_randn((Fr, S * S, V), seed + 2)
+    q = O.seeded_randn((Fr, H * W, A), seed) * (1.5 / A ** 0.5)
+    k = O.seeded_randn((Fr, H * W, A), seed + 1)
+    v = O.seeded_randn((Fr, H * W, V), seed + 2)
     if tie:       # whole windows of equal values (a post-ReLU zero pixel gives exactly the bias): the first element must win
         k[0, 1] = k[0, 0]; v[0, 1] = v[0, 0]
-        k[0, S] = k[0, 0]; v[0, S + 1] = v[0, S]
-        k[1, S + 1] = k[1, S]; k[1, 1] = k[1, S]
+        k[0, W] = k[0, 0]; v[0, W + 1] = v[0, W]
+        k[1, W + 1] = k[1, W]; k[1, 1] = k[1, W]
     return q, k, v
 
 
-@pytest.mark.parametrize("C,S", NL_SHAPES)
+@pytest.mark.parametrize("C,H,W", NL_CASES)
 @pytest.mark.parametrize("tie", [False, True])
-def test_nonlocal_attn_vs_float64(npvp, C, S, tie):
-    q, k, v = _nl_inputs(C, S, 2, 20 + C, tie)
-    go = O.seeded_randn((2, S * S, C // 2), 30 + C)
+def test_nonlocal_attn_vs_float64(npvp, C, H, W, tie):
+    q, k, v = _nl_inputs(C, H, W, 2, 20 + C, tie)
+    go = O.seeded_randn((2, H * W, C // 2), 30 + C)
     qd, kd, vd = (t.double().requires_grad_() for t in (q, k, v))
-    od = _attn_ref(qd, kd, vd, S, S)
+    od = _attn_ref(qd, kd, vd, H, W)
     od.backward(go.double())
     qg, kg, vg = (t.to(DEV).requires_grad_() for t in (q, k, v))
-    og = npvp.ops.nonlocal_attn(qg, kg, vg, S, S)
+    og = npvp.ops.nonlocal_attn(qg, kg, vg, H, W)
     og.backward(go.to(DEV))
     assert rel(og, od) < KERNEL_TOL
     for a, b in ((qg.grad, qd.grad), (kg.grad, kd.grad), (vg.grad, vd.grad)):
@@ -170,7 +174,7 @@ def test_new_kernels_are_bit_reproducible(npvp):
         yn = npvp.ops.bn_act_train(xn, w[:64].detach().clone().requires_grad_(), b[:64].detach().clone(), None, None, 0.1, 1e-5, 0, True)
         yn.backward(O.seeded_randn(yn.shape, 53).to(DEV))
         outs += [yn, xn.grad]
-        q, k, v = (t.to(DEV).requires_grad_() for t in _nl_inputs(64, 64, 2, 54))
+        q, k, v = (t.to(DEV).requires_grad_() for t in _nl_inputs(64, 64, 64, 2, 54))
         o = npvp.ops.nonlocal_attn(q, k, v, 64, 64)
         o.backward(O.seeded_randn(o.shape, 55).to(DEV))
         outs += [o, q.grad, k.grad, v.grad]

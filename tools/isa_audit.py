@@ -1,5 +1,5 @@
 """What the compiler made of every kernel: per kernel the instruction count by class (scalar / vector / MFMA), integer-division
-sequences (v_rcp_iflag_f32 = one 32-bit division, 64-bit ones show as mul_hi chains), VGPRs, spills and scratch bytes, plus the
+sequences (v_rcp_iflag_f32 = one 32-bit division, 64-bit ones show as mul_hi chains), VGPRs, spills, scratch and LDS bytes, plus the
 loops the optimizer refused to unroll (-Rpass-missed=loop-unroll: an epilogue that indexes its accumulator tiles in such a loop keeps
 them in scratch memory).  Runs hipcc --cuda-device-only -S on npvp_amd/csrc/*.hip; no GPU needed.
 Usage: python tools/isa_audit.py [file.hip ...] [--min N]      (kernels with fewer than N instructions are left out, default 50)"""
@@ -25,7 +25,7 @@ def demangle(names):
     return [re.sub(r"\(.*", "", o) for o in out]
 
 
-print(f"{'file':14s} {'instr':>6s} {'scalar':>6s} {'vector':>6s} {'mfma':>5s} {'idiv':>4s} {'mulhi':>5s} {'vgpr':>4s} {'spill':>5s} {'scratch':>7s}  kernel")
+print(f"{'file':14s} {'instr':>6s} {'scalar':>6s} {'vector':>6s} {'mfma':>5s} {'idiv':>4s} {'mulhi':>5s} {'vgpr':>4s} {'spill':>5s} {'scratch':>7s} {'lds':>6s}  kernel")
 for f in files:
     src = os.path.join(CSRC, os.path.basename(f))
     with tempfile.TemporaryDirectory() as td:
@@ -37,7 +37,7 @@ for f in files:
             continue
         missed = sorted(set(re.findall(r"(\S+\.(?:hip|h):\d+):\d+: remark: Unable to (?:fully )?unroll", r.stderr)))
         lines = open(asm).read().split("\n")
-    cur, stats, meta = None, {}, {}
+    cur, stats, meta, lds = None, {}, {}, 0
     for ln in lines:
         m = re.match(r"^(_Z\w+):", ln)
         if m:
@@ -50,7 +50,10 @@ for f in files:
         m = re.match(r"\s+\.name:\s+(\S+)", ln)
         if m:
             metak = m.group(1)
-            meta[metak] = {}
+            meta[metak] = {"group_segment_fixed_size": lds}
+        m = re.match(r"\s+\.group_segment_fixed_size:\s+(\d+)", ln)       # (a kernel's keys are sorted: this one comes before .name)
+        if m:
+            lds = int(m.group(1))
         m = re.match(r"\s+\.(vgpr_count|vgpr_spill_count|private_segment_fixed_size):\s+(\d+)", ln)
         if m and meta:
             meta[metak][m.group(1)] = int(m.group(2))
@@ -70,6 +73,6 @@ for f in files:
     for k, name in zip(keys, demangle(keys)):
         st, mt = stats[k], meta.get(k, {})
         print(f"{os.path.basename(f):14s} {st['n']:6d} {st['s']:6d} {st['v']:6d} {st['mfma']:5d} {st['idiv']:4d} {st['mulhi']:5d} "
-              f"{mt.get('vgpr_count', 0):4d} {mt.get('vgpr_spill_count', 0):5d} {mt.get('private_segment_fixed_size', 0):7d}  {name[:110]}")
+              f"{mt.get('vgpr_count', 0):4d} {mt.get('vgpr_spill_count', 0):5d} {mt.get('private_segment_fixed_size', 0):7d} {mt.get('group_segment_fixed_size', 0):6d}  {name[:110]}")
     for m in missed:
         print(f"{os.path.basename(f):14s} LOOP NOT UNROLLED as the pragma asks: {m}")
