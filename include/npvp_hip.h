@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-typedef void* npvp_stream_t; /* hipStream_t */
+typedef struct ihipStream_t* npvp_stream_t; /* == hipStream_t */
 
 int npvp_version(void);
 const char* npvp_last_error(void);

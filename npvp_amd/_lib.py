@@ -1,140 +1,77 @@
-"""ctypes binding of libnpvp_hip.so (include/npvp_hip.h).  There is NO fallback: if the
-shared object is missing or a call fails, a RuntimeError is raised - the product path never
-computes on the CPU or through torch ops in place of a HIP kernel."""
+"""ctypes binding of libnpvp_hip.so.  include/npvp_hip.h is the one declaration of the C ABI: the library is compiled against it,
+and SIGNATURES below is parsed from it at import (there is no hand-written table to keep in step).  There is NO fallback: if the
+shared object or the header is missing or a call fails, a RuntimeError is raised - the product path never computes on the CPU or
+through torch ops in place of a HIP kernel."""
 import ctypes
 import os
+import re
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libnpvp_hip.so")
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "npvp_hip.h")
 
+# C type of a value parameter or return -> ctypes type (size_t: LP64).  Every pointer parameter and npvp_stream_t is a c_void_p.
+# A type the header uses and this map does not cover is an error: extending the ABI's vocabulary is an edit here.
 c_int, c_ll, c_f, c_u, c_p = ctypes.c_int, ctypes.c_longlong, ctypes.c_float, ctypes.c_uint, ctypes.c_void_p
+_VALUE_TYPES = {"int": c_int, "long long": c_ll, "size_t": c_ll, "float": c_f, "unsigned int": c_u}
+_RETURN_TYPES = dict(_VALUE_TYPES, **{"const char*": ctypes.c_char_p, "void*": c_p})
+_VALUE_TYPES["npvp_stream_t"] = c_p
 
-# name -> (restype, argtypes)  - mirrors include/npvp_hip.h one to one
-SIGNATURES = {
-    "npvp_version": (c_int, []),
-    "npvp_last_error": (ctypes.c_char_p, []),
-    "npvp_launch_count": (c_ll, []),
-    "npvp_dp_unique_id": (c_int, [c_p]),
-    "npvp_dp_init": (c_int, [c_int, c_int, c_p]),
-    "npvp_dp_world": (c_int, []),
-    "npvp_dp_rank": (c_int, []),
-    "npvp_dp_allreduce_async": (c_int, [c_p, c_ll, c_p]),          # (size_t n: LP64)
-    "npvp_dp_wait": (c_int, [c_p]),
-    "npvp_dp_finalize": (c_int, []),
-    "npvp_stream_create_low_priority": (c_p, [c_p, c_p]),
-    "npvp_stream_destroy": (c_int, [c_p]),
-    "npvp_event_create": (c_p, []),
-    "npvp_event_record": (c_int, [c_p, c_p]),
-    "npvp_event_elapsed_ms": (c_f, [c_p, c_p]),
-    "npvp_event_destroy": (c_int, [c_p]),
-    "npvp_graph_node_counts": (c_ll, [c_p, c_p, c_p, c_int]),
-    "npvp_gemm_workspace_bytes": (c_ll, [c_int, c_int, c_int]),
-    "npvp_gemm_kernel_id": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
-    "npvp_gemm_route": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_p]),
-    "npvp_gemm_f32": (c_int, [c_int, c_int, c_int, c_int, c_int, c_p, c_ll, c_p, c_ll, c_p, c_ll, c_p, c_int, c_p, c_p,
-                              c_p, c_ll, c_f, c_int, c_int, c_int, c_p, c_u, c_f, c_int, c_p, c_p, c_int, c_p, c_p, c_p, c_p, c_p,
-                              c_f, c_int, c_int, c_u, c_p, c_ll, c_p]),
-    "npvp_amax": (c_int, [c_p, c_ll, c_ll, c_ll, c_p, c_p]),
-    "npvp_wgrad_f16_chainable": (c_int, [c_int, c_int, c_int]),
-    "npvp_wgrad_f16_chain_workspace_bytes": (c_ll, [c_int, c_int, c_int]),
-    "npvp_wgrad_f16_chained": (c_int, [c_int, c_int, c_int, c_p, c_ll, c_p, c_ll, c_p, c_ll, c_p, c_int, c_p, c_p, c_p, c_f, c_int, c_int,
-                                       c_u, c_p, c_p, c_p, c_p, c_ll, c_p]),
-    "npvp_splitk_reduce_job": (c_int, [c_p, c_p]),
-    "npvp_splitk_reduce_multi": (c_int, [c_p, c_int, c_p]),
-    "npvp_linear_bwd_f16_takes": (c_int, [c_int, c_int, c_int]),
-    "npvp_linear_bwd_f16": (c_int, [c_int, c_int, c_int, c_p, c_ll, c_p, c_p, c_p, c_p, c_ll, c_int, c_p, c_p, c_ll, c_f, c_int, c_int, c_int,
-                                    c_u, c_p, c_p, c_ll, c_p, c_p, c_ll, c_p, c_p, c_f, c_int, c_int, c_u, c_p, c_p, c_p, c_p, c_ll, c_p]),
-    "npvp_split_weight_f16": (c_int, [c_p, c_ll, c_int, c_int, c_p, c_p, c_p, c_p]),
-    "npvp_split_weights_f16": (c_int, [c_p, c_int, c_p, c_ll, c_p]),
-    "npvp_frame_stats_finalize": (c_int, [c_p, c_int, c_f, c_p, c_p, c_int, c_f, c_p]),
-    "npvp_split_weight": (c_int, [c_p, c_ll, c_int, c_int, c_p, c_p, c_p]),
-    "npvp_split_weights_batched": (c_int, [c_p, c_int, c_p]),
-    "npvp_layernorm_fwd": (c_int, [c_p, c_p, c_p, c_p, c_p, c_p, c_ll, c_int, c_f, c_int, c_p, c_p]),
-    "npvp_layernorm_bwd_workspace_bytes": (c_ll, [c_ll, c_int]),
-    "npvp_layernorm_bwd": (c_int, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_ll, c_int, c_int, c_p, c_int, c_p, c_p, c_ll, c_p]),
-    "npvp_layernorm_bwd_reduce": (c_int, [c_p, c_p, c_p, c_ll, c_int, c_int, c_p]),
-    "npvp_layernorm_bwd_reduce_job": (c_int, [c_p, c_p, c_p, c_ll, c_int, c_int, c_p]),
-    "npvp_frameln_act_bwd_reduce_job": (c_int, [c_p, c_p, c_p, c_int, c_int, c_int, c_p]),
-    "npvp_mlpdw_mid_bwd_reduce_job": (c_int, [c_p, c_p, c_p, c_int, c_int, c_p]),
-    "npvp_sum_rows_multi": (c_int, [c_p, c_int, c_p]),
-    "npvp_layernorm_nchw_fwd": (c_int, [c_p, c_p, c_p, c_p, c_p, c_p, c_int, c_int, c_int, c_f, c_int, c_p]),
-    "npvp_frameln_act_bwd_reduce": (c_int, [c_p, c_p, c_p, c_int, c_int, c_int, c_p]),
-    "npvp_frame_stats": (c_int, [c_p, c_p, c_p, c_p, c_int, c_int, c_int, c_f, c_p]),
-    "npvp_posfuse_fwd": (c_int, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_int, c_int, c_int, c_f, c_p, c_p]),
-    "npvp_posfuse_instance_fwd": (c_int, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_int, c_int, c_int, c_int, c_f, c_p, c_p]),
-    "npvp_posfuse_instance_bwd": (c_int, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_int, c_int, c_int, c_int, c_p]),
-    "npvp_ln_posfuse_fwd": (c_int, [c_p, c_p, c_p, c_f, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_int, c_int, c_int, c_int, c_f,
-                                    c_p, c_p, c_p]),
-    "npvp_posfuse_bwd_fused": (c_int, [c_int, c_int, c_int]),
-    "npvp_posfuse_bwd": (c_int, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_int, c_int, c_int, c_int, c_p, c_ll, c_p]),
-    "npvp_frameln_act_fwd": (c_int, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_int, c_int, c_f, c_u, c_f, c_u, c_int, c_p, c_p, c_p]),
-    "npvp_frameln_act_bwd_workspace_bytes": (c_ll, [c_int, c_int]),
-    "npvp_frameln_act_bwd": (c_int, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_int, c_int, c_f, c_u, c_f, c_u, c_int,
-                                     c_p, c_int, c_p, c_p, c_ll, c_p]),
-    "npvp_dwconv3x3": (c_int, [c_p, c_p, c_p, c_p, c_int, c_int, c_int, c_int, c_int, c_p]),
-    "npvp_dwconv3x3_stats": (c_int, [c_p, c_p, c_p, c_p, c_p, c_p, c_int, c_int, c_int, c_int, c_f, c_p, c_ll, c_p]),
-    "npvp_mlpdw_mid_fwd": (c_int, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_int, c_int, c_int, c_int, c_f, c_p, c_ll, c_p]),
-    "npvp_mlpdw_mid_fwd_parts": (c_int, [c_p, c_p, c_int, c_f, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_int, c_int, c_int, c_int, c_f, c_p]),
-    "npvp_frameln_act_fwd_parts": (c_int, [c_p, c_p, c_int, c_f, c_f, c_p, c_p, c_p, c_p, c_p, c_p, c_int, c_int, c_f, c_u, c_f, c_u, c_int,
-                                           c_p, c_p, c_p]),
-    "npvp_mlpdw_mid_bwd_workspace_bytes": (c_ll, [c_int, c_int]),
-    "npvp_mlpdw_mid_bwd": (c_int, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_int, c_int, c_int, c_int, c_int, c_p, c_ll, c_p]),
-    "npvp_mlpdw_mid_bwd_reduce": (c_int, [c_p, c_p, c_int, c_int, c_int, c_p]),
-    "npvp_mlpdw_mid_bwd_reduce_into": (c_int, [c_p, c_p, c_p, c_int, c_int, c_p]),
-    "npvp_mlpdw_mid_bwd_n2": (c_int, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_int, c_f, c_u, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p,
-                                      c_p, c_int, c_int, c_int, c_int, c_int, c_p, c_ll, c_p]),
-    "npvp_frameln_act_bwd_pgrad": (c_int, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_int, c_int, c_f, c_u, c_f, c_u, c_int,
-                                           c_p, c_int, c_p, c_ll, c_p]),
-    "npvp_frameln_act_bwd_apply": (c_int, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_int, c_p, c_p, c_p, c_int, c_int, c_int, c_p, c_p, c_ll, c_p]),
-    "npvp_im2col3x3": (c_int, [c_p, c_p, c_int, c_int, c_int, c_int, c_int, c_p]),
-    "npvp_dwconv3x3_wgrad_workspace_bytes": (c_ll, [c_int, c_int]),
-    "npvp_dwconv3x3_wgrad": (c_int, [c_p, c_p, c_p, c_int, c_int, c_int, c_int, c_p, c_ll, c_p]),
-    "npvp_attn_fwd": (c_int, [c_p, c_ll, c_p, c_ll, c_p, c_ll, c_p, c_ll, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
-                              c_int, c_int, c_int, c_f, c_p, c_u, c_p, c_p]),
-    "npvp_attn_bwd": (c_int, [c_p, c_ll, c_p, c_ll, c_p, c_ll, c_p, c_ll, c_p, c_ll, c_p, c_ll, c_p, c_ll, c_int, c_int,
-                              c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_f, c_p, c_u, c_p, c_p, c_p, c_p]),
-    "npvp_attn_long_fwd": (c_int, [c_p, c_ll, c_p, c_ll, c_p, c_ll, c_p, c_ll, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
-                                   c_int, c_int, c_int, c_f, c_p, c_u, c_p, c_p]),
-    "npvp_attn_long_bwd_workspace_bytes": (c_ll, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
-    "npvp_attn_long_bwd": (c_int, [c_p, c_ll, c_p, c_ll, c_p, c_ll, c_p, c_ll, c_p, c_ll, c_p, c_ll, c_p, c_ll, c_int, c_int,
-                                   c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_f, c_p, c_u, c_p, c_p, c_p, c_p, c_ll, c_p]),
-    "npvp_drop_apply": (c_int, [c_p, c_p, c_ll, c_int, c_f, c_int, c_int, c_int, c_p, c_u, c_p, c_p]),
-    "npvp_transpose": (c_int, [c_p, c_p, c_int, c_int, c_int, c_p]),
-    "npvp_dwtb_accumulate": (c_int, [c_p, c_p, c_p, c_int, c_p]),
-    "npvp_dwtb_build": (c_int, [c_p, c_p, c_p, c_int, c_p]),
-    "npvp_reduce_mid": (c_int, [c_p, c_p, c_int, c_int, c_ll, c_f, c_int, c_p]),
-    "npvp_broadcast_mid": (c_int, [c_p, c_p, c_int, c_int, c_ll, c_f, c_p]),
-    "npvp_colsum_workspace_bytes": (c_ll, [c_ll, c_int]),
-    "npvp_colsum": (c_int, [c_p, c_ll, c_int, c_ll, c_p, c_int, c_p, c_ll, c_p]),
-    "npvp_grad_norm_clip": (c_int, [c_p, c_ll, c_f, c_p, c_p, c_ll, c_p]),
-    "npvp_l1_mean": (c_int, [c_p, c_p, c_ll, c_f, c_p, c_p, c_ll, c_p]),
-    "npvp_l1_mean_bwd": (c_int, [c_p, c_p, c_ll, c_p, c_f, c_p, c_p]),
-    "npvp_sum_all": (c_int, [c_p, c_ll, c_p, c_p, c_ll, c_p]),
-    "npvp_adamw_step": (c_int, [c_p, c_p, c_p, c_p, c_ll, c_p, c_f, c_f, c_f, c_f, c_p, c_ll, c_ll, c_int, c_p]),
-    "npvp_sqdiff_workspace_bytes": (c_ll, [c_int, c_ll]),
-    "npvp_sqdiff_per_image": (c_int, [c_p, c_p, c_int, c_ll, c_f, c_f, c_p, c_p, c_ll, c_p]),
-    "npvp_ssim_workspace_bytes": (c_ll, [c_int, c_int, c_int, c_int]),
-    "npvp_u8hwc_to_f32chw": (c_int, [c_p, c_p, c_ll, c_int, c_int, c_int, c_p, c_p, c_p]),
-    "npvp_bias_act": (c_int, [c_p, c_p, c_p, c_p, c_ll, c_ll, c_int, c_int, c_int, c_p]),
-    "npvp_act_bwd": (c_int, [c_p, c_p, c_p, c_ll, c_int, c_p]),
-    "npvp_bn_workspace_bytes": (c_int, [c_int]),
-    "npvp_bn_stats": (c_int, [c_p, c_ll, c_ll, c_int, c_int, c_p, c_p, c_ll, c_p]),
-    "npvp_bn_act_apply": (c_int, [c_p, c_p, c_p, c_p, c_p, c_ll, c_f, c_f, c_p, c_p, c_ll, c_ll, c_int, c_int, c_int, c_p, c_p, c_p, c_p]),
-    "npvp_bn_act_bwd": (c_int, [c_p, c_p, c_p, c_p, c_p, c_p, c_ll, c_ll, c_int, c_int, c_int, c_int, c_p, c_p, c_p, c_p, c_ll, c_p]),
-    "npvp_bn_act_apply_sync": (c_int, [c_p, c_p, c_p, c_p, c_p, c_f, c_f, c_p, c_p, c_ll, c_ll, c_int, c_int, c_int, c_p, c_p, c_p, c_p]),
-    "npvp_bn_bwd_sums": (c_int, [c_p, c_p, c_p, c_p, c_p, c_p, c_ll, c_ll, c_int, c_int, c_int, c_p, c_p, c_p, c_p, c_ll, c_p]),
-    "npvp_bn_act_bwd_apply": (c_int, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_ll, c_ll, c_int, c_int, c_int, c_p, c_p]),
-    "npvp_reflect_pad": (c_int, [c_p, c_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_p]),
-    "npvp_nonlocal_attn_fwd": (c_int, [c_p, c_ll, c_p, c_ll, c_p, c_ll, c_p, c_ll, c_p, c_int, c_int, c_int, c_int, c_int, c_p]),
-    "npvp_nonlocal_attn_bwd": (c_int, [c_p, c_ll, c_p, c_ll, c_p, c_ll, c_p, c_ll, c_p, c_p, c_p, c_ll, c_p, c_ll, c_p, c_ll, c_int, c_int,
-                                       c_int, c_int, c_int, c_p]),
-    "npvp_nonlocal_attn_grid_fwd": (c_int, [c_p, c_ll, c_p, c_ll, c_p, c_ll, c_p, c_ll, c_p, c_int, c_int, c_int, c_int, c_int, c_p]),
-    "npvp_nonlocal_attn_grid_bwd": (c_int, [c_p, c_ll, c_p, c_ll, c_p, c_ll, c_p, c_ll, c_p, c_p, c_p, c_ll, c_p, c_ll, c_p, c_ll, c_int,
-                                            c_int, c_int, c_int, c_int, c_p]),
-    "npvp_ssim_per_image": (c_int, [c_p, c_p, c_int, c_int, c_int, c_int, c_p, c_int, c_p, c_p, c_ll, c_p]),
-}
+
+def parse_header(text):
+    """{name: (C return type, [C parameter types])} of every prototype in the text of a header written like include/npvp_hip.h:
+    comments, preprocessor lines, the extern "C" braces and typedefs are dropped, and every statement left must be a prototype
+    `type name(type name, ...)` or `type name(void)` - anything else raises."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    text = re.sub(r"^\s*#.*$", " ", text, flags=re.M)
+    text = re.sub(r'extern\s+"C"\s*\{', " ", text)
+    text = re.sub(r"\btypedef\b[^;{]*(\{[^}]*\}[^;{]*)?;", " ", text)
+    *statements, tail = text.split(";")
+    if tail.strip() not in ("", "}"):
+        raise RuntimeError(f"npvp_hip.h: unterminated text after the last prototype: {tail.strip()!r}")
+    protos = {}
+    for st in statements:
+        st = " ".join(st.split())
+        m = re.fullmatch(r"([\w\s]+?[\s*]+)(npvp_\w+) ?\((.*)\)", st)
+        if not m or m.group(2) in protos:
+            raise RuntimeError(f"npvp_hip.h: not a prototype, or declared twice: {st!r}")
+        params = []
+        for p in ([] if m.group(3).strip() == "void" else m.group(3).split(",")):
+            pm = re.fullmatch(r"\s*([\w\s]+?[\s*]+)\w+\s*", p)
+            if not pm:
+                raise RuntimeError(f"npvp_hip.h: parameter {p.strip()!r} of {m.group(2)} is not `type name`: {st!r}")
+            params.append(re.sub(r"\s*\*\s*", "*", pm.group(1)).strip())
+        protos[m.group(2)] = (re.sub(r"\s*\*\s*", "*", m.group(1)).strip(), params)
+    return protos
+
+
+def signatures(protos):
+    """{name: (restype, [argtypes])} for ctypes from parse_header's result; a type outside the maps above raises and names the prototype."""
+    out = {}
+    for name, (ret, params) in protos.items():
+        unmapped = [t for t in params if not t.endswith("*") and t not in _VALUE_TYPES] + [ret] * (ret not in _RETURN_TYPES)
+        if unmapped:
+            raise RuntimeError(f"npvp_hip.h: {name}: no ctypes mapping for C type {unmapped[0]!r} (npvp_amd/_lib.py _VALUE_TYPES / _RETURN_TYPES)")
+        out[name] = (_RETURN_TYPES[ret], [c_p if t.endswith("*") else _VALUE_TYPES[t] for t in params])
+    return out
+
+
+if not os.path.exists(HEADER_PATH):
+    raise RuntimeError(f"{HEADER_PATH} is missing - npvp_amd reads the C ABI of libnpvp_hip.so from the public header of its "
+                       "repository tree. npvp_amd has no CPU fallback.")
+with open(HEADER_PATH) as _f:
+    PROTOTYPES = parse_header(_f.read())     # name -> (C return type, [C parameter types]); build.py casts to these
+SIGNATURES = signatures(PROTOTYPES)          # name -> (restype, argtypes)
 
 _lib = None
+
+
+def bind(cdll, names=SIGNATURES):
+    """give the named entry points of a loaded library (all of them by default) the header's restype / argtypes; returns cdll"""
+    for name in names:
+        fn = getattr(cdll, name)          # AttributeError here = header/library mismatch
+        fn.restype, fn.argtypes = SIGNATURES[name]
+    return cdll
 
 
 def lib():
@@ -146,14 +83,12 @@ def lib():
                 f"{LIB_PATH} is missing - the HIP extension has not been built. Run "
                 "`python -c 'import __graft_entry__ as g; g.build()'` (or `python npvp_amd/build.py`). "
                 "npvp_amd has no CPU fallback.")
-        L = ctypes.CDLL(LIB_PATH, mode=os.RTLD_NOW)        # resolve every symbol now: a broken build fails here
+        L = bind(ctypes.CDLL(LIB_PATH, mode=os.RTLD_NOW))        # resolve every symbol now: a broken build fails here
         bound = _Bound()
-        for name, (res, args) in SIGNATURES.items():
-            fn = getattr(L, name)          # AttributeError here = header/library mismatch
-            fn.restype, fn.argtypes = res, args
-            setattr(bound, name, fn)
+        for name in SIGNATURES:
+            setattr(bound, name, getattr(L, name))
         bound._cdll = L
-        # The same entry points through C-API wrappers (npvp_amd/_npvp_fast.so, generated by build.py from SIGNATURES): ctypes spends
+        # The same entry points through C-API wrappers (npvp_amd/_npvp_fast.so, generated by build.py from the same header): ctypes spends
         # ~0.25 us per argument on its prototype machinery - 7 - 8 ms of a host-bound 8-clip step.  Same functions of the same
         # library, same arguments, same return values; NPVP_FASTCALL=0 keeps ctypes (A/B runs), and so does a missing module.
         bound._fast = 0

@@ -2,7 +2,10 @@
 
 The shared object lives next to this file (npvp_amd/libnpvp_hip.so): it is git-ignored but
 travels to the GPU box with the repo snapshot.  Incremental: a source is recompiled only when it
-(or a header of csrc/) is newer than its object file.
+(or a header of csrc/, or include/npvp_hip.h) is newer than its object file.
+
+include/npvp_hip.h is the one declaration of the C ABI: every source includes it (through csrc/common.h), so a definition that
+disagrees with its prototype stops the build ("conflicting types"), and the generated call wrappers include it too.
 """
 import os
 import subprocess
@@ -11,11 +14,12 @@ from concurrent.futures import ThreadPoolExecutor
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
+INCLUDE = os.path.join(os.path.dirname(HERE), "include")          # the public header npvp_hip.h
 OBJ = os.path.join(CSRC, "obj")
 LIB = os.path.join(HERE, "libnpvp_hip.so")
 FAST = os.path.join(HERE, "_npvp_fast.so")          # CPython call wrappers of the same entry points (see build_fastcall)
 ARCH = "gfx950"
-FLAGS = ["-O3", "-fPIC", "-std=c++17", f"--offload-arch={ARCH}", "-fno-gpu-rdc", "-Wno-unused-result"]
+FLAGS = ["-O3", "-fPIC", "-std=c++17", f"--offload-arch={ARCH}", "-fno-gpu-rdc", "-Wno-unused-result", f"-I{INCLUDE}"]
 
 
 def _hipcc():
@@ -32,7 +36,7 @@ def _newer(a, b):
 def build(force=False, verbose=True):
     os.makedirs(OBJ, exist_ok=True)
     srcs = sorted(f for f in os.listdir(CSRC) if f.endswith(".hip"))
-    hdrs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
+    hdrs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")] + [os.path.join(INCLUDE, "npvp_hip.h")]
     hipcc = _hipcc()
     jobs = []
     for s in srcs:
@@ -69,21 +73,24 @@ def build(force=False, verbose=True):
         build_fastcall(verbose=verbose)
     except (OSError, RuntimeError) as e:
         # _npvp_fast is optional (npvp_amd._lib falls back to ctypes): no g++, or a compile / link error, must not fail the build
-        # of the library itself.  A stale module generated for older SIGNATURES must not be imported either.
+        # of the library itself.  A stale module generated for an older header must not be imported either.
         print(f"[npvp_amd.build] WARNING: the C-API call wrappers were not built ({e}); calls go through ctypes", file=sys.stderr)
         if os.path.exists(FAST):
             os.remove(FAST)
     return LIB
 
 
-# (LP64: ctypes.c_longlong IS ctypes.c_long, its __name__ is "c_long")
-_C_TYPE = {"c_int": ("int", "L"), "c_longlong": ("long long", "L"), "c_long": ("long long", "L"), "c_float": ("float", "F"),
-           "c_uint": ("unsigned int", "U"), "c_void_p": ("void*", "P")}
+# how a wrapper reads an argument of each ctypes kind: (C variable, reader).  (LP64: ctypes.c_longlong IS ctypes.c_long, its
+# __name__ is "c_long")
+_ARG_READ = {"c_int": ("long long", "arg_ll"), "c_longlong": ("long long", "arg_ll"), "c_long": ("long long", "arg_ll"),
+             "c_float": ("float", "arg_f"), "c_uint": ("unsigned int", "arg_u"), "c_void_p": ("void*", "arg_p")}
 
 
 def fastcall_source():
-    """C source of npvp_amd/_npvp_fast: one METH_FASTCALL wrapper per entry point of _lib.SIGNATURES that returns an int or a
-    long long.  ctypes converts every argument through its prototype machinery - 0.25 us per argument, 11 us for the 42 arguments
+    """C source of npvp_amd/_npvp_fast: one METH_FASTCALL wrapper per entry point of include/npvp_hip.h (as _lib parses it) that
+    returns an int or a long long.  The source includes the header and casts every argument to the parameter type declared there,
+    so the C++ compiler checks each call against the prototype the library itself was compiled against.
+    ctypes converts every argument through its prototype machinery - 0.25 us per argument, 11 us for the 42 arguments
     of npvp_gemm_f32, 7 - 8 ms of a host-bound 8-clip step's 36 ms; these wrappers read the same Python ints / floats / None with
     the C API (~30 ns per argument) and call the SAME exported function of libnpvp_hip.so.  Argument meaning, order and the
     return value are those of the header; a wrong argument count or type raises TypeError."""
@@ -91,7 +98,8 @@ def fastcall_source():
     spec = importlib.util.spec_from_file_location("_npvp_lib_sigs", os.path.join(HERE, "_lib.py"))
     mod = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(mod)
-    out = ["/* generated by npvp_amd/build.py from npvp_amd/_lib.py SIGNATURES - do not edit */", "#define PY_SSIZE_T_CLEAN", "#include <Python.h>", "",
+    out = ["/* generated by npvp_amd/build.py from include/npvp_hip.h - do not edit */", "#define PY_SSIZE_T_CLEAN", "#include <Python.h>",
+           "#include \"npvp_hip.h\"", "",
            "static inline int arg_ll(PyObject* o, long long* v) { *v = PyLong_AsLongLong(o); return !(*v == -1 && PyErr_Occurred()); }",
            "static inline int arg_u(PyObject* o, unsigned int* v) { unsigned long long t = PyLong_AsUnsignedLongLongMask(o); if (t == (unsigned long long)-1 && PyErr_Occurred()) return 0; *v = (unsigned int)t; return 1; }",
            "static inline int arg_f(PyObject* o, float* v) { double d = PyFloat_AsDouble(o); if (d == -1.0 && PyErr_Occurred()) return 0; *v = (float)d; return 1; }",
@@ -101,27 +109,16 @@ def fastcall_source():
     table = []
     for name, (res, args) in mod.SIGNATURES.items():
         rname = getattr(res, "__name__", "")
-        if rname not in ("c_int", "c_longlong", "c_long") or any(a.__name__ not in _C_TYPE for a in args):
+        if rname not in ("c_int", "c_longlong", "c_long"):
             continue
-        ctypes_ = [_C_TYPE[a.__name__] for a in args]
-        rt = _C_TYPE[rname][0]
-        out.append(f"extern \"C\" {rt} {name}({', '.join(t for t, _ in ctypes_) or 'void'});")
+        rt, ctexts = mod.PROTOTYPES[name]
         out.append(f"static PyObject* w_{name}(PyObject* self, PyObject* const* a, Py_ssize_t n) {{")
         out.append(f"  if (n != {len(args)}) {{ PyErr_Format(PyExc_TypeError, \"{name} takes {len(args)} arguments (%zd given)\", n); return NULL; }}")
         call = []
-        for i, (t, k) in enumerate(ctypes_):
-            if k == "L":
-                out.append(f"  long long v{i}; if (!arg_ll(a[{i}], &v{i})) return NULL;")
-                call.append(f"({t})v{i}")
-            elif k == "U":
-                out.append(f"  unsigned int v{i}; if (!arg_u(a[{i}], &v{i})) return NULL;")
-                call.append(f"v{i}")
-            elif k == "F":
-                out.append(f"  float v{i}; if (!arg_f(a[{i}], &v{i})) return NULL;")
-                call.append(f"v{i}")
-            else:
-                out.append(f"  void* v{i}; if (!arg_p(a[{i}], &v{i})) return NULL;")
-                call.append(f"v{i}")
+        for i, (t, arg) in enumerate(zip(ctexts, args)):
+            var, read = _ARG_READ[arg.__name__]
+            out.append(f"  {var} v{i}; if (!{read}(a[{i}], &v{i})) return NULL;")
+            call.append(f"({t})v{i}")
         out.append(f"  {rt} r;")
         out.append("  Py_BEGIN_ALLOW_THREADS")
         out.append(f"  r = {name}({', '.join(call)});")
@@ -153,7 +150,7 @@ def build_fastcall(verbose=True):
         return FAST
     with open(src, "w") as f:
         f.write(text)
-    cmd = ["g++", "-O2", "-fPIC", "-shared", "-std=c++17", f"-I{inc}", src, "-o", FAST, f"-L{HERE}", "-l:libnpvp_hip.so",
+    cmd = ["g++", "-O2", "-fPIC", "-shared", "-std=c++17", f"-I{inc}", f"-I{INCLUDE}", src, "-o", FAST, f"-L{HERE}", "-l:libnpvp_hip.so",
            "-Wl,-rpath,$ORIGIN"]          # (Python's own symbols come from the interpreter, as for every extension module)
     r = subprocess.run(cmd, capture_output=True, text=True)
     if r.returncode != 0:

@@ -5,7 +5,7 @@
 
 static thread_local char g_err[512] = "";
 
-extern "C" void npvp_set_error(const char* msg) {
+void npvp_set_error(const char* msg) {
   strncpy(g_err, msg ? msg : "", sizeof(g_err) - 1);
   g_err[sizeof(g_err) - 1] = 0;
 }

@@ -2,18 +2,18 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "npvp_hip.h"   // the C ABI (include/): every extern "C" definition of the library is compiled against its declaration
 
 #define NPVP_OK 0
 #define NPVP_ERR_ARG (-1)
 #define NPVP_ERR_LAUNCH (-2)
 #define NPVP_ERR_WORKSPACE (-3)
 
-// host side: record the last error string (thread local), see api.hip
-extern "C" void npvp_set_error(const char* msg);
+// host side: record the last error string (thread local), see api.hip.  Internal: C++ linkage, not part of the C ABI.
+void npvp_set_error(const char* msg);
 
 // diagnostics: every kernel this library launches goes through NPVP_LAUNCH, which counts it (npvp_launch_count, api.hip; one
 // relaxed atomic add per launch).  bench.py reads the counter around a step to put `launches_per_step` into its record.
-extern "C" long long npvp_launch_count(void);
 namespace npvp { extern long long g_launches; }
 #define NPVP_LAUNCH(...)                                                    \
   do {                                                                      \

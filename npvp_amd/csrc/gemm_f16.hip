@@ -792,7 +792,7 @@ extern "C" int npvp_split_weight_f16(const float* w, long long ld, int N, int K,
 }
 
 // ---- weight gradients whose split-K reduction rides in the NEXT weight-gradient launch (see include/npvp_hip.h) -------------------
-static_assert(sizeof(ReduceJob) == 64, "npvp_reduce_job_t (include/npvp_hip.h) mirrors this layout");
+static_assert(sizeof(ReduceJob) == sizeof(npvp_reduce_job_t), "npvp_reduce_job_t (include/npvp_hip.h) mirrors this layout");
 
 extern "C" int npvp_wgrad_f16_chainable(int M, int N, int K) {
   return (M % 4 == 0 && N % 4 == 0 && f16_wgrad_splits(M, N, K) > 1) ? 1 : 0;

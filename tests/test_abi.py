@@ -25,8 +25,97 @@ def test_header_symbols_exported(built):
     for n in sorted(names):
         assert hasattr(L, n), f"{n} declared in include/npvp_hip.h but not exported"
         assert n in SIGNATURES, f"{n} has no ctypes signature in npvp_amd/_lib.py"
-    assert set(SIGNATURES) <= names | {"npvp_set_error"}
+    assert set(SIGNATURES) <= names
     assert L.npvp_version() >= 100
+
+
+def _dynamic_defined_symbols(path):
+    """names of the dynamic defined symbols of a shared object, read with the binary tools of the hipcc in use: llvm-nm beside hipcc
+    or beside its clang; where the toolchain ships no llvm-nm, the llvm-readelf of the same directory"""
+    import shutil
+    import subprocess
+    from npvp_amd import build
+    hipcc = shutil.which(build._hipcc())
+    clang = subprocess.run([hipcc, "--print-prog-name=clang"], capture_output=True, text=True).stdout.strip()
+    dirs = [os.path.dirname(os.path.realpath(hipcc))] + ([os.path.dirname(os.path.realpath(clang))] if os.path.sep in clang else [])
+    for tool, args, defined in (("llvm-nm", ["-D", "--defined-only", "--format=posix"], lambda f: f[0] if len(f) >= 2 else None),
+                                ("llvm-readelf", ["--dyn-syms", "-W"],
+                                 lambda f: f[7].split("@")[0] if len(f) == 8 and f[0].rstrip(":").isdigit() and f[6] != "UND" else None)):
+        for d in dirs:
+            if os.path.exists(os.path.join(d, tool)):
+                out = subprocess.run([os.path.join(d, tool)] + args + [path], capture_output=True, text=True, check=True).stdout
+                return {n for n in (defined(line.split()) for line in out.splitlines()) if n}
+    raise AssertionError(f"neither llvm-nm nor llvm-readelf in {dirs}")
+
+
+def test_c_linkage_exports_are_exactly_the_header(built):
+    """The library's dynamic defined symbols that start with npvp_ (C linkage: C++-mangled names start with _Z and are not counted)
+    are the names include/npvp_hip.h declares - nothing internal leaks into the C export list, nothing declared is missing."""
+    from npvp_amd import _lib
+    exported = {n for n in _dynamic_defined_symbols(built) if n.startswith("npvp_")}
+    declared = set(_lib.PROTOTYPES)
+    assert len(declared) == len(_lib.SIGNATURES) >= 106
+    assert exported - declared == set(), "exported with C linkage but not declared in include/npvp_hip.h"
+    assert declared - exported == set(), "declared in include/npvp_hip.h but not exported"
+
+
+def test_header_parser_reads_comments_multiline_and_void():
+    import ctypes
+    from npvp_amd import _lib
+    protos = _lib.parse_header("""
+/* a header
+ * int npvp_in_a_comment(int x); */
+#ifndef X
+#define X
+#include <stddef.h>
+#ifdef __cplusplus
+extern "C" {
+#endif
+typedef struct ihipStream_t* npvp_stream_t; /* == hipStream_t */
+typedef struct npvp_rec { const float* a; int b, c; } npvp_rec_t;   /* plain data */
+int npvp_a(void);
+const char* npvp_b(void);  // trailing comment
+void* npvp_c(int* least,
+             int *greatest);
+float npvp_d(void* e0, void* e1);
+long long npvp_e(const float* x /* nullable */, long long rows, size_t n, unsigned int salt,
+                 const unsigned long long* seed, float p /* in [0, 1) */,
+                 npvp_stream_t stream);
+#ifdef __cplusplus
+}
+#endif
+#endif
+""")
+    assert protos == {"npvp_a": ("int", []), "npvp_b": ("const char*", []), "npvp_c": ("void*", ["int*", "int*"]),
+                      "npvp_d": ("float", ["void*", "void*"]),
+                      "npvp_e": ("long long", ["const float*", "long long", "size_t", "unsigned int", "const unsigned long long*", "float",
+                                               "npvp_stream_t"])}
+    sig = _lib.signatures(protos)
+    P = ctypes.c_void_p
+    # the four return kinds that stay with ctypes or are wrapped: int / long long, const char*, void*, float
+    assert sig["npvp_a"] == (ctypes.c_int, []) and sig["npvp_b"] == (ctypes.c_char_p, [])
+    assert sig["npvp_c"] == (P, [P, P]) and sig["npvp_d"] == (ctypes.c_float, [P, P])
+    assert sig["npvp_e"][0] is ctypes.c_longlong
+    assert all(x is y for x, y in zip(sig["npvp_e"][1], [P, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_uint, P, ctypes.c_float, P]))
+
+
+@pytest.mark.parametrize("proto, named", [
+    ("int npvp_x(double eps);", "double"),                       # a value type outside the map
+    ("int npvp_x(int n, unsigned long long seed);", "unsigned long long"),
+    ("double npvp_x(int n);", "double"),                         # ... as a return
+    ("float* npvp_x(int n);", "float*"),                         # a pointer return other than const char* / void*
+    ("npvp_stream_t npvp_x(void);", "npvp_stream_t"),
+    ("int npvp_x(int);", "int"),                                 # a parameter without a name
+    ("int npvp_x(int (*cb)(int));", "npvp_x"),                   # not `type name`
+    ("int npvp_x(int n)", "npvp_x"),                             # no terminating semicolon
+    ("int npvp_x(int n); int npvp_x(int n);", "npvp_x"),         # declared twice
+    ("int g_counter;", "g_counter"),                             # not a prototype
+])
+def test_header_parser_is_strict(proto, named):
+    """Whatever the type map or the prototype grammar does not cover raises at import and names the prototype or the type."""
+    from npvp_amd import _lib
+    with pytest.raises(RuntimeError, match=re.escape(named)):
+        _lib.signatures(_lib.parse_header(proto))
 
 
 def test_argument_errors_do_not_need_a_gpu(built):

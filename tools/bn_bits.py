@@ -12,32 +12,22 @@ import argparse
 import ctypes
 import hashlib
 import os
+import sys
 
 import torch                      # (before the library: both must use the HIP runtime that torch loads)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-P, LL, I, F = ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int, ctypes.c_float
+sys.path.insert(0, ROOT)
+from npvp_amd import _lib  # noqa: E402  (the argument types of include/npvp_hip.h; the library is the one --lib names)
 EPS, MOM = 1e-5, 0.1
 # (layout, C, H, W, frames of shard a, frames of shard b): SHAPES of tests/test_hip_ae_dp.py
 SHAPES = [(0, 4, 2, 2, 1, 2), (0, 64, 3, 3, 2, 3), (0, 32, 12, 12, 2, 3), (0, 512, 8, 8, 1, 2), (1, 64, 3, 4, 2, 3), (1, 512, 8, 8, 1, 2)]
-SIGNATURES = {
-    "npvp_bn_workspace_bytes": (I,),
-    "npvp_bn_stats": (P, LL, LL, I, I, P, P, LL, P),
-    "npvp_bn_act_apply": (P, P, P, P, P, LL, F, F, P, P, LL, LL, I, I, I, P, P, P, P),
-    "npvp_bn_act_bwd": (P, P, P, P, P, P, LL, LL, I, I, I, I, P, P, P, P, LL, P),
-    "npvp_bn_act_apply_sync": (P, P, P, P, P, F, F, P, P, LL, LL, I, I, I, P, P, P, P),
-    "npvp_bn_bwd_sums": (P, P, P, P, P, P, LL, LL, I, I, I, P, P, P, P, LL, P),
-    "npvp_bn_act_bwd_apply": (P, P, P, P, P, P, P, P, LL, LL, I, I, I, P, P),
-}
+ENTRY_POINTS = ("npvp_bn_workspace_bytes", "npvp_bn_stats", "npvp_bn_act_apply", "npvp_bn_act_bwd", "npvp_bn_act_apply_sync",
+                "npvp_bn_bwd_sums", "npvp_bn_act_bwd_apply", "npvp_last_error")
 
 
 def load(path):
-    L = ctypes.CDLL(path)
-    for name, args in SIGNATURES.items():
-        f = getattr(L, name)
-        f.restype, f.argtypes = I, args
-    L.npvp_last_error.restype = ctypes.c_char_p
-    return L
+    return _lib.bind(ctypes.CDLL(path), ENTRY_POINTS)
 
 
 def case(L, layout, C, H, W, n, act, with_res, train, seed):

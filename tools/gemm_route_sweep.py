@@ -12,8 +12,9 @@ import os
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "tests"))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
 import gemm_route_cases as T  # noqa: E402
+from npvp_amd import _lib  # noqa: E402  (the argument types of include/npvp_hip.h; the library is the one --lib names)
 
 
 def around(values):
@@ -38,8 +39,7 @@ def main():
     ap.add_argument("--lib", default=os.path.join(ROOT, "npvp_amd", "libnpvp_hip.so"))
     ap.add_argument("--dump", help="write one line per tuple to this file")
     a = ap.parse_args()
-    L = ctypes.CDLL(a.lib)
-    L.npvp_gemm_workspace_bytes.restype = ctypes.c_longlong
+    L = _lib.bind(ctypes.CDLL(a.lib), ("npvp_gemm_workspace_bytes",))
     ms, ns, ks = lattice()
     out = (ctypes.c_int * 4)()
     ref = ctypes.byref(out)

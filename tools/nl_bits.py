@@ -15,15 +15,15 @@ import ast
 import ctypes
 import hashlib
 import os
+import sys
 
 import torch                      # (before the library: both must use the HIP runtime that torch loads)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-P, LL, I = ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int
+sys.path.insert(0, ROOT)
+from npvp_amd import _lib  # noqa: E402  (the argument types of include/npvp_hip.h; the library is the one --lib names)
 FRAMES = 2
 CONFIG_SHAPES = [(64, 64, 64), (128, 32, 32), (256, 16, 16), (512, 8, 8)]          # (C, H, W)
-FWD = (P, LL, P, LL, P, LL, P, LL, P, I, I, I, I, I, P)
-BWD = (P, LL, P, LL, P, LL, P, LL, P, P, P, LL, P, LL, P, LL, I, I, I, I, I, P)
 
 
 def grid_shapes():
@@ -35,13 +35,8 @@ def grid_shapes():
 
 
 def load(path):
-    L = ctypes.CDLL(path)
-    for stem in ("npvp_nonlocal_attn", "npvp_nonlocal_attn_grid"):
-        for pas, args in (("_fwd", FWD), ("_bwd", BWD)):
-            f = getattr(L, stem + pas)
-            f.restype, f.argtypes = I, args
-    L.npvp_last_error.restype = ctypes.c_char_p
-    return L
+    return _lib.bind(ctypes.CDLL(path), ("npvp_nonlocal_attn_fwd", "npvp_nonlocal_attn_bwd", "npvp_nonlocal_attn_grid_fwd",
+                                         "npvp_nonlocal_attn_grid_bwd", "npvp_last_error"))
 
 
 def case(L, stem, C, H, W, seed):

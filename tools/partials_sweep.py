@@ -16,25 +16,21 @@ import ctypes
 import hashlib
 import os
 import struct
+import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from npvp_amd import _lib  # noqa: E402  (the argument types of include/npvp_hip.h; the library is the one --lib names)
 RECORD = "<QQQiiiiii"                       # in, out, out_b, nb, stride, ncols, split, accum, mode
 WS, OUT, OUT_B = 0x7f0000000000, 0x7e0000000000, 0x7d0000000000          # made-up 16-byte aligned addresses: never dereferenced
-P, LL, I = ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int
 
 
 def load(path):
-    L = ctypes.CDLL(path)
-    for name, res, args in (("npvp_layernorm_bwd_workspace_bytes", LL, (LL, I)), ("npvp_frameln_act_bwd_workspace_bytes", LL, (I, I)),
-                            ("npvp_mlpdw_mid_bwd_workspace_bytes", LL, (I, I)), ("npvp_dwconv3x3_wgrad_workspace_bytes", LL, (I, I)),
-                            ("npvp_layernorm_bwd_reduce_job", I, (P, P, P, LL, I, I, P)), ("npvp_frameln_act_bwd_reduce_job", I, (P, P, P, I, I, I, P)),
-                            ("npvp_mlpdw_mid_bwd_reduce_job", I, (P, P, P, I, I, P)),
-                            ("npvp_layernorm_bwd_reduce", I, (P, P, P, LL, I, I, P)), ("npvp_frameln_act_bwd_reduce", I, (P, P, P, I, I, I, P)),
-                            ("npvp_mlpdw_mid_bwd_reduce", I, (P, P, I, I, I, P)), ("npvp_mlpdw_mid_bwd_reduce_into", I, (P, P, P, I, I, P)),
-                            ("npvp_sum_rows_multi", I, (P, I, P))):
-        f = getattr(L, name)
-        f.restype, f.argtypes = res, args
-    return L
+    return _lib.bind(ctypes.CDLL(path), (
+        "npvp_layernorm_bwd_workspace_bytes", "npvp_frameln_act_bwd_workspace_bytes", "npvp_mlpdw_mid_bwd_workspace_bytes",
+        "npvp_dwconv3x3_wgrad_workspace_bytes", "npvp_layernorm_bwd_reduce_job", "npvp_frameln_act_bwd_reduce_job",
+        "npvp_mlpdw_mid_bwd_reduce_job", "npvp_layernorm_bwd_reduce", "npvp_frameln_act_bwd_reduce", "npvp_mlpdw_mid_bwd_reduce",
+        "npvp_mlpdw_mid_bwd_reduce_into", "npvp_sum_rows_multi"))
 
 
 def around(values, d=(-1, 0, 1)):
