@@ -366,6 +366,12 @@ inline int wide_wgrad_splits(int M, int N, int K) { return wgrad_splits(M, N, K,
 // weight gradient.
 inline int f16_wgrad_splits(int M, int N, int K) { return wgrad_splits(M, N, K, 1024); }
 
+// a row-group mask on the rows of A (GemmParams::adrop) as an entry point may ask for it: p in [0, 0.5) - the masked operand must stay
+// inside its amax scale -, and with p > 0 a device seed and whole groups (rows16: of a multiple of 16 rows - a weight gradient's K-steps)
+inline bool adrop_args_ok(float p, int g1, int g2, const unsigned long long* seed, bool rows16) {
+  return p >= 0.f && p < 0.5f && (p == 0.f || (seed && g1 > 0 && g2 > 0 && (!rows16 || g1 % 16 == 0)));
+}
+
 // The launchers run what the planner of gemm.hip (plan_gemm) chose: they set p.tiles_* / p.colgroups for their tiles and launch.
 // gemm_wide.hip: 128 x 256 (variant 1) or 128 x 128 (variant 2) tiles, 4 waves, A = fp32 [M][K] split on the fly, B = pre-split planes
 int wide_variant(int M, int N, int K);           // 0 not taken (the 128 x 128 gemm_split_db_kernel runs)

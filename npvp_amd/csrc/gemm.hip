@@ -643,7 +643,7 @@ extern "C" int npvp_gemm_f32(int a_kc, int b_kc, int M, int N, int K, const floa
 
   // row-group mask on operand A (see GemmParams::adrop): only the fp16 kernels implement it, and only with whole K-steps per group
   NPVP_CHECK_ARG(adrop_p >= 0.f && adrop_p < 0.5f, "gemm: adrop_p must be in [0, 0.5) (the masked operand must stay inside its amax scale)");
-  NPVP_CHECK_ARG(adrop_p == 0.f || (seed && want_h && adrop_g1 > 0 && adrop_g2 > 0 && (a_kc || adrop_g1 % 16 == 0)),
+  NPVP_CHECK_ARG(adrop_p == 0.f || (want_h && adrop_args_ok(adrop_p, adrop_g1, adrop_g2, seed, !a_kc)),
                  "gemm: adrop needs precision 6, a device seed and (for a weight gradient) groups of a multiple of 16 rows");
   NPVP_CHECK_ARG(!rowstats || ((precision == 4 || want_h) && a_kc && b_kc && M % 64 == 0 && N % 128 == 0 && act == 0 && !aux_out && !residual &&
                                drop_p == 0.f && !accumulate),

@@ -19,6 +19,7 @@
 // per CU) with two planes per operand: 24.8 KB per stage instead of 36.4, 24 MFMAs and ~20 VALU of splitting per wave and
 // K-step instead of 48 and ~60.
 #include "gemm.h"
+#include <cstdio>
 #include <cstdlib>
 
 namespace npvp {
@@ -620,13 +621,50 @@ static int reduce_rows_for(const ReduceJob& j, int tiles) {
   return (int)((want + tiles - 1) / tiles);
 }
 
-void launch_gemm_wgrad_f16(GemmParams& p, hipStream_t stream) {
+// the grid of gemm_wgrad_f16_body for p: x = its 128 x 256 tiles, y = p's splits + the rows that reduce p.prev; sets p.tiles_* / p.prev.blocks
+static dim3 size_gemm_wgrad_f16(GemmParams& p) {
   p.tiles_m = (p.M + 127) / 128;
   p.tiles_n = (p.N + 255) / 256;
   const int tiles = p.tiles_m * p.tiles_n, rr = reduce_rows_for(p.prev, tiles);
   p.prev.blocks = rr * tiles;
-  dim3 grid(tiles, p.splits + rr), block(256);
-  NPVP_LAUNCH((gemm_wgrad_f16_kernel<2, 4, 2, 2>), grid, block, 0, stream, p);
+  return dim3(tiles, p.splits + rr);
+}
+
+void launch_gemm_wgrad_f16(GemmParams& p, hipStream_t stream) {
+  const dim3 grid = size_gemm_wgrad_f16(p);
+  NPVP_LAUNCH((gemm_wgrad_f16_kernel<2, 4, 2, 2>), grid, dim3(256), 0, stream, p);
+}
+
+// ---- a weight gradient whose split-K reduction runs LATER (npvp_wgrad_f16_chained, npvp_linear_bwd_f16): the argument rules the two
+// entry points share (`who` names the entry point in the error text), the problem, the record of its reduction
+static bool deferred_wgrad_args_ok(const char* who, const float* dy, long long lda, const float* x, long long ldb, const float* dw, long long ldc, float adrop_p,
+                                   int adrop_g1, int adrop_g2, const unsigned long long* seed, const void* workspace, long long ws_bytes, long long ws_need) {
+  const char* what = ((((uintptr_t)dy | (uintptr_t)x | (uintptr_t)dw) & 15) || ((lda | ldb | ldc) & 3)) ? "operands must be 16-byte aligned with leading dimensions that are multiples of 4"
+                     : !adrop_args_ok(adrop_p, adrop_g1, adrop_g2, seed, true) ? "adrop needs a device seed and groups of a multiple of 16 rows"
+                     : (!workspace || ws_bytes < ws_need) ? "workspace too small" : nullptr;
+  char msg[192];
+  if (what) { snprintf(msg, sizeof(msg), "%s: %s", who, what); npvp_set_error(msg); }
+  return !what;
+}
+
+// dw[M][N] (+)= dy[K][M]^T x[K][N] on the fp16 kernel, its split-K slabs (and column sums) left in `workspace`; prev_job rides along
+static GemmParams deferred_wgrad_params(int M, int N, int K, const float* dy, long long lda, const float* x, long long ldb, const float* a_amax, const float* b_amax,
+                                        unsigned int* range_flag, const DropSpec& adrop, const unsigned long long* seed, const void* prev_job, void* workspace,
+                                        bool want_db, int accumulate) {
+  GemmParams p = {};
+  p.A = dy; p.B = x; p.lda = lda; p.ldb = ldb; p.M = M; p.N = N; p.alpha = 1.f;
+  p.splits = f16_wgrad_splits(M, N, K); p.colgroups = 1; p.accum = accumulate ? 1 : 0;
+  aim_at_workspace(p, K, p.splits, workspace, want_db);
+  p.seed = seed; p.drop = make_drop_spec(0.f, 0u, 0, 1, 1); p.adrop = adrop;
+  p.a_amax = a_amax; p.b_amax = b_amax; p.range_flag = range_flag;
+  if (prev_job) p.prev = *reinterpret_cast<const ReduceJob*>(prev_job);
+  return p;
+}
+
+// the record of p's own reduction, for whoever runs it: dw (+)= the sum of the slabs, db (+)= the sum of the column sums
+static void leave_reduce_job(const GemmParams& p, float* dw, long long ldc, float* db, void* my_job) {
+  const ReduceJob mine = {(const float*)p.C, dw, ldc, p.M, p.N, p.splits, p.accum, 1.f, 0, p.colsum, db};
+  *reinterpret_cast<ReduceJob*>(my_job) = mine;
 }
 
 // forward / dgrad with scaled fp16 planes: 1 = 128 x 256 tiles, 2 = 128 x 128 tiles (outputs that 128 x 256 tiles do not
@@ -810,26 +848,14 @@ extern "C" int npvp_wgrad_f16_chained(int M, int N, int K, const float* dy, long
                                       long long ws_bytes, hipStream_t stream) {
   NPVP_CHECK_ARG(npvp_wgrad_f16_chainable(M, N, K), "wgrad_f16_chained: shape not taken (npvp_wgrad_f16_chainable tells)");
   NPVP_CHECK_ARG(dy && x && dw && a_amax && b_amax && my_job, "wgrad_f16_chained: null operand / amax slot / job");
-  NPVP_CHECK_ARG(((uintptr_t)dy % 16) == 0 && ((uintptr_t)x % 16) == 0 && ((uintptr_t)dw % 16) == 0 && lda % 4 == 0 && ldb % 4 == 0 && ldc % 4 == 0,
-                 "wgrad_f16_chained: operands must be 16-byte aligned with leading dimensions that are multiples of 4");
+  if (!deferred_wgrad_args_ok("wgrad_f16_chained", dy, lda, x, ldb, dw, ldc, adrop_p, adrop_g1, adrop_g2, seed, workspace, ws_bytes,
+                              npvp_wgrad_f16_chain_workspace_bytes(M, N, K))) return NPVP_ERR_ARG;
   NPVP_CHECK_ARG(!db || ((uintptr_t)db % 16) == 0, "wgrad_f16_chained: the bias gradient must be 16-byte aligned");
-  NPVP_CHECK_ARG(workspace && ws_bytes >= npvp_wgrad_f16_chain_workspace_bytes(M, N, K), "wgrad_f16_chained: workspace too small");
-  NPVP_CHECK_ARG(adrop_p >= 0.f && adrop_p < 0.5f && (adrop_p == 0.f || (seed && adrop_g1 > 0 && adrop_g2 > 0 && adrop_g1 % 16 == 0)),
-                 "wgrad_f16_chained: adrop needs a device seed and groups of a multiple of 16 rows");
-  const int sh = f16_wgrad_splits(M, N, K);
-  GemmParams p = {};
-  p.A = dy; p.B = x; p.lda = lda; p.ldb = ldb; p.M = M; p.N = N; p.alpha = 1.f;
-  p.splits = sh; p.colgroups = 1; p.accum = accumulate ? 1 : 0;
-  aim_at_workspace(p, K, sh, workspace, db != nullptr);
-  p.seed = seed;
-  p.drop = make_drop_spec(0.f, 0u, 0, 1, 1);
-  p.adrop = make_drop_spec(adrop_p, adrop_salt, 1, adrop_g1, adrop_g2);
-  p.a_amax = a_amax; p.b_amax = b_amax; p.range_flag = range_flag;
-  if (prev_job) p.prev = *reinterpret_cast<const ReduceJob*>(prev_job);
+  GemmParams p = deferred_wgrad_params(M, N, K, dy, lda, x, ldb, a_amax, b_amax, range_flag, make_drop_spec(adrop_p, adrop_salt, 1, adrop_g1, adrop_g2),
+                                       seed, prev_job, workspace, db != nullptr, accumulate);
   launch_gemm_wgrad_f16(p, stream);
   NPVP_CHECK_LAUNCH();
-  ReduceJob mine = {(const float*)workspace, dw, ldc, M, N, sh, accumulate ? 1 : 0, 1.f, 0, p.colsum, db};
-  *reinterpret_cast<ReduceJob*>(my_job) = mine;
+  leave_reduce_job(p, dw, ldc, db, my_job);
   return NPVP_OK;
 }
 
@@ -848,16 +874,14 @@ extern "C" int npvp_linear_bwd_f16(int R, int N, int K, const float* dy, long lo
                                    long long ws_bytes, hipStream_t stream) {
   NPVP_CHECK_ARG(npvp_linear_bwd_f16_takes(R, N, K), "linear_bwd_f16: shape not taken (npvp_linear_bwd_f16_takes tells)");
   NPVP_CHECK_ARG(dy && dy_amax && w_planes_d && w_amax && dx && x && x_amax && dw && my_job, "linear_bwd_f16: null operand / amax slot / job");
-  NPVP_CHECK_ARG(((uintptr_t)dy % 16) == 0 && ((uintptr_t)x % 16) == 0 && ((uintptr_t)dw % 16) == 0 && ((uintptr_t)dx % 16) == 0 &&
-                 ((uintptr_t)w_planes_d % 16) == 0 && ldy % 4 == 0 && ldxx % 4 == 0 && ldw % 4 == 0 && ldx % 4 == 0,
+  if (!deferred_wgrad_args_ok("linear_bwd_f16", dy, ldy, x, ldxx, dw, ldw, adrop_p, adrop_g1, adrop_g2, seed, workspace, ws_bytes,
+                              npvp_wgrad_f16_chain_workspace_bytes(N, K, R))) return NPVP_ERR_ARG;
+  NPVP_CHECK_ARG(((uintptr_t)dx % 16) == 0 && ((uintptr_t)w_planes_d % 16) == 0 && ldx % 4 == 0,
                  "linear_bwd_f16: operands must be 16-byte aligned with leading dimensions that are multiples of 4");
   NPVP_CHECK_ARG((!db || ((uintptr_t)db % 16) == 0) && (!residual || (((uintptr_t)residual % 16) == 0 && ldr % 4 == 0)) &&
                  (!aux_in || ((uintptr_t)aux_in % 16) == 0), "linear_bwd_f16: db / residual / aux_in must be 16-byte aligned");
   NPVP_CHECK_ARG(act == 0 || ((act == 3 || act == 4) && aux_in), "linear_bwd_f16: act must be 0, or 3 / 4 with aux_in");
   NPVP_CHECK_ARG(drop_p >= 0.f && drop_p < 1.f && (drop_p == 0.f || seed), "linear_bwd_f16: dropout p out of range or no seed");
-  NPVP_CHECK_ARG(adrop_p >= 0.f && adrop_p < 0.5f && (adrop_p == 0.f || (seed && adrop_g1 > 0 && adrop_g2 > 0 && adrop_g1 % 16 == 0)),
-                 "linear_bwd_f16: adrop needs a device seed and groups of a multiple of 16 rows");
-  NPVP_CHECK_ARG(workspace && ws_bytes >= npvp_wgrad_f16_chain_workspace_bytes(N, K, R), "linear_bwd_f16: workspace too small");
   GemmGroup g = {};
   // problem 0: dx[R][K] = epilogue((mask) dy[R][N] . W[N][K])  - what npvp_gemm_f32(a_kc = 1, b_kc = 0, M = R, N = K, K = N) builds
   GemmParams& d = g.p[0];
@@ -867,38 +891,26 @@ extern "C" int npvp_linear_bwd_f16(int R, int N, int K, const float* dy, long lo
   d.adrop = make_drop_spec(adrop_p, adrop_salt, 1, adrop_g1, adrop_g2);
   d.b_pre = w_planes_d; d.b_pre_plane = (long long)N * K;
   d.a_amax = dy_amax; d.b_amax = w_amax; d.c_amax = dx_amax;
-  // problem 1: dW[N][K] (+)= dy^T x over R rows, split-K, reduction handed to the next launch (npvp_wgrad_f16_chained)
-  const int sh = f16_wgrad_splits(N, K, R);
+  // problem 1: dW[N][K] += dy^T x over R rows, split-K, reduction handed to a later launch (as npvp_wgrad_f16_chained)
+  GemmParams& w = g.p[1] = deferred_wgrad_params(N, K, R, dy, ldy, x, ldxx, dy_amax, x_amax, range_flag, d.adrop, seed, prev_job, workspace, db != nullptr, 1);
+  const dim3 wgrid = size_gemm_wgrad_f16(w);
   // the dgrad's tiles: 64 x 128 where the launch then still fits the chip's 512 workgroup slots with the weight gradient's
   // workgroups beside it, else 128 x 128 (8 192 rows: 256 + 256 workgroups in one round beat 512 + 256 in one and a half -
   // profiles/r05_linear_bwd_bench.txt)
-  const int t128 = ((R + 127) / 128) * ((K + 127) / 128), wwg = ((N + 127) / 128) * ((K + 255) / 256) * sh;
+  const int t128 = ((R + 127) / 128) * ((K + 127) / 128), wwg = (int)wgrid.x * w.splits;
   int v = gemm_f16_variant(R, K, N);                     // 2, 3 or 4 (npvp_linear_bwd_f16_takes)
   if (v == 4 && 2 * t128 + wwg > 512) v = 2;
   prep_gemm_f16(d, v);
-  GemmParams& w = g.p[1];
-  w.A = dy; w.B = x; w.lda = ldy; w.ldb = ldxx; w.M = N; w.N = K; w.alpha = 1.f;
-  w.splits = sh; w.colgroups = 1; w.accum = 1;
-  aim_at_workspace(w, R, sh, workspace, db != nullptr);
-  w.seed = seed;
-  w.drop = make_drop_spec(0.f, 0u, 0, 1, 1);
-  w.adrop = d.adrop;
-  w.a_amax = dy_amax; w.b_amax = x_amax; w.range_flag = range_flag;
-  if (prev_job) w.prev = *reinterpret_cast<const ReduceJob*>(prev_job);
-  w.tiles_m = (N + 127) / 128; w.tiles_n = (K + 255) / 256;
-  const int tiles = w.tiles_m * w.tiles_n, rr = reduce_rows_for(w.prev, tiles);
-  w.prev.blocks = rr * tiles;
   g.count[0] = d.tiles_m * d.tiles_n;
   g.first[0] = 0; g.first[1] = (g.count[0] + 7) & ~7;
-  g.count[1] = tiles * (sh + rr);
+  g.count[1] = wgrid.x * wgrid.y;
   g.first[2] = g.first[1] + ((g.count[1] + 7) & ~7);
-  g.gx = tiles;
+  g.gx = wgrid.x;
   if (v == 2) NPVP_LAUNCH((gemm_f16_group_kernel<2, 2>), dim3(g.first[2]), dim3(256), 0, stream, g);
   else if (v == 4) NPVP_LAUNCH((gemm_f16_group_kernel<1, 2>), dim3(g.first[2]), dim3(256), 0, stream, g);
   else NPVP_LAUNCH((gemm_f16_group_kernel<2, 1>), dim3(g.first[2]), dim3(256), 0, stream, g);
   NPVP_CHECK_LAUNCH();
-  ReduceJob mine = {(const float*)workspace, dw, ldw, N, K, sh, 1, 1.f, 0, w.colsum, db};
-  *reinterpret_cast<ReduceJob*>(my_job) = mine;
+  leave_reduce_job(w, dw, ldw, db, my_job);
   return NPVP_OK;
 }
 

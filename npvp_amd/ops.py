@@ -3,8 +3,9 @@ the current HIP stream and the autograd graph; every piece of arithmetic on the 
 a hand-written gfx950 kernel reached through ctypes.  There is no CPU / eager fallback:
 tensors must be fp32 CUDA(ROCm) tensors and the library must be built.
 """
-import ctypes
+import functools
 import os
+from collections import namedtuple
 
 import torch
 
@@ -12,7 +13,7 @@ from ._lib import lib, check
 # scheduling state (per trainer: sched.StepContext) and the process-wide pieces beside it; re-exported here because the rest of the
 # package, the tests and the tools reach them as ops.<name>
 from . import sched as _S            # (hot paths read the current context as _S._cur.<field>: one global + two attribute loads)
-from .sched import (_p, _ptr, _stream, _ws, AmaxSlot, GemmProbe, HbmProbe, ProbeEvent, probe_pair, AuxStream, StepContext, current, use, scoped,
+from .sched import (_p, _ptr, _stream, _ws, AmaxSlot, GemmProbe, HbmProbe, ProbeEvent, AuxStream, StepContext, current, use, scoped,
                     remember, rng, GradSink, WgradStream, WgradChain, ReduceQueue, RangeGuard)
 
 
@@ -358,12 +359,10 @@ def gemm(a_kc, b_kc, M, N, K, A, lda, B, ldb, out, bias=None, act=0, aux_in=None
         DropRecorder.note(drop, "elem" if drop.mode == 0 else "group", M * N if drop.mode == 0 else drop.g2)
     # every launch is timed on the stream it runs on, also those that share the device with a kernel of another stream:
     # the population (and the average duration) is then the same as in a rocprofv3 kernel trace of the same command
-    probe = GemmProbe.armed
-    if probe:
+    pe = None
+    if GemmProbe.armed:
         kid = _gemm_kernel_id(a_kc, b_kc, M, N, K, prec, planes is not None)
-        probe = GemmProbe.only is None or kid in GemmProbe.only
-    if probe:
-        e0, e1 = probe_pair()
+        pe = GemmProbe.begin(kid)
     rc = lib().npvp_gemm_f32(
         a_kc, b_kc, M, N, K, A.data_ptr(), lda, B.data_ptr(), ldb, out.data_ptr(), out.stride(0),
         None if bias is None else bias.data_ptr(), act, None if aux_in is None else aux_in.data_ptr(),
@@ -376,29 +375,20 @@ def gemm(a_kc, b_kc, M, N, K, A, lda, B, ldb, out, bias=None, act=0, aux_in=None
         a_drop.p, a_drop.g1, a_drop.g2, a_drop.salt, None if ws is None else ws.data_ptr(), wsn, _stream())
     if rc:
         check(rc, "npvp_gemm_f32")
-    if probe:
-        e1.record()
-        GemmProbe.records.append((e0, e1, 2.0 * M * N * K, 4.0 * (M * K + N * K + M * N), ((a_kc, b_kc), kid)))
+    if pe is not None:
+        GemmProbe.end(pe, 2.0 * M * N * K, 4.0 * (M * K + N * K + M * N), (a_kc, b_kc), kid)
     return out
 
 
-_KID_CACHE, _WSB_CACHE = {}, {}
-
-
+@functools.lru_cache(maxsize=None)
 def _gemm_kernel_id(a_kc, b_kc, M, N, K, prec, has_planes):
     """npvp_gemm_kernel_id, remembered per shape (a pure function of its arguments; one C call less per GEMM)"""
-    key = (a_kc, b_kc, M, N, K, prec, has_planes)
-    v = _KID_CACHE.get(key)
-    if v is None:
-        v = _KID_CACHE[key] = lib().npvp_gemm_kernel_id(a_kc, b_kc, M, N, K, prec, int(has_planes))
-    return v
+    return lib().npvp_gemm_kernel_id(a_kc, b_kc, M, N, K, prec, int(has_planes))
 
 
+@functools.lru_cache(maxsize=None)
 def _gemm_ws_bytes(M, N, K):
-    v = _WSB_CACHE.get((M, N, K))
-    if v is None:
-        v = _WSB_CACHE[(M, N, K)] = lib().npvp_gemm_workspace_bytes(M, N, K)
-    return v
+    return lib().npvp_gemm_workspace_bytes(M, N, K)
 
 
 def _planes(w, want, R):
@@ -408,6 +398,60 @@ def _planes(w, want, R):
 def _new_slot(dev, want=True):
     """a fresh amax slot for a tensor a kernel is about to produce, when the GEMM mode uses them"""
     return AmaxSlot.new(dev) if (want and GEMM_PRECISION == 6) else None
+
+
+# --------------------------------------------------------------------------- linear backward: the plan
+# Where the weight gradient of y = x w^T + b goes is decided once each: by `linear_bwd_plan` when the layer's backward runs, by
+# `wgrad_plan` when the weight-gradient launch is enqueued (possibly later, inside WgradStream.flush).  Pure functions of shapes
+# (R token rows: dy [R, N], x [R, K], dw [N, K]) and plain facts, remembered per argument tuple; the callers read tensors and context.
+def _sunk(sk, want_b):
+    """a sink exists and takes exactly the gradients wanted (it has a bias slot iff there is a bias gradient)"""
+    return bool(sk) and want_b == (sk[1] is not None)
+
+
+def _h16(N, K, R, precision):
+    """the fp16 weight-gradient kernel takes this shape: its operands need amax slots, its launch watches the range flag"""
+    return precision == 6 and _gemm_kernel_id(0, 0, N, K, R, 6, False) == 6
+
+
+LinearBwdPlan = namedtuple("LinearBwdPlan", "fused reduction sunk on_grad_stream urgent fill_slots")
+WgradPlan = namedtuple("WgradPlan", "route precision watch")
+
+
+@functools.lru_cache(maxsize=None)
+def linear_bwd_plan(R, N, K, precision, sunk, grad_stream, guard_quiet=True, unit_strides=True, planes=False, fused_on=False,
+                    fused_with_stream=False, max_rows=0):
+    """fused: dgrad + weight gradient in ONE launch (FusedLinearBwd), its split-K `reduction` "chained" or "queued".  Else two launches,
+    the weight gradient `sunk` or returned; sunk `on_grad_stream` as a closure (`urgent`: flushed at once) or here, with `fill_slots`
+    after its operands' amax slots were filled on the CURRENT stream (the gradient stream is ordered after this one: a slot first
+    filled there would be read here unordered).  guard_quiet: the range guard is neither in fallback nor strict; unit_strides: of dy,
+    x and the weight-gradient slice; planes: the weight has D-planes; fused_on, fused_with_stream, max_rows: FusedLinearBwd's knobs."""
+    if (fused_on and precision == 6 and sunk and R <= max_rows and (fused_with_stream or not grad_stream) and guard_quiet
+            and unit_strides and planes and lib().npvp_linear_bwd_f16_takes(R, N, K) and WgradChain.takes(N, K, R)):
+        return LinearBwdPlan(True, "queued" if grad_stream else "chained", False, False, False, False)
+    on_side = sunk and grad_stream
+    return LinearBwdPlan(False, None, sunk, on_side, on_side and 2.0 * R * N * K >= 3e10, sunk and _h16(N, K, R, precision))
+
+
+@functools.lru_cache(maxsize=None)
+def wgrad_plan(N, K, R, precision, wgrad_precision, accumulate, masked, fallback, strict, in_flush, grad_stream, listener,
+               chain_on, unit_strides):
+    """route "strict" (scratch result, poll, one bf16x6 retry), "chained" (npvp_wgrad_f16_chained) or "gemm" with `precision` passed down
+    (None, 4, WGRAD_PRECISION); watch: the launch raises the range flag.  accumulate: into a sink slice; masked: a row-group mask rides
+    in the launch (it needs the fp16 kernel: it stays there); listener: a data-parallel one is set.  Chained: on the gradient stream
+    (in_flush), or - without one (the single-stream step that is captured into a graph) - on the current stream, where the pending
+    reduction rides in the next weight-gradient or fused launch and ReduceQueue.finish() runs the last one.  Not without a gradient
+    stream under data parallelism: a bucket's all-reduce must not overtake a reduction that is not enqueued yet."""
+    prec = wgrad_precision if precision == 4 else None
+    watch = _h16(N, K, R, precision)
+    if watch and fallback and not masked:
+        prec, watch = 4, False
+    if watch and strict and not masked:
+        return WgradPlan("strict", None, True)
+    if (watch and accumulate and prec is None and chain_on and WgradChain.takes(N, K, R)
+            and (in_flush or (not grad_stream and not listener)) and unit_strides):
+        return WgradPlan("chained", None, True)
+    return WgradPlan("gemm", prec, watch)
 
 
 def linear_fwd(x, w, b, act=0, aux_out=None, residual=None, drop=NO_DROP, rowstats=None, x_amax=None, y_amax=None):
@@ -445,8 +489,7 @@ def masked_grad(dy2, drop, w):
     R, N = dy2.shape
     K = w.shape[1]
     if (drop.mode == 1 and drop.g1 % 16 == 0 and drop.p < 0.5 and GEMM_PRECISION == 6 and R <= DROP_PATH_IN_GEMM_ROWS
-            and _planes(w, "D", R) is not None and _gemm_kernel_id(1, 0, R, K, N, 6, True) in (5, 7)
-            and _gemm_kernel_id(0, 0, N, K, R, 6, False) == 6):
+            and _planes(w, "D", R) is not None and _gemm_kernel_id(1, 0, R, K, N, 6, True) in (5, 7) and _h16(N, K, R, 6)):
         return dy2, drop
     return drop_apply(dy2, drop), NO_DROP
 
@@ -468,18 +511,18 @@ def linear_wgrad(dy, x, with_bias_grad=False, into=None, into_b=None, dy_amax=No
     acc = into is not None
     dw = into if acc else torch.empty(N, K, dtype=torch.float32, device=dy.device)
     db = (into_b if acc else torch.empty(N, dtype=torch.float32, device=dy.device)) if with_bias_grad else None
-    prec = WGRAD_PRECISION if GEMM_PRECISION == 4 else None
-    watch = GEMM_PRECISION == 6 and _gemm_kernel_id(0, 0, N, K, R, 6, False) == 6
-    if watch and _S._cur.range_guard.fallback and not a_drop.on:
-        prec, watch = 4, False                     # (a launch that carries a row-group mask needs the fp16 kernel: it stays there)
-    if watch and _S._cur.range_guard.strict and not a_drop.on:
-        # strict: into a scratch result first, so that a flagged launch leaves the accumulation target untouched
-        flag = _S._cur.range_guard.flag(dy.device)
+    c = _S._cur
+    g = c.range_guard
+    plan = wgrad_plan(N, K, R, GEMM_PRECISION, WGRAD_PRECISION, acc, a_drop.on, g.fallback, g.strict, c.wgrad.in_flush, c.wgrad.enabled,
+                      c.grad_sink.listener is not None, c.chain.enabled, dy.stride(1) == 1 and x.stride(1) == 1 and dw.stride(1) == 1)
+    flag = g.flag(dy.device) if plan.watch else None
+    if plan.route == "strict":
+        # into a scratch result first, so that a flagged launch leaves the accumulation target untouched
         tw = torch.empty(N, K, dtype=torch.float32, device=dy.device)
         tb = torch.empty(N, dtype=torch.float32, device=dy.device) if with_bias_grad else None
         gemm(0, 0, N, K, R, dy, dy.stride(0), x, x.stride(0), tw, colsum_a=tb, a_amax=dy_amax, b_amax=x_amax, range_flag=flag)
-        if _S._cur.range_guard.poll(dy.device):
-            _S._cur.range_guard.fallback = False             # (strict mode repairs launch by launch)
+        if g.poll(dy.device):
+            g.fallback = False             # (strict mode repairs launch by launch)
             gemm(0, 0, N, K, R, dy, dy.stride(0), x, x.stride(0), tw, colsum_a=tb, precision=4)
         if acc:
             dw.add_(tw)
@@ -487,31 +530,19 @@ def linear_wgrad(dy, x, with_bias_grad=False, into=None, into_b=None, dy_amax=No
                 db.add_(tb)
         else:
             dw, db = tw, tb
-        return (dw, db) if with_bias_grad else dw
-    flag = _S._cur.range_guard.flag(dy.device) if watch else None
-    # chained: on the gradient stream, or - without one (the single-stream step that is captured into a graph) - on the current stream,
-    # where the pending reduction rides in the next weight-gradient or fused launch and ReduceQueue.finish() runs the last one.  Not
-    # without a gradient stream under data parallelism: a bucket's all-reduce must not overtake a reduction that is not enqueued yet.
-    on_side = _S._cur.wgrad.in_flush
-    if (watch and acc and prec is None and _S._cur.chain.enabled and _S._cur.chain.takes(N, K, R)
-            and (on_side or (not _S._cur.wgrad.enabled and _S._cur.grad_sink.listener is None))
-            and dy.stride(1) == 1 and x.stride(1) == 1 and dw.stride(1) == 1):
-        _S._cur.chain.launch(dy, x, dw, db, amax_of(dy, dy_amax), amax_of(x, x_amax), a_drop, flag)
-        if not on_side:
-            _S._cur.reduce._arm()
-        return (dw, db) if with_bias_grad else dw
-    gemm(0, 0, N, K, R, dy, dy.stride(0), x, x.stride(0), dw, colsum_a=db, accumulate=acc, precision=prec, a_amax=dy_amax, b_amax=x_amax,
-         a_drop=a_drop, range_flag=flag)
+    elif plan.route == "chained":
+        c.chain.launch(dy, x, dw, db, amax_of(dy, dy_amax), amax_of(x, x_amax), a_drop, flag)
+    else:
+        gemm(0, 0, N, K, R, dy, dy.stride(0), x, x.stride(0), dw, colsum_a=db, accumulate=acc, precision=plan.precision, a_amax=dy_amax,
+             b_amax=x_amax, a_drop=a_drop, range_flag=flag)
     return (dw, db) if with_bias_grad else dw
 
 
 class FusedLinearBwd:
     """dgrad + weight gradient of one linear layer as ONE launch (include/npvp_hip.h, npvp_linear_bwd_f16) - for the shapes on which
     each of the two alone leaves half the chip idle: small-tile dgrads with at least 1 024 and at most MAX_ROWS token rows (the
-    8-clip shards of the data-parallel configurations; the large workloads keep the two-stream schedule).  The weight gradient's
-    split-K reduction is the only in-place gradient write: with a gradient stream it is queued for that stream (ReduceQueue), where
-    every in-place write is serialised; without one (the step captured single-stream into a HIP graph) it rides in the next fused
-    launch on the same stream (WgradChain)."""
+    8-clip shards of the data-parallel configurations; the large workloads keep the two-stream schedule).  Its split-K reduction is
+    the only in-place gradient write: queued for the gradient stream, where those are serialised, or chained without one."""
     enabled = True
     MAX_ROWS = 16384
     # Beside a gradient stream the two launches on two streams are the better schedule wherever the GPU is the bound (in-process
@@ -521,15 +552,11 @@ class FusedLinearBwd:
     # 1 160 per c4 step), which is what a host-bound step wants (bench.py tries both under data parallelism, where the step
     # cannot be replayed from a graph).
     with_gradient_stream = False
-    _ok = {}
 
     @classmethod
     def takes(cls, R, N, K):
-        key = (R, N, K)
-        v = cls._ok.get(key)
-        if v is None:
-            v = cls._ok[key] = bool(lib().npvp_linear_bwd_f16_takes(R, N, K)) and _S._cur.chain.takes(N, K, R)
-        return v and R <= cls.MAX_ROWS
+        """the shape, with everything else in favour (linear_bwd_plan)"""
+        return linear_bwd_plan(R, N, K, 6, True, False, True, True, True, True, False, cls.MAX_ROWS).fused
 
 
 def linear_bwd(dy, x, w, b, sk, act=0, aux_in=None, drop=NO_DROP, residual=None, dy_amax=None, dx_amax=None, a_drop=NO_DROP):
@@ -539,50 +566,37 @@ def linear_bwd(dy, x, w, b, sk, act=0, aux_in=None, drop=NO_DROP, residual=None,
     R, N = dy.shape
     K = w.shape[1]
     has_b = b is not None
-    if (FusedLinearBwd.enabled and GEMM_PRECISION == 6 and sk and has_b == (sk[1] is not None) and FusedLinearBwd.takes(R, N, K)
-            and (FusedLinearBwd.with_gradient_stream or not _S._cur.wgrad.enabled) and not _S._cur.range_guard.fallback and not _S._cur.range_guard.strict and dy.stride(1) == 1 and x.stride(1) == 1):
-        pl = _planes(w, "D", R)
-        gw = sk[0][0]
-        if pl is not None and gw.stride(1) == 1:
-            planes, w_amax = pl
-            gb = sk[1][0] if has_b else None
-            dev = dy.device
-            dy_amax, x_amax = amax_of(dy, dy_amax), amax_of(x)
-            dx = torch.empty(R, K, dtype=torch.float32, device=dev)
-            ws, wsn = _ws(_S._cur.chain._wsb[(N, K, R)], dev)
-            st = _stream()
-            seed = _S._cur.rng.seed_tensor(dev) if (drop.on or a_drop.on) else None
-            outs = (gw.data_ptr(),) if gb is None else (gw.data_ptr(), gb.data_ptr())
-            chain = not _S._cur.wgrad.enabled
-            if chain:
-                job = ctypes.create_string_buffer(64)
-                prev = _S._cur.chain._pending.pop(st, None)
-                job_addr, prev_addr = ctypes.addressof(job), (ctypes.addressof(prev[0]) if prev is not None else None)
-            else:
-                job_addr, prev_addr = _S._cur.reduce.splitk_slot(outs), None
-            probe = GemmProbe.armed and (GemmProbe.only is None or 8 in GemmProbe.only)
-            if probe:
-                e0, e1 = probe_pair()
-            check(lib().npvp_linear_bwd_f16(R, N, K, dy.data_ptr(), dy.stride(0), dy_amax.data_ptr(), planes.data_ptr(), w_amax.data_ptr(),
-                                            dx.data_ptr(), dx.stride(0), act, _ptr(aux_in), _ptr(residual),
-                                            0 if residual is None else residual.stride(0), drop.p, drop.mode, drop.g1, drop.g2, drop.salt,
-                                            _ptr(dx_amax), x.data_ptr(), x.stride(0), x_amax.data_ptr(), gw.data_ptr(), gw.stride(0),
-                                            _ptr(gb), _ptr(_S._cur.range_guard.flag(dev)), a_drop.p, a_drop.g1, a_drop.g2, a_drop.salt, _ptr(seed),
-                                            prev_addr, job_addr, ws.data_ptr(), wsn, st), "npvp_linear_bwd_f16")
-            if probe:
-                e1.record()
-                GemmProbe.records.append((e0, e1, 4.0 * R * N * K, 4.0 * (2 * R * N + 2 * R * K + 2 * N * K), ((1, 0), 8)))
-            if chain:
-                if prev is not None and prev[4] is not None:
-                    _S._cur.grad_sink.wrote(*prev[4])            # (its reduction rode in the launch just enqueued)
-                _S._cur.chain._pending[st] = (job, ws, gw, gb, sk)
-                _S._cur.reduce._arm()                      # (the backward pass's end runs the last one: ReduceQueue.finish)
-            else:
-                _S._cur.reduce.splitk_added(outs, ws, sk)
-            return dx, None, None
-    dx = linear_dgrad(dy, w, act=act, aux_in=aux_in, drop=drop, residual=residual, dy_amax=dy_amax, dx_amax=dx_amax, a_drop=a_drop)
-    gw, gb = _lin_grads(dy, x, w, b, sk, a_drop=a_drop)
-    return dx, gw, gb
+    c = _S._cur
+    sunk = _sunk(sk, has_b)
+    pl = _planes(w, "D", R)
+    plan = linear_bwd_plan(R, N, K, GEMM_PRECISION, sunk, c.wgrad.enabled, not (c.range_guard.fallback or c.range_guard.strict),
+                           dy.stride(1) == 1 and x.stride(1) == 1 and (not sunk or sk[0][0].stride(1) == 1), pl is not None,
+                           FusedLinearBwd.enabled, FusedLinearBwd.with_gradient_stream, FusedLinearBwd.MAX_ROWS)
+    if not plan.fused:
+        dx = linear_dgrad(dy, w, act=act, aux_in=aux_in, drop=drop, residual=residual, dy_amax=dy_amax, dx_amax=dx_amax, a_drop=a_drop)
+        gw, gb = _lin_grads(dy, x, w, b, sk, a_drop=a_drop, plan=plan)
+        return dx, gw, gb
+    planes, w_amax = pl
+    gw, gb = sk[0][0], (sk[1][0] if has_b else None)
+    dev = dy.device
+    dy_amax, x_amax = amax_of(dy, dy_amax), amax_of(x)
+    dx = torch.empty(R, K, dtype=torch.float32, device=dev)
+    ws, wsn = _ws(c.chain.workspace_bytes(N, K, R), dev)
+    st = _stream()
+    seed = c.rng.seed_tensor(dev) if (drop.on or a_drop.on) else None
+    outs = (gw.data_ptr(),) if gb is None else (gw.data_ptr(), gb.data_ptr())
+    later = c.chain if plan.reduction == "chained" else c.reduce       # who runs this launch's split-K reduction
+    job_addr, prev_addr = later.job_slot(st, outs)
+    pe = GemmProbe.begin(8)
+    check(lib().npvp_linear_bwd_f16(R, N, K, dy.data_ptr(), dy.stride(0), dy_amax.data_ptr(), planes.data_ptr(), w_amax.data_ptr(),
+                                    dx.data_ptr(), dx.stride(0), act, _ptr(aux_in), _ptr(residual),
+                                    0 if residual is None else residual.stride(0), drop.p, drop.mode, drop.g1, drop.g2, drop.salt,
+                                    _ptr(dx_amax), x.data_ptr(), x.stride(0), x_amax.data_ptr(), gw.data_ptr(), gw.stride(0),
+                                    _ptr(gb), _ptr(c.range_guard.flag(dev)), a_drop.p, a_drop.g1, a_drop.g2, a_drop.salt, _ptr(seed),
+                                    prev_addr, job_addr, ws.data_ptr(), wsn, st), "npvp_linear_bwd_f16")
+    GemmProbe.end(pe, 4.0 * R * N * K, 4.0 * (2 * R * N + 2 * R * K + 2 * N * K), (1, 0), 8)
+    later.job_added(st, outs, (ws, gw, gb), sk)
+    return dx, None, None
 
 
 def colsum(x):
@@ -1044,38 +1058,32 @@ class _Linear(torch.autograd.Function):
         dx = linear_dgrad(dz, w, a_drop=ad).reshape(ctx.xshape) if ctx.needs_input_grad[0] else None
         dw = db = None
         want_b = ctx.has_b and ctx.needs_input_grad[2]
-        sk = ctx.sink
-        if sk and ctx.needs_input_grad[1] and want_b == (sk[1] is not None):
-            _sunk_wgrad(dz, x2, want_b, sk, a_drop=ad)
-        elif ctx.needs_input_grad[1]:
-            dw = linear_wgrad(dz, x2, want_b, a_drop=ad)
-            if want_b:
-                dw, db = dw
+        if ctx.needs_input_grad[1]:
+            dw, db = _lin_grads(dz, x2, w, True if want_b else None, ctx.sink, a_drop=ad)
         elif want_b:
             db = colsum(dz)
         dres = dy if ctx.has_r else None
         return dx, dw, db, dres, None, None
 
 
-def _wgrad_slots(dy, x, dy_amax=None, x_amax=None):
-    """the amax slots of a weight-gradient GEMM's operands when the fp16 kernel will take it, filled on the CURRENT stream
-    (the GEMM itself may run on the gradient stream, which is ordered after this one; a slot first filled over there would
-    be read here without any ordering)"""
-    if GEMM_PRECISION == 6 and _gemm_kernel_id(0, 0, dy.shape[1], x.shape[1], dy.shape[0], 6, False) == 6:
-        return amax_of(dy, dy_amax), amax_of(x, x_amax)
-    return None, None
-
-
-def _sunk_wgrad(dy, x, with_b, sk, dy_amax=None, x_amax=None, a_drop=NO_DROP):
-    """accumulate dW (and db) of one linear into its gradient slots - on the wgrad stream when enabled"""
-    dy_amax, x_amax = _wgrad_slots(dy, x, dy_amax, x_amax)
-    fn = lambda dy=dy, x=x, gw=sk[0][0], gb=(sk[1][0] if with_b else None), a1=dy_amax, a2=x_amax, ad=a_drop: \
-        linear_wgrad(dy, x, with_b, into=gw, into_b=gb, dy_amax=a1, x_amax=a2, a_drop=ad)
-    if _S._cur.wgrad.enabled:
-        _S._cur.wgrad.run(fn, dy, x, wrote=sk, urgent=2.0 * dy.shape[0] * dy.shape[1] * x.shape[1] >= 3e10)
+def _lin_grads(dy, x, w, b, sk, a_drop=NO_DROP, plan=None):
+    """weight (+ bias) gradient of y = x w^T + b (`b` only says whether there is a bias gradient to take): accumulated into the
+    sink `sk` (-> None, None) - on the gradient stream when there is one - or returned"""
+    has_b = b is not None
+    if plan is None:
+        plan = linear_bwd_plan(dy.shape[0], dy.shape[1], x.shape[1], GEMM_PRECISION, _sunk(sk, has_b), _S._cur.wgrad.enabled)
+    if not plan.sunk:
+        g = linear_wgrad(dy, x, has_b, a_drop=a_drop)
+        return (g[0], g[1]) if has_b else (g, None)
+    a1, a2 = (amax_of(dy), amax_of(x)) if plan.fill_slots else (None, None)
+    fn = lambda dy=dy, x=x, gw=sk[0][0], gb=(sk[1][0] if has_b else None), a1=a1, a2=a2, ad=a_drop: \
+        linear_wgrad(dy, x, has_b, into=gw, into_b=gb, dy_amax=a1, x_amax=a2, a_drop=ad)
+    if plan.on_grad_stream:
+        _S._cur.wgrad.run(fn, dy, x, wrote=sk, urgent=plan.urgent)
     else:
         fn()
         _S._cur.grad_sink.wrote(*sk)
+    return None, None
 
 
 def _wb_sink(w, b):
@@ -1112,7 +1120,7 @@ class _FFN(torch.autograd.Function):
         ctx.save_for_backward(xn2, h, a, w1, w2)
         ctx.d2, ctx.d3, ctx.shape = d2, d3, x.shape
         s1, s2 = _wb_sink(w1, b1), _wb_sink(w2, b2)
-        ctx.sink = (s1, s2) if (s1 and s2 and s1[1] is not None and s2[1] is not None) else None
+        ctx.sink = (s1, s2) if (_sunk(s1, True) and _sunk(s2, True)) else None
         return y.reshape(x.shape)
 
     @scoped
@@ -1124,9 +1132,9 @@ class _FFN(torch.autograd.Function):
         sk = ctx.sink
         if sk:
             dh = linear_dgrad(dz2, w2, act=3, aux_in=h, drop=ctx.d2, a_drop=ad)
-            _sunk_wgrad(dz2, a, True, sk[1], a_drop=ad)
+            _lin_grads(dz2, a, w2, True, sk[1], a_drop=ad)
             dxn = linear_dgrad(dh, w1)
-            _sunk_wgrad(dh, xn2, True, sk[0])
+            _lin_grads(dh, xn2, w1, True, sk[0])
             return dxn.reshape(ctx.shape), dy, None, None, None, None, None
         dw2, db2 = linear_wgrad(dz2, a, True, a_drop=ad)
         dh = linear_dgrad(dz2, w2, act=3, aux_in=h, drop=ctx.d2, a_drop=ad)
@@ -1632,16 +1640,6 @@ def _raw_posfuse_bwd(dy, x, add, beta_shape, gamma, st, N, T, want_add, sinks=(N
         else:
             dadd = reduce_mid(du.view(N, T, PF)).view(add.shape)
     return du, dadd, dbeta, dgamma
-
-
-def _lin_grads(dy, x, w, b, sk, a_drop=NO_DROP):
-    """weight (+ bias) gradient of y = x w^T + b: into the sink on the gradient stream (-> None, None) or returned"""
-    has_b = b is not None
-    if sk and (has_b == (sk[1] is not None)):
-        _sunk_wgrad(dy, x, has_b, sk, a_drop=a_drop)
-        return None, None
-    g = linear_wgrad(dy, x, has_b, a_drop=a_drop)
-    return (g[0], g[1]) if has_b else (g, None)
 
 
 class _SelfAttnSublayer(torch.autograd.Function):

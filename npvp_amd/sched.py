@@ -19,6 +19,7 @@ on the tensors they mirror), the gradient stream of a device, bench.py's probes,
 """
 import contextlib
 import ctypes
+import functools
 import os
 
 import torch
@@ -131,11 +132,13 @@ class ProbeEvent:
                 pass
 
 
-def probe_pair():
-    """two fresh timing events, the first already recorded"""
-    e0, e1 = ProbeEvent(), ProbeEvent()
-    e0.record()
-    return e0, e1
+def _stamp(on):
+    """a fresh timing event, recorded on the current stream - or None when the probe is off"""
+    if not on:
+        return None
+    e = ProbeEvent()
+    e.record()
+    return e
 
 
 class GemmProbe:
@@ -163,6 +166,16 @@ class GemmProbe:
         cls.armed = False
 
     @classmethod
+    def begin(cls, kid):
+        """-> the recorded start event of a launch of kernel `kid`, or None when that kernel is not being timed"""
+        return _stamp(cls.armed and (cls.only is None or kid in cls.only))
+
+    @classmethod
+    def end(cls, e0, flops, nbytes, layout, kid):
+        if e0 is not None:
+            cls.records.append((e0, _stamp(True), flops, nbytes, (layout, kid)))
+
+    @classmethod
     def summary(cls):
         """{(layout, kernel id): (launches, total_ms, total_flops, total_algorithmic_bytes)} - after torch.cuda.synchronize()"""
         out = {}
@@ -185,19 +198,12 @@ class HbmProbe:
 
     @classmethod
     def begin(cls):
-        if not cls.armed:
-            return None
-        e0 = ProbeEvent()
-        e0.record()
-        return e0
+        return _stamp(cls.armed)
 
     @classmethod
     def end(cls, e0, name, nbytes):
-        if e0 is None:
-            return
-        e1 = ProbeEvent()
-        e1.record()
-        cls.records.append((e0, e1, name, float(nbytes)))
+        if e0 is not None:
+            cls.records.append((e0, _stamp(True), name, float(nbytes)))
 
     @classmethod
     def summary(cls):
@@ -480,7 +486,8 @@ class ReduceQueueState:
 
     def __init__(self, ctx):
         self.ctx = ctx
-        self._buf = self._addr = self._skbuf = self._skaddr = None
+        self._buf, self._skbuf = ctypes.create_string_buffer(self.JOB * self.CAP), ctypes.create_string_buffer(self.SKJOB * self.SKCAP)
+        self._addr, self._skaddr = ctypes.addressof(self._buf), ctypes.addressof(self._skbuf)        # (host buffers of job records)
         self._n = self._skn = 0
         self._bytes = 0
         self._keep, self._wrote, self._outs = [], [], set()
@@ -495,23 +502,24 @@ class ReduceQueueState:
         read back 1.3 GB at a time: with the count alone the c2 step lost 0.9 ms to the queue, profiles/r05_ab_knobs.txt)"""
         return self._n >= self.LAUNCH or self._skn >= self.SKLAUNCH or self._bytes >= self.LAUNCH_BYTES
 
-    def splitk_slot(self, out_ptrs):
-        """host address for the next 64-byte split-K job record (the C call that leaves the partial slabs writes it)"""
-        if self._skbuf is None:
-            self._skbuf = ctypes.create_string_buffer(self.SKJOB * self.SKCAP)
-            self._skaddr = ctypes.addressof(self._skbuf)
+    def job_slot(self, st, out_ptrs):
+        """before a launch that leaves split-K slabs for dw, db at `out_ptrs`: -> (host address for its 64-byte job record, None: no job rides in it)"""
         if self._skn == self.SKCAP or not self._outs.isdisjoint(out_ptrs):
             self.run_pending()
-        return self._skaddr + self.SKJOB * self._skn
+        return self._skaddr + self.SKJOB * self._skn, None
 
-    def splitk_added(self, out_ptrs, keep, wrote):
+    def job_added(self, st, out_ptrs, keep, wrote):
+        """after it: the record counts; keep = (workspace, dw, db), wrote = the sink slots to report when the reduction is enqueued"""
         self._skn += 1
+        self._added(out_ptrs, keep[0], wrote)   # (dw, db are slices of the flat gradient buffer)
+
+    def _added(self, out_ptrs, keep, wrote):
         self._bytes += keep.numel() * 4
         self._keep.append(keep)
         self._outs.update(out_ptrs)
         if wrote is not None:
             self._wrote.append(wrote)
-        self._arm()
+        self.arm()
         self._dp_progress()
 
     def _dp_progress(self):
@@ -522,7 +530,7 @@ class ReduceQueueState:
         if self.ctx.grad_sink.listener is not None and self._n + self._skn >= self.DP_LAUNCH:
             self.run_pending()
 
-    def _arm(self):
+    def arm(self):
         if not self._armed:
             self._armed = True
             try:
@@ -532,20 +540,11 @@ class ReduceQueueState:
 
     def add(self, filler, name, args, out_ptrs, keep, wrote):
         """filler(*args, job address) = one of the npvp_*_reduce_job entry points; out_ptrs: device addresses the job writes"""
-        if self._buf is None:
-            self._buf = ctypes.create_string_buffer(self.JOB * self.CAP)
-            self._addr = ctypes.addressof(self._buf)
         if self._n == self.CAP or not self._outs.isdisjoint(out_ptrs):
             self.run_pending()
         check(filler(*args, self._addr + self.JOB * self._n), name)
         self._n += 1
-        self._bytes += keep.numel() * 4
-        self._keep.append(keep)
-        self._outs.update(out_ptrs)
-        if wrote is not None:
-            self._wrote.append(wrote)
-        self._arm()
-        self._dp_progress()
+        self._added(out_ptrs, keep, wrote)
 
     def run_pending(self):
         """the queued jobs, now, on the stream where in-place gradient writes belong: the gradient stream whenever there is one
@@ -598,41 +597,51 @@ class WgradChainState:
     reduction launches of an 8-clip step; HBM-bound work beside MFMA-bound work), WgradStream.join() runs the last one.  Same
     summation order as the stand-alone reduction, so results are bit-identical.  `enabled = False`: one reduction launch each."""
     enabled = True
-    _ok, _wsb = {}, {}           # (shape caches: pure functions of the shape, process-wide)
 
     def __init__(self, ctx):
         self.ctx = ctx
-        self._pending = {}       # raw stream -> (job bytes, workspace, dw, db, sink slots to report): alive until the job is handed on
+        self._pending = {}       # raw stream -> (job bytes, keep-alives, sink slots to report): until the job is handed on
+        self._open = None        # (job bytes, the job popped for it) between job_slot() and job_added()
 
-    @classmethod
-    def takes(cls, M, N, K):
-        key = (M, N, K)
-        v = cls._ok.get(key)
-        if v is None:
-            v = cls._ok[key] = bool(lib().npvp_wgrad_f16_chainable(M, N, K))
-            cls._wsb[key] = lib().npvp_wgrad_f16_chain_workspace_bytes(M, N, K)
-        return v
+    @staticmethod
+    @functools.lru_cache(maxsize=None)
+    def takes(M, N, K):
+        return bool(lib().npvp_wgrad_f16_chainable(M, N, K))
+
+    @staticmethod
+    @functools.lru_cache(maxsize=None)
+    def workspace_bytes(M, N, K):
+        return lib().npvp_wgrad_f16_chain_workspace_bytes(M, N, K)
+
+    def job_slot(self, st, out_ptrs=None):
+        """before a launch on `st` that leaves split-K slabs: -> (host address for its 64-byte job record, the job the previous launch on `st` left or None)"""
+        self._open = job, prev = ctypes.create_string_buffer(64), self._pending.pop(st, None)
+        return ctypes.addressof(job), (ctypes.addressof(prev[0]) if prev is not None else None)
+
+    def job_added(self, st, out_ptrs, keep, wrote):
+        """after it: the previous job rode in it (its sink slots are reported); this one waits for the next launch on `st` or for flush() - outside
+        WgradStream.flush the end of the backward pass calls that (ReduceQueue.finish)"""
+        job, prev = self._open
+        if prev is not None and prev[2] is not None:
+            self.ctx.grad_sink.wrote(*prev[2])
+        self._pending[st] = (job, keep, wrote)
+        if not self.ctx.wgrad.in_flush:
+            self.ctx.reduce.arm()
 
     def launch(self, dy, x, dw, db, dy_amax, x_amax, a_drop, flag):
         """dw (+)= dy^T x, db (+)= colsum(dy), both ACCUMULATED (GradSink slices), reduction deferred"""
         R, N = dy.shape
         K = x.shape[1]
         st = _stream()
-        ws, wsn = _ws(self._wsb[(N, K, R)], dy.device)
-        job = ctypes.create_string_buffer(64)
-        prev = self._pending.pop(st, None)
+        ws, wsn = _ws(self.workspace_bytes(N, K, R), dy.device)
+        job_addr, prev_addr = self.job_slot(st)
         seed = self.ctx.rng.seed_tensor(dy.device) if a_drop.on else None
-        probe = GemmProbe.armed and (GemmProbe.only is None or 6 in GemmProbe.only)
-        if probe:
-            e0, e1 = probe_pair()
+        pe = GemmProbe.begin(6)
         check(lib().npvp_wgrad_f16_chained(N, K, R, _ptr(dy), dy.stride(0), _ptr(x), x.stride(0), _ptr(dw), dw.stride(0), _ptr(db), 1,
                                            _ptr(dy_amax), _ptr(x_amax), _ptr(flag), a_drop.p, a_drop.g1, a_drop.g2, a_drop.salt,
-                                           _ptr(seed), ctypes.addressof(prev[0]) if prev is not None else None, ctypes.addressof(job),
-                                           _ptr(ws), wsn, st), "npvp_wgrad_f16_chained")
-        if probe:
-            e1.record()
-            GemmProbe.records.append((e0, e1, 2.0 * N * K * R, 4.0 * (N * R + K * R + N * K), ((0, 0), 6)))
-        self._pending[st] = (job, ws, dw, db, None)
+                                           _ptr(seed), prev_addr, job_addr, _ptr(ws), wsn, st), "npvp_wgrad_f16_chained")
+        GemmProbe.end(pe, 2.0 * N * K * R, 4.0 * (N * R + K * R + N * K), (0, 0), 6)
+        self.job_added(st, None, (ws, dw, db), None)
 
     def flush(self):
         """the pending job of the CURRENT stream, as a launch of its own"""
@@ -640,8 +649,8 @@ class WgradChainState:
         prev = self._pending.pop(st, None)
         if prev is not None:
             check(lib().npvp_splitk_reduce_job(ctypes.addressof(prev[0]), st), "npvp_splitk_reduce_job")
-            if prev[4] is not None:
-                self.ctx.grad_sink.wrote(*prev[4])
+            if prev[2] is not None:
+                self.ctx.grad_sink.wrote(*prev[2])
 
 
 class RangeGuardState:

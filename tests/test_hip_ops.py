@@ -410,6 +410,68 @@ def test_drop_path_mask_rides_in_the_gemms(K, R, g1, g2):
     assert torch.equal(dx == 0, dx_r == 0), "dropped rows must be exactly zero in both routes"
 
 
+@pytest.mark.parametrize("R,N,K_,g1,g2", [(1024, 128, 128, 64, 16), (1056, 512, 256, 48, 22)])
+def test_linear_backward_routes_are_bit_identical(K, R, N, K_, g1, g2):
+    """ops.linear_bwd of one nn.Linear whose parameters sit in a FlatBuffers, on every launch route the scheduling knobs can send it
+    down: weight gradient on the gradient stream (chained there, or a plain GEMM with the chain off), chained on the current stream,
+    fused with the dgrad (reduction chained, or queued beside a gradient stream).  Same tiles, same splits, same summation order:
+    dx, dW and db are bit-identical across the five and agree with the fp64 product; with a DropPath mask on the rows of dy the five
+    are compared with each other.  The smallest shapes at which the fused and chained routes exist; R = 1056 is no multiple of 64,
+    so its dgrad runs on 128 x 64 tiles."""
+    from npvp_amd.ops import Drop
+    from npvp_amd.trainer import FlatBuffers
+    if K.GEMM_PRECISION != 6:
+        pytest.skip("the chained and fused launches belong to the fp16 kernels")
+    dev = torch.device(DEV)
+    dy, x = O.seeded_randn((R, N), 311), O.seeded_randn((R, K_), 312)
+    lin = torch.nn.Linear(K_, N)
+    with torch.no_grad():
+        lin.weight.copy_(O.seeded_randn((N, K_), 313) / K_ ** 0.5)
+    lin = lin.to(dev)
+    fb = FlatBuffers(lin)
+    w, b = lin.weight, lin.bias
+    sk = K._wb_sink(w, b)
+    assert sk is not None and sk[1] is not None, "the layer's gradients must go into the flat buffer"
+    dyg, xg = dy.to(DEV), x.to(DEV)
+    K.rng.manual_seed(5, dev)
+    mask = Drop(0.1, 1, g1, g2)
+    assert K.masked_grad(dyg, mask, w)[1].on, "the mask must ride in the GEMMs at this shape"
+    # gradient stream, chain, fused, fused beside a gradient stream
+    settings = [(True, True, False, False), (True, False, False, False), (False, True, False, False), (False, True, True, False),
+                (True, True, True, True)]
+    old = (K.WgradStream.enabled, K.WgradChain.enabled, K.FusedLinearBwd.enabled, K.FusedLinearBwd.with_gradient_stream)
+    got = {}
+    try:
+        for a_drop in (K.NO_DROP, mask):
+            for s in settings:
+                K.WgradStream.join()
+                K.WgradStream.enabled, K.WgradChain.enabled, K.FusedLinearBwd.enabled, K.FusedLinearBwd.with_gradient_stream = s
+                K.rng.manual_seed(5, dev)
+                K.rng.begin_step(dev)
+                fb.flat_g.zero_()
+                dx, gw, gb = K.linear_bwd(dyg, xg, w, b, sk, a_drop=a_drop)
+                K.ReduceQueue.finish()
+                K.WgradStream.join()
+                torch.cuda.synchronize()
+                assert gw is None and gb is None, "the gradients go into the sink"
+                assert not K.WgradChain._pending and not K.ReduceQueue.pending(), "a deferred reduction was left behind"
+                got[(a_drop.on, s)] = (dx.clone(), w.grad.clone(), b.grad.clone())
+    finally:
+        K.WgradStream.join()
+        K.WgradStream.enabled, K.WgradChain.enabled, K.FusedLinearBwd.enabled, K.FusedLinearBwd.with_gradient_stream = old
+    for masked in (False, True):
+        first = got[(masked, settings[0])]
+        assert float(first[1].abs().max()) > 0 and float(first[2].abs().max()) > 0
+        for s in settings[1:]:
+            for u, v, n in zip(got[(masked, s)], first, ("dx", "dw", "db")):
+                assert torch.equal(u, v), f"{n}, masked {masked}: setting {s} differs from {settings[0]} by {rel(u, v):.3e}"
+    dx, dw, db = got[(False, settings[0])]
+    wd = w.detach().double().cpu()
+    close(dx, (dy.double() @ wd).float(), tol=1e-5, what="dx")
+    close(dw, (dy.double().T @ x.double()).float(), tol=1e-5, what="dw")
+    close(db, dy.double().sum(0).float(), tol=1e-5, what="db")
+
+
 @pytest.mark.parametrize("with_add,with_gamma", [(True, False), (False, True)])
 def test_layernorm_and_positional_fuse_in_one_kernel(K, with_add, with_gamma):
     """npvp_ln_posfuse_fwd (frames of 64 token rows x 512 channels held in a block's registers) against npvp_layernorm_fwd followed

@@ -1,6 +1,8 @@
 """GPU: a fingerprint of the library calls the autograd glue makes.  Every bound entry point of npvp_amd._lib.lib() is replaced by
 a recorder; fixed-seed cases of tests/golden_cases.py run under the three scheduling modes that select the three arms of
-ops._reduce_partials, plus one GraphedTrainStep capture; per case the number of calls and a SHA-256 over the sequence of (entry
+ops._reduce_partials, plus one GraphedTrainStep capture; one step with 4 096 decoder token rows - where the fp16 weight-gradient
+kernel, the chained split-K reductions and the fused dgrad + weight-gradient launch run - under those modes and the knobs of the
+linear backward (LINEAR_MODES); per case the number of calls and a SHA-256 over the sequence of (entry
 point, every scalar argument; an address reduced to null / non-null) are printed.  Two trees that print the same lines make the
 same calls with the same arguments in the same order: run it before and after a change of npvp_amd/ops.py that is meant to move none.
 
@@ -28,11 +30,21 @@ MODES = {"default": (True, True), "closure": (True, False), "inline": (False, Fa
 FAMILIES = ("npvp_layernorm_bwd_reduce", "npvp_frameln_act_bwd_reduce", "npvp_mlpdw_mid_bwd_reduce")
 JOB = {f + "_job" for f in FAMILIES}
 DIRECT = {FAMILIES[0], FAMILIES[1], FAMILIES[2] + "_into"}
+# shape queries answered on the host and remembered per shape by the glue: WHEN one is first asked is no property of the launch sequence
+QUERIES = {"npvp_gemm_kernel_id", "npvp_gemm_workspace_bytes", "npvp_linear_bwd_f16_takes", "npvp_wgrad_f16_chainable",
+           "npvp_wgrad_f16_chain_workspace_bytes"}
+# the knobs of the linear backward, beside (gradient stream, ReduceQueue) of MODES: fused beside a gradient stream, chain, range guard
+LINEAR_MODES = {"fused": dict(with_gradient_stream=True), "nochain": dict(chain=False), "strict": dict(strict=True),
+                "fallback": dict(fallback=True)}
+LINEAR_CALLS = ("npvp_linear_bwd_f16", "npvp_wgrad_f16_chained", "npvp_splitk_reduce_job", "npvp_splitk_reduce_multi")
 
 
 def install():
     L = _lib.lib()
     for name, (_, argtypes) in _lib.SIGNATURES.items():
+        if name in QUERIES:
+            continue
+
         def rec(*a, _f=getattr(L, name), _n=name, _t=argtypes):
             CALLS.append((_n,) + tuple(bool(getattr(v, "value", v)) if t is ctypes.c_void_p else (float(v) if t is ctypes.c_float else int(v))
                                        for v, t in zip(a, _t)))
@@ -46,6 +58,20 @@ def graphed_step():
     past, fut = GC.O.synth_features((2, 3, 512, 8, 8), 92).to(DEV), GC.O.synth_features((2, 4, 512, 8, 8), 93).to(DEV)
     step = impl.GraphedTrainStep(m, make_opt(m), past, fut, 0.01, 1e-6, 1.0, warmup=1)
     step(past, fut, lr=1e-4)
+
+
+def shard_step():
+    """the step of tests/test_hip_golden.py::test_chained_split_k_reductions_are_bit_identical: forward, backward, join"""
+    N, To, Tp = 8, 2, 8
+    past, fut = GC.O.synth_features((N, To, 512, 8, 8), 92).to(DEV), GC.O.synth_features((N, Tp, 512, 8, 8), 93).to(DEV)
+    m = GC._small_predictor(impl, False, 101, DEV, To=To, Tp=Tp, dropout=0.1, drop_path=0.1)
+    m.train()
+    opt = make_opt(m)
+    ops.rng.manual_seed(777, torch.device(DEV))
+    ops.rng.begin_step(torch.device(DEV))
+    opt.zero_grad()
+    (m(past) - fut).abs().mean().backward()
+    ops.WgradStream.join()
 
 
 def make_opt(m):
@@ -93,6 +119,23 @@ def main():
         assert tuple(n > 0 for n in arms) == want, (mode, arms)
     ops.WgradStream.enabled = ops.ReduceQueue.enabled = True
     run("graph", "graphed_step_D", graphed_step, a.dump)
+    hit = dict.fromkeys(LINEAR_CALLS, 0)
+    for mode, knobs in list(MODES.items()) + list(LINEAR_MODES.items()):
+        ops.WgradStream.join()
+        ops.WgradStream.enabled, ops.ReduceQueue.enabled = knobs if isinstance(knobs, tuple) else (True, True)
+        k = dict(with_gradient_stream=False, chain=True, strict=False, fallback=False)
+        k.update({} if isinstance(knobs, tuple) else knobs)
+        ops.FusedLinearBwd.with_gradient_stream, ops.WgradChain.enabled, ops.RangeGuard.strict = k["with_gradient_stream"], k["chain"], k["strict"]
+        ops.RangeGuard.reset()
+        ops.RangeGuard.fallback = k["fallback"]
+        run(mode, "shard_step", shard_step, a.dump)
+        for n in LINEAR_CALLS:
+            hit[n] += sum(c[0] == n for c in CALLS)
+    ops.RangeGuard.reset()
+    ops.WgradStream.enabled = ops.ReduceQueue.enabled = ops.WgradChain.enabled = True
+    ops.FusedLinearBwd.with_gradient_stream = ops.RangeGuard.strict = False
+    print("linear backward calls over the shard_step modes: " + ", ".join(f"{n} {hit[n]}" for n in LINEAR_CALLS), flush=True)
+    assert all(hit.values()), hit
 
 
 if __name__ == "__main__":
