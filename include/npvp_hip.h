@@ -408,6 +408,19 @@ int npvp_dwtb_accumulate(const float* dwtb, float* gw, float* gb, int C, npvp_st
 int npvp_dwtb_build(const float* w, const float* b, float* wtb, int C, npvp_stream_t stream);
 int npvp_reduce_mid(const float* in, float* out, int A, int B, long long Cc, float scale, int accumulate, npvp_stream_t stream);    /* accumulate = 1: out += */
 int npvp_broadcast_mid(const float* in, float* out, int A, int B, long long Cc, float scale, npvp_stream_t stream);
+/* Centre padding of a feature grid to the next multiple of the attention window and its adjoint (ref/models/VidHRFormer.py:488-511,
+ * PadBlock.pad_if_needed / depad_if_needed), on token rows [frames][H*W][C] with row strides ld_* (floats).  The caller supplies the
+ * geometry: Hp >= H, Wp >= W, 0 <= top <= Hp - H, 0 <= left <= Wp - W (the reference: top = (Hp - H) / 2, left = (Wp - W) / 2).
+ * C % 4 == 0, strides % 4 == 0, buffers 16-byte aligned, row counts below 2^31.
+ *   pad: src [F*H*W, C] -> dst [rows_out >= F*Hp*Wp, C].  Every element of dst is written exactly once: the centre rows are copies, the
+ *        border rows and the trailing rows [F*Hp*Wp, rows_out) zeros (a caller rounds rows_out up for a GEMM; no zero-filled buffer is
+ *        assumed and nothing is memset).  F = 0 writes rows_out zero rows.
+ *   cut: src [>= F*Hp*Wp, C] -> dst [F*H*W, C] = the centre rows, + addend [F*H*W, C] (row stride ld_add) when it is not NULL.
+ * Each is the other's adjoint.  dst_amax (nullable): the amax slot of dst.  Plain copies: bit-reproducible. */
+int npvp_grid_center_pad(const float* src, long long ld_src, float* dst, long long ld_dst, int F, int H, int W, int Hp, int Wp, int top,
+                         int left, int C, long long rows_out, float* dst_amax, npvp_stream_t stream);
+int npvp_grid_center_cut(const float* src, long long ld_src, const float* addend, long long ld_add, float* dst, long long ld_dst, int F,
+                         int H, int W, int Hp, int Wp, int top, int left, int C, float* dst_amax, npvp_stream_t stream);
 
 /* out[n] = sum_r x[r][n]: bias gradients of every Linear / Conv2d on the path */
 long long npvp_colsum_workspace_bytes(long long rows, int N);

@@ -43,9 +43,19 @@ class MultiheadAttention(nn.Module):
         """q = k source x_qk [R,C], value source x_v [R,C] -> residual + drop(out_proj(core))."""
         C = self.embed_dim
         w, b = self.in_proj_weight, self.in_proj_bias
+        if not cfg.tiles:
+            # the window does not tile the grid: centre-pad both sources BEFORE the in-projection (ref :287,295 - a pad token is a
+            # zero row, so its q, k, v are the biases and it is an ordinary key of its window), cut the centre back out (ref :305)
+            x_qk, x_v = ops.grid_pad(x_qk, cfg), ops.grid_pad(x_v, cfg)
         qk = ops.linear(x_qk, w[:2 * C], b[:2 * C])
         v = ops.linear(x_v, w[2 * C:], b[2 * C:])
         o = ops.attn_packed(qk, v, cfg)
+        if not cfg.tiles:
+            o = ops.grid_cut(o, cfg)
+            if residual is None and not drop.on:
+                # the module called on its own: the real rows of a few frames of such a grid are seldom a multiple of the 32 the
+                # out-projection's weight gradient sums in (inside a block the residual stream has the whole batch's rows)
+                return ops.linear_any_rows(o, self.out_proj.weight, self.out_proj.bias)
         return ops.linear(o, self.out_proj.weight, self.out_proj.bias, residual=residual, drop=drop)
 
     def cross_attention(self, x_q, x_k, x_v, cfg, residual=None, drop=ops.NO_DROP):
@@ -68,8 +78,8 @@ class SpatialLocalMultiheadAttention(nn.Module):
 
     def _cfg(self, N, T, H, W):
         if H % self.window_size or W % self.window_size:
-            raise NotImplementedError("feature grid must be a multiple of the window (8/4 in every config); the "
-                                      "centre-pad branch of ref PadBlock is not on the hot path")
+            # ref PadBlock (:488-511): the grid is centre-padded to the next multiple of the window and the centre cut back out
+            return AttnCfg.spatial(N * T, H, W, self.window_size, self.num_heads, self.dropout if self.training else 0.0)
         return AttnCfg(0, N * T, H * W, W, self.window_size, 0, 0, self.num_heads, 0,
                        self.dropout if self.training else 0.0)
 

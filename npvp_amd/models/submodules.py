@@ -59,10 +59,10 @@ class NRMLP(nn.Module):
     def forward(self, x):
         x = self.gaussian_mapping(x)
         for m in self.MLP:
-            x = ops.linear(x, m.weight, m.bias) if isinstance(m, nn.Linear) else torch.relu(x)
-        beta = ops.linear(x, self.mlp_beta.weight, self.mlp_beta.bias)
+            x = ops.linear_any_rows(x, m.weight, m.bias) if isinstance(m, nn.Linear) else torch.relu(x)
+        beta = ops.linear_any_rows(x, self.mlp_beta.weight, self.mlp_beta.bias)
         if self.fuse_method == 'SPADE':
-            gamma = ops.linear(x, self.mlp_gamma.weight, self.mlp_gamma.bias)
+            gamma = ops.linear_any_rows(x, self.mlp_gamma.weight, self.mlp_gamma.bias)
         else:
             gamma = torch.zeros_like(beta)     # as the reference (ref :309-312); Predictor drops it (1 + 0 is exact)
         return beta, gamma
@@ -134,15 +134,15 @@ class EventEncoder(nn.Module):
         h = torch.relu(_bn_rows(h, self.conv1[1]))
         w2 = self.conv2[0].weight                                        # [hid, C, 3, 3] -> tap-major [hid, 9*C]
         cols = ops.im2col3x3(h.view(N, P, C), N, H, W)
-        h = ops.linear(cols, w2.permute(0, 2, 3, 1).reshape(w2.shape[0], 9 * C))
+        h = ops.linear_any_rows(cols, w2.permute(0, 2, 3, 1).reshape(w2.shape[0], 9 * C))
         h = torch.relu(_bn_rows(h, self.conv2[1]))
         for i in range(self.n_layers):
             m = getattr(self, f'MLP_{i}')
-            h = torch.relu(_bn_rows(ops.linear(h, m[0].weight.flatten(1)), m[1]))
-        mu = ops.linear(h, self.mu_net.weight.flatten(1), self.mu_net.bias).view(N, P, C)
+            h = torch.relu(_bn_rows(ops.linear_any_rows(h, m[0].weight.flatten(1)), m[1]))
+        mu = ops.linear_any_rows(h, self.mu_net.weight.flatten(1), self.mu_net.bias).view(N, P, C)
         if not self.stochastic:
             return mu
-        logvar = ops.linear(h, self.logvar_net.weight.flatten(1), self.logvar_net.bias).view(N, P, C)
+        logvar = ops.linear_any_rows(h, self.logvar_net.weight.flatten(1), self.logvar_net.bias).view(N, P, C)
         if self.eps_fn is not None:
             eps = ops.transpose(self.eps_fn((N, C, H, W)).reshape(N, C, P))
         else:

@@ -1156,13 +1156,45 @@ def ffn(xn, x, w1, b1, w2, b2, p):
     return _FFN.apply(xn, x, w1, b1, w2, b2, p)
 
 
-class AttnCfg:
-    __slots__ = ("mode", "dim0", "P", "W", "ws", "Tq", "Tk", "heads", "mask_mode", "drop")
+def window_pad_geometry(H, W, ws):
+    """(Hp, Wp, top, left) of ref/models/VidHRFormer.py:488-511 (PadBlock): the grid is centre-padded to the next multiple of the
+    window; an odd pad puts the smaller half first.  THE place these formulas are written in npvp_amd."""
+    Hp, Wp = -(-H // ws) * ws, -(-W // ws) * ws
+    return Hp, Wp, (Hp - H) // 2, (Wp - W) // 2
 
-    def __init__(self, mode, dim0, P, W, ws, Tq, Tk, heads, mask_mode, p_drop):
+
+class AttnCfg:
+    """What the attention entry points take.  grid = None: the window tiles the grid (every call written before the centre-pad
+    route means this).  grid = (H, W, top, left): a spatial-window site whose H x W grid the window does not tile - P and W
+    describe the PADDED Hp x Wp grid the kernels run on (Hp = P / W, Wp = W), the real grid lies at (top, left) in it."""
+    __slots__ = ("mode", "dim0", "P", "W", "ws", "Tq", "Tk", "heads", "mask_mode", "drop", "grid")
+
+    def __init__(self, mode, dim0, P, W, ws, Tq, Tk, heads, mask_mode, p_drop, grid=None):
         self.mode, self.dim0, self.P, self.W, self.ws, self.Tq, self.Tk = mode, dim0, P, W, ws, Tq, Tk
         self.heads, self.mask_mode = heads, mask_mode
         self.drop = Drop(p_drop)
+        self.grid = grid
+
+    @property
+    def tiles(self):
+        return self.grid is None
+
+    @classmethod
+    def spatial(cls, frames, H, W, ws, heads, p_drop):
+        """the spatial-window configuration of an H x W grid: the tiling one, or the centre-padded one"""
+        Hp, Wp, top, left = window_pad_geometry(H, W, ws)
+        grid = None if (Hp, Wp) == (H, W) else (H, W, top, left)
+        return cls(0, frames, Hp * Wp, Wp, ws, 0, 0, heads, 0, p_drop, grid)
+
+    def pad_args(self):
+        """(F, H, W, Hp, Wp, top, left) as npvp_grid_center_pad / _cut take them"""
+        H, W, top, left = self.grid
+        return self.dim0, H, W, self.P // self.W, self.W, top, left
+
+    @property
+    def padded_rows(self):
+        """rows of the padded buffers: dim0 * Hp * Wp rounded up to the 32 the weight-gradient GEMM wants (the trailing rows are zeros)"""
+        return -(-self.dim0 * self.P // 32) * 32
 
 
 # Sequences of at least this many rows on either side take the streaming kernels (npvp_attn_long_*: any length); shorter ones the
@@ -1240,6 +1272,8 @@ class _AttnPacked(torch.autograd.Function):
         go = _c(go)
         dqk, dv = torch.empty_like(qk), torch.empty_like(v)
         _attn_bwd(qk[:, :C], qk[:, C:], v, go, dqk[:, :C], dqk[:, C:], dv, ctx.cfg, packed=dqk)
+        if not ctx.cfg.tiles:
+            _zero_tail(ctx.cfg, dqk, dv)
         return dqk, dv, None
 
 
@@ -1642,6 +1676,119 @@ def _raw_posfuse_bwd(dy, x, add, beta_shape, gamma, st, N, T, want_add, sinks=(N
     return du, dadd, dbeta, dgamma
 
 
+# The centre-pad route of spatial window attention (cfg.grid set: the window does not tile the H x W grid; ref/models/VidHRFormer.py:
+# 287-305, 488-511): the q|k and value sources are padded with zero rows BEFORE the in-projection, so a pad token's q, k, v are the bias
+# vectors and it is an ordinary key of its window; the pad queries' outputs are cut away.  _raw_grid_pad / _raw_grid_cut are THE call
+# sites of the two entry points; each is the other's backward.
+def _raw_grid_pad(x2, cfg, want_amax=True, out=None):
+    """x2 [F*H*W, C] -> [cfg.padded_rows, C]: the centre rows are x2's, every other row (border, trailing) is written as zeros.
+    out: write into these rows of an existing buffer instead (x2 = None with a geometry of no frames: zero rows, _zero_tail)"""
+    F_, H, W, Hp, Wp, top, left = cfg.pad_args()
+    rows = cfg.padded_rows
+    if out is None:
+        out = torch.empty(rows, x2.shape[1], dtype=torch.float32, device=x2.device)
+    C = out.shape[1]
+    if (0 if x2 is None else x2.shape[0]) != F_ * H * W or (x2 is not None and x2.stride(1) != 1) or out.shape[0] != rows or out.stride(1) != 1:
+        raise RuntimeError(f"grid pad: {None if x2 is None else tuple(x2.shape)} -> {tuple(out.shape)} is not {F_} frames of {H} x {W} "
+                           f"unit-stride token rows -> {rows} rows")
+    slot = _new_slot(out.device, want_amax)
+    check(lib().npvp_grid_center_pad(_ptr(x2), C if x2 is None else x2.stride(0), _ptr(out), out.stride(0), F_, H, W, Hp, Wp, top, left, C,
+                                     rows, _ptr(slot), _stream()), "npvp_grid_center_pad")
+    return tag_amax(out, slot)
+
+
+def _raw_grid_cut(xp, cfg, addend=None, want_amax=False):
+    """xp [>= F*Hp*Wp, C] -> its centre rows [F*H*W, C] (+ addend)"""
+    F_, H, W, Hp, Wp, top, left = cfg.pad_args()
+    C = xp.shape[1]
+    if xp.shape[0] < F_ * Hp * Wp or xp.stride(1) != 1 or (addend is not None and (addend.shape != (F_ * H * W, C) or addend.stride(1) != 1)):
+        raise RuntimeError(f"grid cut: {tuple(xp.shape)} does not hold {F_} frames of {Hp} x {Wp} unit-stride token rows")
+    out = torch.empty(F_ * H * W, C, dtype=torch.float32, device=xp.device)
+    slot = _new_slot(xp.device, want_amax)
+    check(lib().npvp_grid_center_cut(_ptr(xp), xp.stride(0), _ptr(addend), 0 if addend is None else addend.stride(0), _ptr(out),
+                                     out.stride(0), F_, H, W, Hp, Wp, top, left, C, _ptr(slot), _stream()), "npvp_grid_center_cut")
+    return tag_amax(out, slot)
+
+
+class _ZeroRows:
+    """the geometry of no frames: the pad entry point then writes `padded_rows` zero rows"""
+    __slots__ = ("padded_rows",)
+
+    def __init__(self, rows):
+        self.padded_rows = rows
+
+    def pad_args(self):
+        return 0, 1, 1, 1, 1, 0, 0
+
+
+def _zero_tail(cfg, *ts):
+    """zero rows [F*Hp*Wp, padded_rows) of gradient buffers the attention backward filled up to F*Hp*Wp: they are rows of the
+    weight- and bias-gradient GEMMs.  (A kernel, not a memset: a captured step has no memset node.  No launch when there is no tail.)"""
+    body = cfg.dim0 * cfg.P
+    for t in ts:
+        if t.shape[0] > body:
+            _raw_grid_pad(None, _ZeroRows(t.shape[0] - body), want_amax=False, out=t[body:])
+
+
+class _GridPad(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x2, cfg):
+        remember(ctx)
+        _chk(x2)
+        ctx.cfg = cfg
+        return _raw_grid_pad(_c(x2), cfg)
+
+    @scoped
+    def backward(ctx, g):
+        return _raw_grid_cut(_c(g), ctx.cfg), None
+
+
+class _GridCut(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, xp, cfg):
+        remember(ctx)
+        _chk(xp)
+        ctx.cfg = cfg
+        return _raw_grid_cut(_c(xp), cfg, want_amax=True)
+
+    @scoped
+    def backward(ctx, g):
+        return _raw_grid_pad(_c(g), ctx.cfg), None
+
+
+def grid_pad(x2, cfg):
+    """token rows [F*H*W, C] -> centre-padded [cfg.padded_rows, C] (autograd: the backward is grid_cut)"""
+    return _GridPad.apply(x2, cfg)
+
+
+def grid_cut(xp, cfg):
+    """centre-padded token rows -> [F*H*W, C] (autograd: the backward is grid_pad)"""
+    return _GridCut.apply(xp, cfg)
+
+
+class _RowTail:
+    """The degenerate geometry of the two entry points: one frame, an R x 1 grid with nothing around it, followed by zero rows up to
+    the next multiple of 32 - what a linear layer over R token rows needs where R is no multiple of 32 (the weight-gradient GEMM
+    sums over the rows in steps of 32; zero rows add exact zeros to dW, and the cut hands zero gradient rows back, so db is
+    untouched too)."""
+    __slots__ = ("R", "padded_rows")
+
+    def __init__(self, R):
+        self.R, self.padded_rows = R, -(-R // 32) * 32
+
+    def pad_args(self):
+        return 1, self.R, 1, self.R, 1, 0, 0
+
+
+def linear_any_rows(x, w, b=None):
+    """ops.linear for any number of token rows: zero rows are appended to the input and cut from the output where the count is no
+    multiple of 32 (a 6 x 10 grid's NRMLP tables and event-coding rows); the same call as ops.linear where it is"""
+    if x.shape[0] % 32 == 0:
+        return linear(x, w, b)
+    tail = _RowTail(x.shape[0])
+    return grid_cut(linear(grid_pad(x, tail), w, b), tail)
+
+
 class _SelfAttnSublayer(torch.autograd.Function):
     """y = x + drop(out_proj(attn(q = k = fuse(LN(x) [+ add]), v = LN(x))))   - spatial-window or temporal self-attention
     (ref/models/VidHRFormer.py:87-88,94-107,210-212,217-221): LN, positional fuse (2 kernels), q|k GEMM, v GEMM, attention
@@ -1659,10 +1806,21 @@ class _SelfAttnSublayer(torch.autograd.Function):
         gamma_c = None if gamma is None else _c(gamma)
         add_c = None if add is None else _c(add)
         x1, lst, fused, pst = _raw_ln_posfuse_fwd(x2, lw, lb, eps, add_c, beta_c, gamma_c, N, T)
-        qk = linear_fwd(fused, wqk, bqk)
-        v = linear_fwd(x1, wv, bv)
-        o = torch.empty_like(v)
-        _attn_fwd(qk[:, :C], qk[:, C:], v, o, cfg)
+        if cfg.tiles:
+            qk = linear_fwd(fused, wqk, bqk)
+            v = linear_fwd(x1, wv, bv)
+            o = torch.empty_like(v)
+            _attn_fwd(qk[:, :C], qk[:, C:], v, o, cfg)
+        else:
+            # centre-pad route: both projections and the core run on the padded rows (a zero row projects to the bias), the
+            # out-projection on the real rows.  The padded q|k source is saved IN PLACE of the unpadded one (only the weight
+            # gradient reads it); the padded value source is made again in the backward (x1 itself is needed there anyway)
+            fused = _raw_grid_pad(fused, cfg)
+            qk = linear_fwd(fused, wqk, bqk)
+            v = linear_fwd(_raw_grid_pad(x1, cfg), wv, bv)
+            o_p = torch.empty_like(v)
+            _attn_fwd(qk[:, :C], qk[:, C:], v, o_p, cfg)
+            o = _raw_grid_cut(o_p, cfg, want_amax=True)
         y = linear_fwd(o, wo, bo, residual=x2, drop=drop)
         ctx.save_for_backward(x2, x1, lst, fused, pst, qk, v, o, lw, lb, gamma_c, add_c, wqk, bqk, wv, bv, wo, bo)
         ctx.act_sinks = (ActSink.of(beta), ActSink.of(gamma), ActSink.of(add))
@@ -1679,12 +1837,24 @@ class _SelfAttnSublayer(torch.autograd.Function):
         dy2 = _c(dy).reshape(-1, C)
         dz, ad = masked_grad(dy2, drop, wo)
         do, gwo, gbo = linear_bwd(dz, o, wo, bo, s_o, a_drop=ad)
+        if not cfg.tiles:
+            do = _raw_grid_pad(do, cfg, want_amax=False)            # the pad queries' outputs were cut away: their gradient is 0
         dqk, dv = torch.empty_like(qk), torch.empty_like(v)
         _attn_bwd(qk[:, :C], qk[:, C:], v, do, dqk[:, :C], dqk[:, C:], dv, cfg, packed=dqk)
+        if not cfg.tiles:
+            _zero_tail(cfg, dqk, dv)
+        # (centre-pad route: `fused` holds the padded rows, see forward - the bias gradients sum the pad rows too, they are keys of
+        # their windows, and the weight gradients see their zero rows)
         dfused, gwqk, gbqk = linear_bwd(dqk, fused, wqk, bqk, s_qk)
+        if not cfg.tiles:
+            dfused = _raw_grid_cut(dfused, cfg)
         du, dadd, dbeta, dgamma = _raw_posfuse_bwd(dfused, x1, add, beta_shape, gamma, pst, N, T, ctx.needs_input_grad[6], ctx.act_sinks)
-        # dx1 = dv Wv + du: the second consumer's gradient rides in as the dgrad GEMM's residual input (no separate add)
-        dx1, gwv, gbv = linear_bwd(dv, x1, wv, bv, s_v, residual=du)
+        if cfg.tiles:
+            # dx1 = dv Wv + du: the second consumer's gradient rides in as the dgrad GEMM's residual input (no separate add)
+            dx1, gwv, gbv = linear_bwd(dv, x1, wv, bv, s_v, residual=du)
+        else:
+            dx1, gwv, gbv = linear_bwd(dv, _raw_grid_pad(x1, cfg), wv, bv, s_v)
+            dx1 = _raw_grid_cut(dx1, cfg, addend=du)                # ... here the shapes differ: du rides in as the cut's addend
         dx, glw, glb = _raw_ln_bwd(dx1, x2, lw, lb, lst, dy2, s_ln, probe=True)
         return (dx.view(xshape), glw, glb, None, dbeta, dgamma, dadd, gwqk, gbqk, gwv, gbv, gwo, gbo, None, None, None, None)
 
