@@ -723,12 +723,16 @@ __global__ void frameln_act_bwd_fused_kernel(FlnParams p, const float* __restric
   __shared__ float ared[16];
   const unsigned int peek = amax_peek_block(amax);
   float am = 0.f;
-  if (e >= p.per_frame) { amax_slot_commit_block(amax, am, ared, peek); return; }      // (every thread joins the block's commit)
+  // Every thread joins the block's ONE commit below, at one barrier: a thread past the frame's end only skips the work.  (A commit of
+  // its own for those threads put two barriers into a wave that is partly past the end - per_frame / 4 no multiple of 64 - and
+  // thread 0 then read the block's maxima before that wave's live lanes had left theirs.)
+  const bool live = e < p.per_frame;
   const unsigned long long seed = (p.seed && (p.drop_thresh || p.dp_thresh)) ? *p.seed : 0ull;
-  const float4 ww = ld4(p.w + e), bb = ld4(p.b + e);
-  float4 aw = make_float4(0.f, 0.f, 0.f, 0.f), ab = make_float4(0.f, 0.f, 0.f, 0.f);
+  const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
+  const float4 ww = live ? ld4(p.w + e) : zero4, bb = live ? ld4(p.b + e) : zero4;
+  float4 aw = zero4, ab = zero4;
   const int f0 = blockIdx.y * frames_per_chunk;
-  const int f1 = min(frames, f0 + frames_per_chunk);
+  const int f1 = live ? min(frames, f0 + frames_per_chunk) : f0;
   for (long long f = f0; f < f1; ++f) {
     const long long g0 = f * p.per_frame + e;
     const float mu = p.mean[f], rs = p.rstd[f];
@@ -751,6 +755,7 @@ __global__ void frameln_act_bwd_fused_kernel(FlnParams p, const float* __restric
     am = amax4(am, o);
   }
   amax_slot_commit_block(amax, am, ared, peek);
+  if (!live) return;
   float* o = part + (long long)blockIdx.y * 2 * p.per_frame;
   st4(o + e, aw);
   st4(o + p.per_frame + e, ab);
