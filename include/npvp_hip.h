@@ -396,6 +396,30 @@ int npvp_attn_long_bwd(const float* q, long long ld_q, const float* k, long long
                        float* dk_amax /* may equal dq_amax */, float* dv_amax, void* workspace, long long ws_bytes,
                        npvp_stream_t stream);
 
+/* ---- the stochastic predictor as a sampler: S futures per clip, the context encoded once (forward only).
+ * The reference draws ONE latent per forward (ref/models/Predictor.py:320-322: zo = evt_prior(...), reparameterize at
+ * ref/models/submodules.py:408-410) and its encoder-decoder attention (ref/models/VidHRFormer.py:229-239) sees one query set
+ * per clip; S samples there are S whole forwards.  Here the decoder runs on S * N clips, sample-major (clip s * N + n), while
+ * the memory and its K / V projections stay at N clips.
+ *
+ * npvp_reparam_samples: z[s][i] = mu[i] + expf(0.5f * logvar[i]) * g(ctr), ctr = (sample_base + s) * numel + i in 64 bits,
+ *   g = sqrtf(-2 logf(u1)) * cosf(2 pi u2), u1 = ((r1 >> 8) + 1) * 2^-24, u2 = (r2 >> 8) * 2^-24, r1 / r2 = the library's
+ *   counter hash (the dropout masks' rng_u32) of (seed, salt, 2 ctr) / (seed, salt, 2 ctr + 1).  mu, logvar [numel]; z and the
+ *   nullable eps_out [S][numel] (eps_out receives g).  Sample sample_base + s is the same bits for every S and every split of
+ *   S into calls.  `seed` points to a 64-bit value in DEVICE memory (as for dropout: a captured graph reads a fresh seed on
+ *   replay).  Pointers 16-byte aligned; no amax slot (z is the fuser's `add` operand, which takes none). */
+int npvp_reparam_samples(const float* mu, const float* logvar, float* z, float* eps_out, long long numel, int S,
+                         long long sample_base, const unsigned long long* seed, unsigned int salt, npvp_stream_t stream);
+/* npvp_attn_samples_fwd: the temporal (mode 1) attention core of npvp_attn_fwd, no mask, no dropout, for S query sets per
+ *   clip: q / o rows ((s * N + n) * Tq + t) * P + p, k / v rows (n * Tk + t) * P + p, own row strides as in npvp_attn_fwd,
+ *   head_dim 64, ONE o_amax slot for the whole output.  Tq, Tk <= 32 (the MFMA form; longer sequences are an argument error:
+ *   call npvp_attn_fwd / npvp_attn_long_fwd once per sample slab, the slab being a pointer offset).  One wave loads a (clip,
+ *   pixel, head) group's K / V tiles once and serves `sample_chunk` samples with them (0: the library chooses; any value gives
+ *   the same bits): sample s of o is bit for bit what npvp_attn_fwd writes for that sample's slab of q on the same k / v. */
+int npvp_attn_samples_fwd(const float* q, long long ld_q, const float* k, long long ld_k, const float* v, long long ld_v, float* o,
+                          long long ld_o, int S, int N, int P, int Tq, int Tk, int heads, int head_dim, int sample_chunk,
+                          float* o_amax, npvp_stream_t stream);
+
 /* ---- layout / reductions / masks */
 int npvp_drop_apply(const float* x, float* out, long long rows, int ncols, float p, int mode, int g1, int g2,
                     const unsigned long long* seed, unsigned int salt, float* out_amax, npvp_stream_t stream);

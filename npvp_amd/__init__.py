@@ -33,7 +33,8 @@ from .models import (Predictor, VidHRFormerEncoder, VidHRformerDecoderNAR, VidHR
                      SpatialLocalMultiheadAttention, MlpDWBN, MultiheadAttention, CoorGenerator, NRMLP, PosFeatFuser,
                      EventEncoder, L1Loss, Div_KL, DropPath, ResnetEncoder, ResnetDecoder, build_frozen_autoencoder, to_device_layout,
                      build_autoencoder, prepare_trainable_autoencoder)
-from .trainer import (FlatAdamW, predictor_train_step, full_train_step, predictor_val_step, full_val_step, cosine_warm_restarts_lr, build_predictor_from_cfg,
+from .trainer import (FlatAdamW, predictor_train_step, full_train_step, predictor_val_step, full_val_step, predictor_sample_step, full_sample_step,
+                      cosine_warm_restarts_lr, build_predictor_from_cfg,
                       context_lists, rand_context_collate, rand_context_batch_process, vfi_batch_process,
                       save_lightning_checkpoint, load_lightning_checkpoint, GraphedTrainStep,
                       AEPair, ae_optimizer, ae_train_step, ae_data_parallel, ae_val_step, save_ae_checkpoint, load_ae_checkpoint)
@@ -42,7 +43,8 @@ from . import metrics, data
 
 __all__ = ["Predictor", "VidHRFormerEncoder", "VidHRformerDecoderNAR", "VidHRFormerBlockEnc", "VidHRFormerBlockDecNAR",
            "SpatialLocalMultiheadAttention", "MlpDWBN", "MultiheadAttention", "CoorGenerator", "NRMLP", "PosFeatFuser",
-           "EventEncoder", "L1Loss", "Div_KL", "DropPath", "ResnetEncoder", "ResnetDecoder", "build_frozen_autoencoder", "to_device_layout", "FlatAdamW", "predictor_train_step", "full_train_step", "predictor_val_step", "full_val_step", "context_lists",
+           "EventEncoder", "L1Loss", "Div_KL", "DropPath", "ResnetEncoder", "ResnetDecoder", "build_frozen_autoencoder", "to_device_layout", "FlatAdamW", "predictor_train_step", "full_train_step", "predictor_val_step", "full_val_step", "predictor_sample_step",
+           "full_sample_step", "context_lists",
            "rand_context_collate", "rand_context_batch_process", "vfi_batch_process",
            "save_lightning_checkpoint", "load_lightning_checkpoint", "GraphedTrainStep",
            "cosine_warm_restarts_lr", "build_predictor_from_cfg", "ops", "metrics", "data",

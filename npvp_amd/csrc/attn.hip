@@ -211,6 +211,76 @@ __global__ __launch_bounds__(256) void attn_fwd_mfma_kernel(AttnParams p) {
   amax_slot_commit(p.o_amax, am_o, pk_o);
 }
 
+// ---- S query sets per clip on ONE clip's keys and values (the stochastic predictor's sampler: npvp_attn_samples_fwd).  Temporal
+// (mode 1) geometry, no mask, no dropout.  The decoder of the sampler runs on S * N clips (sample-major: clip s * N + n), the memory
+// and its K / V projections stay at N clips.  One wave owns (clip n, pixel, head, a chunk of samples): it loads that group's K and
+// V tiles into registers once - exactly the tiles attn_fwd_mfma_kernel loads - and then runs that kernel's query-block body
+// (attn_load_r, attn_mm_d, the same scale / maximum / __expf / sum / normalise order, attn_mm_rows, attn_store_d) once per sample
+// of its chunk, so a sample's output is bit for bit what attn_fwd_mfma_kernel writes for that sample's slab of q against the same
+// K / V, whatever the chunk.  The query side's clip index s * N + n is resolved here (gq); AttnRows / attn_row are as they were.
+template <int NQ, int NK>
+__global__ __launch_bounds__(256) void attn_samples_fwd_mfma_kernel(AttnParams p, int nsamp, int nclip, int chunk) {
+  const int lane = threadIdx.x & 63, n = lane & 15, c = lane >> 4;
+  const long long wid = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (wid >= p.total) return;                      // waves are independent: no barriers in this kernel
+  const int head = (int)((unsigned int)wid % (unsigned int)p.heads);
+  const unsigned int gi = (unsigned int)wid / (unsigned int)p.heads, ngroup = (unsigned int)nclip * (unsigned int)p.P;
+  const unsigned int ck = gi / ngroup;             // which chunk of samples
+  AttnRows gk = attn_rows(p, gi - ck * ngroup);    // a = clip n, b = pixel
+  AttnRows gq = gk;
+  const int L = p.L, S = p.S, Tq = p.Tq, Tk = p.Tk;
+  AttnTileR kr[NK];
+  AttnTileG vg[NK];
+  float am_o = 0.f;
+  const unsigned int pk_o = amax_peek_wave(p.o_amax);
+#pragma unroll
+  for (int kb = 0; kb < NK; ++kb) {
+    attn_load_r(kr[kb], p.k, p.ld_k, p, gk, S, Tk, head, n, c, kb);
+    attn_load_g(vg[kb], p.v, p.ld_v, p, gk, S, Tk, head, n, c, kb);
+  }
+  const int s_end = min(nsamp, ((int)ck + 1) * chunk);
+  for (int s = (int)ck * chunk; s < s_end; ++s) {
+    gq.a = s * nclip + gk.a;
+#pragma unroll
+    for (int qb = 0; qb < NQ; ++qb) {
+      AttnTileR qr;
+      attn_load_r(qr, p.q, p.ld_q, p, gq, L, Tq, head, n, c, qb);
+      __builtin_amdgcn_sched_barrier(0);      // all tile loads in flight before the first MFMA waits for one of them
+      // orientation A: sc[kb][i] = S[query 16qb + n][key 16kb + 4c+i]
+      float sc[NK][4], mx = -INFINITY;
+#pragma unroll
+      for (int kb = 0; kb < NK; ++kb) {
+        const f32x4_t sa = attn_mm_d(kr[kb], qr);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const int j = 16 * kb + 4 * c + i;
+          float sv = sa[i] * p.scale;
+          if (j >= S) sv = -INFINITY;
+          sc[kb][i] = sv; mx = fmaxf(mx, sv);
+        }
+      }
+      mx = quad_max(mx);
+      float sum = 0.f;
+#pragma unroll
+      for (int kb = 0; kb < NK; ++kb)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) { sc[kb][i] = (sc[kb][i] == -INFINITY) ? 0.f : __expf(sc[kb][i] - mx); sum += sc[kb][i]; }
+      sum = quad_sum(sum);
+      const float inv = 1.f / sum;
+      f32x4_t o[4];
+      attn_zero(o);
+#pragma unroll
+      for (int kb = 0; kb < NK; ++kb) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) sc[kb][i] *= inv;
+        attn_mm_rows(o, sc[kb], vg[kb]);
+      }
+      attn_store_d(o, p.o, p.ld_o, p, gq, L, Tq, head, n, c, qb, am_o);
+    }
+  }
+  amax_slot_commit(p.o_amax, am_o, pk_o);
+}
+
 template <int NQ, int NK>
 __global__ __launch_bounds__(256) void attn_bwd_mfma_kernel(AttnParams p) {
   const int lane = threadIdx.x & 63, n = lane & 15, c = lane >> 4;
@@ -975,6 +1045,52 @@ extern "C" int npvp_attn_fwd(const float* q, long long ld_q, const float* k, lon
   else if (nq == 1) NPVP_LAUNCH((attn_fwd_mfma_kernel<1, 2>), mg, mb, 0, stream, p);
   else if (nk == 1) NPVP_LAUNCH((attn_fwd_mfma_kernel<2, 1>), mg, mb, 0, stream, p);
   else NPVP_LAUNCH((attn_fwd_mfma_kernel<2, 2>), mg, mb, 0, stream, p);
+  NPVP_CHECK_LAUNCH();
+  return NPVP_OK;
+}
+
+// S query sets per clip on one clip's K / V (see include/npvp_hip.h and attn_samples_fwd_mfma_kernel).
+extern "C" int npvp_attn_samples_fwd(const float* q, long long ld_q, const float* k, long long ld_k, const float* v, long long ld_v,
+                                     float* o, long long ld_o, int S, int N, int P, int Tq, int Tk, int heads, int head_dim,
+                                     int sample_chunk, float* o_amax, hipStream_t stream) {
+  NPVP_CHECK_ARG(head_dim == HD, "attn_samples: head_dim must be 64");
+  NPVP_CHECK_ARG(S > 0 && N > 0 && P > 0 && heads > 0, "attn_samples: empty batch");
+  NPVP_CHECK_ARG(Tq >= 1 && Tk >= 1 && Tq <= 32 && Tk <= 32,
+                 "attn_samples: sequence length must be in [1,32] (longer: npvp_attn_fwd / npvp_attn_long_fwd per sample)");
+  NPVP_CHECK_ARG(sample_chunk >= 0, "attn_samples: sample_chunk must be 0 (the library chooses) or positive");
+  NPVP_CHECK_ARG(q && k && v && o, "attn_samples: null operand");
+  NPVP_CHECK_ARG(ld_q % 4 == 0 && ld_k % 4 == 0 && ld_v % 4 == 0 && ld_o % 4 == 0, "attn_samples: row strides must be multiples of 4");
+  const long long base = (long long)N * P * heads;          // waves at one chunk: (clip, pixel, head)
+  // Samples per wave.  A larger chunk amortises a wave's K / V tile loads over more query sets, but those run one after the other
+  // in the wave, and this kernel is bound by the latency of its loads, which only other resident waves hide: the chip has
+  // 256 CUs x 4 SIMDs, up to 8 waves per SIMD, and the kernel's registers (78 .. 121 VGPRs + 20 AGPRs by template form) admit
+  // 3 (two key blocks) or 4 of them - so keep at least 4 waves per SIMD = 4096 waves in the launch, the most any form can hold
+  // (N = 1, P = 64, 8 heads is 512 per chunk: S = 32 -> chunks of 4), and stop at 8 samples per wave, where the K / V traffic is
+  // already an eighth of the replicated form's.  A tuning choice only: the chunk does not enter any output bit.
+  long long chunk = sample_chunk;
+  if (chunk == 0) {
+    chunk = base * S / 4096;
+    if (chunk > 8) chunk = 8;
+    if (chunk < 1) chunk = 1;
+  }
+  if (chunk > S) chunk = S;
+  const long long nchunk = (S + chunk - 1) / chunk;
+  AttnParams p = {};
+  p.mode = 1; p.heads = heads; p.P = P; p.Tq = Tq; p.Tk = Tk; p.L = Tq; p.S = Tk; p.nww = p.nwin = 1;
+  p.scale = 0.125f;   // 1/sqrt(64)
+  p.total = base * nchunk;
+  // (group, head) and token rows are resolved in 32-bit arithmetic (AttnRows); the query side has S * N clips
+  const long long rows_q = (long long)S * N * P * Tq, rows_k = (long long)N * P * Tk;
+  if (p.total >= (1ll << 31) || rows_q >= (1ll << 31) || rows_k >= (1ll << 31)) {
+    npvp_set_error("attn_samples: too many token rows / (group, head, chunk) waves for one launch"); return NPVP_ERR_ARG;
+  }
+  p.q = q; p.k = k; p.v = v; p.o = o; p.ld_q = ld_q; p.ld_k = ld_k; p.ld_v = ld_v; p.ld_o = ld_o; p.o_amax = o_amax;
+  const dim3 mg((unsigned)((p.total + 3) / 4)), mb(256);
+  const int nq = (Tq + 15) / 16, nk = (Tk + 15) / 16, ck = (int)chunk;
+  if (nq == 1 && nk == 1) NPVP_LAUNCH((attn_samples_fwd_mfma_kernel<1, 1>), mg, mb, 0, stream, p, S, N, ck);
+  else if (nq == 1) NPVP_LAUNCH((attn_samples_fwd_mfma_kernel<1, 2>), mg, mb, 0, stream, p, S, N, ck);
+  else if (nk == 1) NPVP_LAUNCH((attn_samples_fwd_mfma_kernel<2, 1>), mg, mb, 0, stream, p, S, N, ck);
+  else NPVP_LAUNCH((attn_samples_fwd_mfma_kernel<2, 2>), mg, mb, 0, stream, p, S, N, ck);
   NPVP_CHECK_LAUNCH();
   return NPVP_OK;
 }

@@ -96,3 +96,55 @@ def pred_ave_metrics(model, data_loader, metric_func, renorm_transform, num_futu
                 ave_metric[i] += float(m) * pred_t.shape[0]
             sample_num += pred.shape[0]
     return ave_metric / sample_num
+
+
+def best_of_samples(pred, target, metric_func, higher_is_better=True):
+    """Best-of-S evaluation of a stochastic predictor, on the device: pred (N, S, T, C, H, W) - what Predictor.sample and
+    predictor_sample_step return - against target (N, T, C, H, W) under the per-image form (`mean_flag=False`) of `SSIM` / `PSNR` /
+    `MSEScore`.  -> best_idx [N] (the sample with the best mean over T; ties go to the lowest index), best [N, T] (that sample's
+    per-step values) and all [N, S, T].  One metric call per sample on the N * T frames of that sample's slab pred[:, s] (contiguous
+    in the sampler's sample-major result; a per-image metric gives every image the same value however the images are batched).
+    Nothing is converted to a host number in here."""
+    if pred.dim() != 6 or target.dim() != 5 or pred.shape[0] != target.shape[0] or pred.shape[2:] != target.shape[1:]:
+        raise ValueError(f"best_of_samples: pred (N, S, T, C, H, W) and target (N, T, C, H, W) are needed, got {tuple(pred.shape)} "
+                         f"and {tuple(target.shape)}")
+    N, S, T = pred.shape[:3]
+    img = tuple(pred.shape[3:])
+    tgt = target.reshape((N * T,) + img)
+    vals = [metric_func(pred[:, s].reshape((N * T,) + img), tgt, mean_flag=False).reshape(N, T) for s in range(S)]
+    every = torch.stack(vals, dim=1)                                  # [N, S, T]
+    score = every.mean(dim=2)                                         # [N, S]
+    top = score.max(dim=1, keepdim=True).values if higher_is_better else score.min(dim=1, keepdim=True).values
+    order = torch.arange(S, device=score.device).expand(N, S)
+    best_idx = torch.where(score == top, order, torch.full_like(order, S)).min(dim=1).values      # lowest index among the ties
+    best = every.gather(1, best_idx.view(N, 1, 1).expand(N, 1, T)).squeeze(1)
+    return best_idx, best, every
+
+
+def pred_best_metrics(model, data_loader, metric_func, renorm_transform, num_future_frames, n_samples, seed, higher_is_better=True,
+                      ckpt=None, device='cuda:0'):
+    """The best-of-S counterpart of `pred_ave_metrics`: per-time-step average over a data loader of the best sample's `metric_func`
+    (per clip: the sample with the best mean over the future steps).  `model.sample(past_frames, n_samples, seed=seed,
+    sample_base=k)` must give the sampled frames (N, S, Tp, C, H, W); batch b draws samples b * n_samples .. of the seed's stream.
+    One host transfer per batch (the [Tp] sums), none per time-step."""
+    if ckpt is not None:
+        from .trainer import load_lightning_checkpoint
+        load_lightning_checkpoint(ckpt, getattr(model, "predictor", model))
+    model = model.eval()
+    ave_metric = np.zeros(num_future_frames)
+    sample_num = 0
+    with torch.no_grad():
+        for b, (past_frames, future_frames) in enumerate(data_loader):
+            past_frames, future_frames = past_frames.to(device), future_frames.to(device)
+            pred = model.sample(past_frames, n_samples, seed=seed, sample_base=b * n_samples)
+            N, S, T = pred.shape[:3]
+            img = tuple(pred.shape[3:])
+            # renormalise frame by frame, in the sample-major order the sampler produced (no re-layout of its result)
+            p = renorm_transform(pred.permute(1, 0, 2, 3, 4, 5).reshape((S * N * T,) + img))
+            p = p.view((S, N, T) + tuple(p.shape[1:])).permute(1, 0, 2, 3, 4, 5)
+            g = renorm_transform(future_frames.reshape((N * T,) + img))
+            g = g.view((N, T) + tuple(g.shape[1:]))
+            _, best, _ = best_of_samples(p[:, :, :num_future_frames], g[:, :num_future_frames], metric_func, higher_is_better)
+            ave_metric += best.sum(dim=0).double().cpu().numpy()
+            sample_num += N
+    return ave_metric / sample_num

@@ -124,6 +124,70 @@ class Predictor(nn.Module):
         mu_o = self.evt_posterior.forward_canonical(obs_evt, H, W)
         return self._decode(mu_o, memory, op, pp)
 
+    # -- the stochastic model as a sampler: S futures per clip, the context encoded once ---------------
+    SAMPLE_SALT = 0x53414D50          # the sampler's stream of the counter hash (dropout sites count 1, 2, ... per step)
+
+    def sample_seed_tensor(self, seed, dev):
+        """the device-resident seed of the sampler: the scheduling context's seed tensor (seed None), or a tensor of the sampler's
+        own that receives the given int (a device fill: no host read, and the trainer's mask stream is left alone)"""
+        if seed is None:
+            return ops.current().rng.seed_tensor(dev)
+        t = getattr(self, "_sample_seed", None)
+        if t is None or t.device != dev:
+            t = self._sample_seed = torch.zeros(1, dtype=torch.int64, device=dev)
+        t.fill_(int(seed) & 0x7FFFFFFFFFFFFFFF)
+        return t
+
+    def sample_context(self, observed_features):
+        """Everything of a sampled forward that depends on the context only, run ONCE whatever the number of samples: positional
+        tables, the EVT_Former encoder, the prior head (ref Predictor.py:312-321 up to the draw).  Call under no_grad in eval
+        mode (`sample` does); -> the state `sample_decode` takes."""
+        if not self.stochastic:
+            raise ValueError("Predictor.sample needs a stochastic predictor (stochastic=True): a deterministic one has one future")
+        H, W = observed_features.shape[-2:]
+        op = self._pos(self.observed_coor)
+        pp = self._pos(self.predict_coor)
+        memory, obs_evt = self._encode(observed_features, op)
+        _, mu, logvar = self.evt_prior.forward_canonical(obs_evt, H, W, draw=False)
+        return dict(memory=memory, mu=mu, logvar=logvar, op=op, pp=pp, HW=(H, W))
+
+    def sample_decode(self, ctx, n_samples, seed_t, sample_base=0, return_eps=False):
+        """S = n_samples futures from one `sample_context`: z [S, N, H*W, C] from the device sampler (samples sample_base ..
+        sample_base + S - 1 of the stream of `seed_t`), the decoder on S*N clips, sample-major, against the N-clip memory.
+        -> (N, S, Tp, C, H, W), a permuted view of the sample-major result (S*N, Tp, C, H, W); with return_eps also eps and z
+        [S, N, H*W, C] (canonical layout)."""
+        S = int(n_samples)
+        if S < 1:
+            raise ValueError("Predictor.sample: n_samples must be at least 1")
+        memory, mu = ctx["memory"], ctx["mu"]
+        N, T1, H, W, C = memory.shape
+        z = ops.reparam_samples(mu, ctx["logvar"], S, seed_t, self.SAMPLE_SALT, sample_base, return_eps)
+        z, eps = z if return_eps else (z, None)
+        out = self.transformer.forward_canonical(z.view(S * N, H, W, C), memory, ctx["op"], ctx["pp"], self.fuser, self.TP, nchw=True,
+                                                 samples=S)
+        out = out.view(S, N, self.TP, C, H, W).permute(1, 0, 2, 3, 4, 5)
+        return (out, eps, z) if return_eps else out
+
+    def sample(self, observed_features, n_samples, seed=None, sample_base=0, return_eps=False):
+        """observed_features (N, To, C, H, W) -> n_samples futures per clip, (N, S, Tp, C, H, W) [, eps [S, N, H*W, C]].
+        The eval forward (ref Predictor.py:312-322) with S draws of zo instead of one: positional tables, encoder and prior
+        head run once, the latent comes from the device sampler (ops.reparam_samples; `evt_prior.eps_fn` is not consulted), the
+        decoder runs on S*N clips against the N-clip memory.  seed None: the scheduling context's device seed; an int: that value.
+        Sample sample_base + s of a seed is the same latent however S is cut into calls.  Runs under no_grad with eval
+        behaviour; the module's train / eval state is restored."""
+        if not self.stochastic:
+            raise ValueError("Predictor.sample needs a stochastic predictor (stochastic=True): a deterministic one has one future")
+        was_training = self.training
+        self.eval()
+        try:
+            with torch.no_grad():
+                ctx = self.sample_context(observed_features)
+                seed_t = self.sample_seed_tensor(seed, observed_features.device)
+                res = self.sample_decode(ctx, n_samples, seed_t, sample_base, return_eps)
+        finally:
+            self.train(was_training)
+        return (res[0], res[1]) if return_eps else res
+
     def evt_coding_forward(self, x, pos_beta, pos_gamma):
         """x (N,T,C,H,W) -> (encoder output (N,T,C,H,W), event coding (N,C,H,W))   ref :337-350"""
         N, T, C, H, W = x.shape

@@ -413,6 +413,32 @@ class VidHRFormerBlockDecNAR(nn.Module):
         x, x1 = ops.layernorm_res(x, self.norm6.weight, self.norm6.bias, self.norm6.eps)
         return self.SpatialFFN1.fused(x1, x, dp)                                                                     # :243
 
+    def forward_samples(self, tgt, query_evt, memory, memory_pos, tgt_pos, pos_fuser, fused_memory, samples):
+        """The sampler's route (forward only, eval behaviour, stock fuser): tgt (S*N,T2,H,W,C) and query_evt (S*N,H,W,C) hold
+        S = `samples` draws per clip, sample-major (clip s*N + n); memory / fused_memory stay at the N clips (N,T1,H,W,C).  `forward`
+        in eval mode, sub-layer for sub-layer, on the batch S*N - except the encoder-decoder site, whose K / V side is shared by a
+        clip's samples (ops.cross_attn_samples) instead of replicated."""
+        B, T2, H, W, C = tgt.shape
+        S = int(samples)
+        N, T1, P = memory.shape[0], memory.shape[1], H * W
+        if self.training:
+            raise RuntimeError("VidHRFormerBlockDecNAR.forward_samples: the sampler has eval behaviour only (call .eval() first)")
+        if B != S * N or not _stock_fuser(pos_fuser):
+            raise ValueError("VidHRFormerBlockDecNAR.forward_samples: tgt must hold samples * N clips, and the stock PosFeatFuser('layer')")
+        tb, tg = tgt_pos
+        tgt, query_evt = tgt.contiguous(), query_evt.contiguous()
+        nd = ops.NO_DROP
+        x = ops.self_attn_sublayer(tgt, self.norm1, tb, tg, query_evt, self.SLMHSA.attn, self.SLMHSA._cfg(B, T2, H, W), nd, B, T2)
+        x, x1 = ops.layernorm_res(x, self.norm2.weight, self.norm2.bias, self.norm2.eps)
+        x = self.SpatialFFN.fused(x1, x, 0.0)
+        x = ops.self_attn_sublayer(x, self.norm3, tb, tg, None, self.temporal_MHSA,
+                                   AttnCfg(1, B, P, W, 0, T2, T2, self.num_heads, 0, 0.0), nd, B, T2)
+        x = ops.ffn_sublayer(x, self.norm4, self.linear1, self.linear2, 0.0)
+        x = ops.cross_attn_samples(x, self.norm5, tb, tg, query_evt, fused_memory, memory, self.EncDecAttn,
+                                   AttnCfg(1, N, P, W, 0, T2, T1, self.num_heads, 0, 0.0), S, N, T2)              # ref :229-239
+        x, x1 = ops.layernorm_res(x, self.norm6.weight, self.norm6.bias, self.norm6.eps)
+        return self.SpatialFFN1.fused(x1, x, 0.0)
+
 
 class VidHRformerDecoderNAR(nn.Module):
     """ref/models/VidHRFormer.py:118-161 (return_intermediate=False)."""
@@ -426,9 +452,13 @@ class VidHRformerDecoderNAR(nn.Module):
                                                          Spatial_FFN_hidden_ratio, dim_feedforward), num_layers)
         self.num_layers, self.norm, self.return_intermediate = num_layers, norm, return_intermediate
 
-    def forward_canonical(self, qe, memory, memory_pos, tgt_pos, pos_fuser, T2, nchw=False):
+    def forward_canonical(self, qe, memory, memory_pos, tgt_pos, pos_fuser, T2, nchw=False, samples=1):
         """qe (N,H,W,C), memory (N,T1,H,W,C) canonical -> (N,T2,H,W,C) canonical, after LN + ReLU
-        (nchw=True: the reference's (N,T2,C,H,W) layout instead)."""
+        (nchw=True: the reference's (N,T2,C,H,W) layout instead).
+        samples = S > 1 (forward only, eval behaviour): qe (S*N,H,W,C) holds S event latents per clip, sample-major (clip s*N + n), memory
+        stays at N clips; -> (S*N,T2,...).  Memory, its fused form and every layer's K / V projection are never repeated S times."""
+        if samples != 1:
+            return self._forward_samples(qe, memory, memory_pos, tgt_pos, pos_fuser, T2, nchw, int(samples))
         N, H, W, C = qe.shape
         out = torch.zeros(N, T2, H, W, C, dtype=torch.float32, device=qe.device)
         # memory and its fused form are the key / value sources of all the layers' encoder-decoder attention: fan_out lets the
@@ -445,6 +475,37 @@ class VidHRformerDecoderNAR(nn.Module):
         else:
             out = torch.relu(out)
         return ops.canonical_to_nchw(out, N, T2, H, W) if nchw else out
+
+    def _final(self, out, B, T2, H, W, nchw):
+        if nchw and self.norm is not None and ops.layernorm_nchw_supported(out, H, W):
+            return ops.layernorm_nchw(out, self.norm.weight, self.norm.bias, self.norm.eps, True, B, T2, H, W)
+        if self.norm is not None:
+            out = ops.layernorm(out, self.norm.weight, self.norm.bias, self.norm.eps, relu=True)
+        else:
+            out = torch.relu(out)
+        return ops.canonical_to_nchw(out, B, T2, H, W) if nchw else out
+
+    def _forward_samples(self, qe, memory, memory_pos, tgt_pos, pos_fuser, T2, nchw, S):
+        B, H, W, C = qe.shape
+        N = memory.shape[0]
+        if S < 1 or B != S * N:
+            raise ValueError(f"VidHRformerDecoderNAR: samples={S} needs qe of samples * N = {S * N} clips, got {B}")
+        if (torch.is_grad_enabled() and (qe.requires_grad or memory.requires_grad)) or self.training:
+            raise RuntimeError("VidHRformerDecoderNAR: the sampled route is forward only with eval behaviour (no_grad, .eval())")
+        fused_memory = pos_fuser(memory, *memory_pos)
+        if not _stock_fuser(pos_fuser):
+            # another fuser: per-sample calls of the existing path (memory and its fused form still made once)
+            outs = []
+            for s in range(S):
+                out = torch.zeros(N, T2, H, W, C, dtype=torch.float32, device=qe.device)
+                for layer in self.layers:
+                    out = layer(out, qe[s * N:(s + 1) * N], memory, memory_pos, tgt_pos, pos_fuser, fused_memory)
+                outs.append(out)
+            return self._final(torch.cat(outs, 0), B, T2, H, W, nchw)
+        out = torch.zeros(B, T2, H, W, C, dtype=torch.float32, device=qe.device)
+        for layer in self.layers:
+            out = layer.forward_samples(out, qe, memory, memory_pos, tgt_pos, pos_fuser, fused_memory, S)
+        return self._final(out, B, T2, H, W, nchw)
 
     def forward(self, query_evt, memory, memory_pos, tgt_pos, pos_fuser):
         """query_evt (N,T2,C,H,W), memory (N,T1,C,H,W) -> (N,T2,C,H,W)   (reference signature)"""

@@ -125,8 +125,9 @@ class EventEncoder(nn.Module):
             self.logvar_net = nn.Conv2d(hidden_channels, in_channels, 1, 1, bias=True)
         self.eps_fn = None   # test hook: callable(shape (N,C,H,W)) -> eps
 
-    def forward_canonical(self, x, H, W):
-        """x [N, H*W, C] -> mu (and z, logvar) as [N, H*W, C]."""
+    def forward_canonical(self, x, H, W, draw=True):
+        """x [N, H*W, C] -> mu (and z, logvar) as [N, H*W, C].  draw=False (Predictor.sample, which draws its latents with
+        ops.reparam_samples): neither eps_fn nor the host generator is consulted, z comes back as None."""
         N, P, C = x.shape
         w1 = self.conv1[0].weight                                        # [C,1,3,3] depthwise, no bias
         wtb = torch.cat([ops._Transpose.apply(w1.reshape(1, C, 9)).reshape(9, C), torch.zeros(1, C, device=x.device)], 0)
@@ -143,6 +144,8 @@ class EventEncoder(nn.Module):
         if not self.stochastic:
             return mu
         logvar = ops.linear_any_rows(h, self.logvar_net.weight.flatten(1), self.logvar_net.bias).view(N, P, C)
+        if not draw:
+            return None, mu, logvar
         if self.eps_fn is not None:
             eps = ops.transpose(self.eps_fn((N, C, H, W)).reshape(N, C, P))
         else:

@@ -1227,6 +1227,33 @@ def _attn_fwd(q, k, v, o, cfg):
     tag_amax(o, slot)
 
 
+ATTN_SAMPLES_MAX = 32      # longest sequence npvp_attn_samples_fwd takes (the one- and two-block MFMA form)
+
+
+def _attn_samples_fwd(q, k, v, o, cfg, S, sample_chunk=0):
+    """The sampler's encoder-decoder core (forward only, no mask, no dropout): q / o hold S * cfg.dim0 clips, sample-major, k / v the
+    cfg.dim0 clips of the memory - never replicated.  Up to 32 rows per side: ONE launch of npvp_attn_samples_fwd (a wave loads a
+    group's K / V tiles once for several samples).  Longer: one call of the existing forward entry points per sample slab (the slab
+    of a sample is contiguous: a pointer offset), `_attn_long` choosing between them as in `_attn_fwd`, every call on the same k / v
+    and the same amax slot (a slot is a maximum: exact)."""
+    if cfg.mode != 1 or cfg.mask_mode != 0 or cfg.drop.on:
+        raise ValueError("_attn_samples_fwd: temporal geometry without mask and dropout only")
+    hd = o.shape[1] // cfg.heads
+    slot = _new_slot(q.device)
+    if max(cfg.Tq, cfg.Tk) <= ATTN_SAMPLES_MAX:
+        check(lib().npvp_attn_samples_fwd(_ptr(q), q.stride(0), _ptr(k), k.stride(0), _ptr(v), v.stride(0), _ptr(o), o.stride(0),
+                                          S, cfg.dim0, cfg.P, cfg.Tq, cfg.Tk, cfg.heads, hd, sample_chunk, _ptr(slot), _stream()),
+              "npvp_attn_samples_fwd")
+    else:
+        fn, what = (lib().npvp_attn_long_fwd, "npvp_attn_long_fwd") if _attn_long(cfg) else (lib().npvp_attn_fwd, "npvp_attn_fwd")
+        rows = cfg.dim0 * cfg.Tq * cfg.P          # query rows of one sample
+        for s in range(S):
+            check(fn(q.data_ptr() + 4 * s * rows * q.stride(0), q.stride(0), _ptr(k), k.stride(0), _ptr(v), v.stride(0),
+                     o.data_ptr() + 4 * s * rows * o.stride(0), o.stride(0), 1, cfg.dim0, cfg.P, cfg.W, 0, cfg.Tq, cfg.Tk, cfg.heads,
+                     hd, 0, 0.0, None, 0, _ptr(slot), _stream()), what)
+    tag_amax(o, slot)
+
+
 def _attn_bwd(q, k, v, go, dq, dk, dv, cfg, packed=None):
     """packed: the [R, 2C] tensor dq and dk are the halves of (one amax slot for both, tagged on it)"""
     hd = go.shape[1] // cfg.heads
@@ -1963,6 +1990,55 @@ def cross_attn_sublayer(x, norm, beta, gamma, add, key, memory, mha, cfg, drop, 
     w, b = mha.in_proj_weight, mha.in_proj_bias
     return _CrossAttnSublayer.apply(x, norm.weight, norm.bias, norm.eps, beta, gamma, add, key, memory, w[:C], b[:C], w[C:2 * C],
                                     b[C:2 * C], w[2 * C:], b[2 * C:], mha.out_proj.weight, mha.out_proj.bias, cfg, drop, N, T)
+
+
+def _no_grad_inputs(what, *ts):
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in ts):
+        raise RuntimeError(f"{what} is forward only: call it under torch.no_grad() or on tensors that do not require grad")
+
+
+def cross_attn_samples(x, norm, beta, gamma, add, key, memory, mha, cfg, S, N, T):
+    """The encoder-decoder sub-layer of the sampler (forward only): the arithmetic of _CrossAttnSublayer.forward with `drop` off for
+    x of S * N clips (sample-major) and add [S * N, H, W, C], against key / memory of N clips.  LN + positional fuse + Q projection
+    run on the S * N clips, the K and V projections on the N clips, the core is _attn_samples_fwd (cfg: the N-clip temporal
+    configuration, cfg.dim0 == N), then the out-projection with the residual."""
+    w, b = mha.in_proj_weight, mha.in_proj_bias
+    _no_grad_inputs("cross_attn_samples", x, add, key, memory, beta, gamma, w, b, mha.out_proj.weight, mha.out_proj.bias, norm.weight, norm.bias)
+    _chk(x, beta, gamma, add, key, memory, w, b)
+    if cfg.dim0 != N or x.shape[0] != S * N:
+        raise ValueError(f"cross_attn_samples: x must hold S * N = {S * N} clips and cfg the N = {N} clips of the memory")
+    C = mha.embed_dim
+    with torch.no_grad():
+        x2 = _c(x).reshape(-1, C)
+        k2, m2 = _c(key).reshape(-1, C), _c(memory).reshape(-1, C)
+        _, _, query, _ = _raw_ln_posfuse_fwd(x2, norm.weight, norm.bias, norm.eps, None if add is None else _c(add), _c(beta),
+                                             None if gamma is None else _c(gamma), S * N, T)
+        q = linear_fwd(query, w[:C], b[:C])
+        k = linear_fwd(k2, w[C:2 * C], b[C:2 * C])
+        v = linear_fwd(m2, w[2 * C:], b[2 * C:])
+        o = torch.empty_like(q)
+        _attn_samples_fwd(q, k, v, o, cfg, S)
+        y = linear_fwd(o, mha.out_proj.weight, mha.out_proj.bias, residual=x2)
+    return y.view(x.shape)
+
+
+def reparam_samples(mu, logvar, S, seed, salt, sample_base=0, return_eps=False):
+    """S draws of z = mu + exp(0.5 logvar) * eps (ref/models/submodules.py:408-410) in one launch: -> z [S, *mu.shape] (and eps, same
+    shape).  eps is Box-Muller over the library's counter hash of (seed, salt, element index in the array of ALL samples): sample
+    sample_base + s has the same bits for every S and every split of S into calls (csrc/sample.hip has the formula).  seed: a
+    one-element int64 DEVICE tensor (the scheduling context's seed tensor, or one of the caller's); salt: an int below 2^32."""
+    _no_grad_inputs("reparam_samples", mu, logvar)
+    _chk(mu, logvar)
+    if mu.shape != logvar.shape:
+        raise ValueError("reparam_samples: mu and logvar must have one shape")
+    if not (seed.is_cuda and seed.dtype == torch.int64 and seed.numel() == 1):
+        raise ValueError("reparam_samples: seed must be a one-element int64 tensor on the device")
+    mu_c, lv_c = _c(mu.detach()), _c(logvar.detach())
+    z = torch.empty((S,) + tuple(mu.shape), dtype=torch.float32, device=mu.device)
+    eps = torch.empty_like(z) if return_eps else None
+    check(lib().npvp_reparam_samples(_ptr(mu_c), _ptr(lv_c), _ptr(z), _ptr(eps), mu_c.numel(), S, sample_base, _ptr(seed),
+                                     int(salt) & 0xFFFFFFFF, _stream()), "npvp_reparam_samples")
+    return (z, eps) if return_eps else z
 
 
 def ffn_sublayer(x, norm, lin1, lin2, p):

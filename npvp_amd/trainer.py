@@ -345,6 +345,54 @@ def full_val_step(predictor, enc, dec, past_frames, future_frames, lam_PF_L1=0.0
                               future_frames=future_frames, sync=sync)
 
 
+def predictor_sample_step(predictor, past_feats, n_samples, seed=None, frozen_dec=None, chunk=None, sample_base=0, return_eps=False):
+    """n_samples futures per clip from a stochastic predictor (Predictor.sample): -> predicted features (N, S, Tp, C, H, W), or the
+    frames (N, S, Tp, c, h, w) of `frozen_dec` when one is given.  chunk (None = all at once): the samples are decoded `chunk` at a
+    time, one piece after the other - the encoder / prior part still runs ONCE for all pieces, and a sample's latent does not depend
+    on the cut (the pieces only see other GEMM row counts: rounding).  return_eps: also eps and z, each [S, N, H*W, C].  Eval
+    behaviour under no_grad; the module's train / eval state is restored (as predictor_val_step does)."""
+    if not predictor.stochastic:
+        raise ValueError("predictor_sample_step needs a stochastic predictor (stochastic=True)")
+    S = int(n_samples)
+    step = S if chunk is None else int(chunk)
+    if S < 1 or step < 1:
+        raise ValueError("predictor_sample_step: n_samples and chunk must be at least 1")
+    was_training = predictor.training
+    predictor.eval()
+    try:
+        with torch.no_grad():
+            ctx = predictor.sample_context(past_feats)
+            seed_t = predictor.sample_seed_tensor(seed, past_feats.device)
+            preds, epss, zs = [], [], []
+            for s0 in range(0, S, step):
+                res = predictor.sample_decode(ctx, min(step, S - s0), seed_t, sample_base + s0, return_eps)
+                pred = res[0] if return_eps else res                            # (N, s, Tp, C, H, W)
+                if frozen_dec is not None:
+                    N, s, Tp = pred.shape[:3]
+                    # the decoder takes (B, T, C, H, W): the sample-major result as it is, B = s * N
+                    fr = frozen_dec(pred.permute(1, 0, 2, 3, 4, 5).reshape((s * N, Tp) + tuple(pred.shape[3:])))
+                    pred = fr.view((s, N) + tuple(fr.shape[1:])).permute(1, 0, 2, 3, 4, 5)
+                preds.append(pred)
+                if return_eps:
+                    epss.append(res[1]); zs.append(res[2])
+            pred = preds[0] if len(preds) == 1 else torch.cat(preds, 1)
+    finally:
+        predictor.train(was_training)
+    if return_eps:
+        return pred, torch.cat(epss, 0), torch.cat(zs, 0)
+    return pred
+
+
+def full_sample_step(predictor, enc, dec, past_frames, n_samples, seed=None, chunk=None, sample_base=0, return_eps=False):
+    """predictor_sample_step from pixels: frozen encoder on the past frames, n_samples sampled futures, frozen decoder ->
+    frames (N, S, Tp, c, h, w)."""
+    enc.eval(); dec.eval()
+    with torch.no_grad():
+        past_feats = enc(past_frames)
+    return predictor_sample_step(predictor, past_feats, n_samples, seed, frozen_dec=dec, chunk=chunk, sample_base=sample_base,
+                                 return_eps=return_eps)
+
+
 # ---- batch shaping of the reference's other Stage-2 modes (ref/models/Predictor.py:30-40,62-70,241-262 and the
 # ---- random-context collate ref/utils/dataset.py:162-178): SURVEY 8f "next" row #2
 def context_lists(P, num_past, num_future):
