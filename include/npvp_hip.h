@@ -116,6 +116,21 @@ int npvp_gemm_f32(int a_kc, int b_kc, int M, int N, int K, const float* A, long 
                   const void* b_pre, int accumulate, float* rowstats, const float* a_amax, const float* b_amax,
                   float* c_amax, unsigned int* range_flag, float adrop_p, int adrop_g1, int adrop_g2, unsigned int adrop_salt,
                   void* workspace, long long ws_bytes, npvp_stream_t stream);
+/* npvp_gemm_f32 with a ROW-SKIP spec (a_kc = 1 only): (skip_p, skip_g1, skip_g2, skip_salt) name, like adrop, the row groups
+ * (row / g1) % g2 that a DropPath site drops - rows whose result the caller multiplies by an exact 0 (forward) or whose rows of A
+ * are exact zeros (dgrad).  On the precision-6 forward / dgrad kernels (ids 5 / 7) a tile all of whose rows lie in dropped groups
+ * is not computed - no operand loads, no K loop, no row-guard pass - and runs its usual epilogue on zero accumulators, so C, the
+ * rowstats partials and c_amax are written as always and a dropped row of a forward launch holds the bias.  Tiles that touch a kept
+ * group, and every other kernel, compute as npvp_gemm_f32 does.  The decision is taken on the device from `seed`; skip_p = 0 is
+ * npvp_gemm_f32. */
+int npvp_gemm_f32_skip(int a_kc, int b_kc, int M, int N, int K, const float* A, long long lda, const float* B, long long ldb,
+                       float* C, long long ldc, const float* bias, int act, const float* aux_in, float* aux_out,
+                       const float* residual, long long ldr, float drop_p, int drop_mode, int drop_g1, int drop_g2,
+                       const unsigned long long* seed, unsigned int salt, float alpha, int precision, float* colsum_a,
+                       const void* b_pre, int accumulate, float* rowstats, const float* a_amax, const float* b_amax,
+                       float* c_amax, unsigned int* range_flag, float adrop_p, int adrop_g1, int adrop_g2, unsigned int adrop_salt,
+                       float skip_p, int skip_g1, int skip_g2, unsigned int skip_salt, void* workspace, long long ws_bytes,
+                       npvp_stream_t stream);
 /* Range of the precision-6 (two-term fp16) arithmetic, per ROW.  Operands are scaled by ONE power of two per tensor (their amax
  * slot), so a row that lies 2^18 or more below its tensor's bound would keep only subnormal low terms.  Forward / dgrad launches
  * (kernel ids 5 / 7) repair this themselves: every thread keeps the running |max| of the rows of A it stages, and a tile in which
@@ -192,6 +207,14 @@ int npvp_linear_bwd_f16(int R, int N, int K, const float* dy, long long ldy, con
                         unsigned int* range_flag, float adrop_p, int adrop_g1, int adrop_g2, unsigned int adrop_salt,
                         const unsigned long long* seed, const void* prev_job, void* my_job, void* workspace, long long ws_bytes,
                         npvp_stream_t stream);
+/* the same with the row-skip spec of npvp_gemm_f32_skip on the dgrad's tiles (the weight gradient's K-steps all run) */
+int npvp_linear_bwd_f16_skip(int R, int N, int K, const float* dy, long long ldy, const float* dy_amax, const void* w_planes_d,
+                             const float* w_amax, float* dx, long long ldx, int act, const float* aux_in, const float* residual,
+                             long long ldr, float drop_p, int drop_mode, int drop_g1, int drop_g2, unsigned int drop_salt,
+                             float* dx_amax, const float* x, long long ldxx, const float* x_amax, float* dw, long long ldw, float* db,
+                             unsigned int* range_flag, float adrop_p, int adrop_g1, int adrop_g2, unsigned int adrop_salt,
+                             float skip_p, int skip_g1, int skip_g2, unsigned int skip_salt, const unsigned long long* seed,
+                             const void* prev_job, void* my_job, void* workspace, long long ws_bytes, npvp_stream_t stream);
 /* w [N][K] -> the fp16 planes of precision 6: F[2 terms][K/8][N][8 over k], D[2 terms][N/8][K][8 over n] (2*N*K fp16 each,
  * either may be null), scaled by the power of two of w's amax, which is (re)computed into amax_slot (zeroed here first).
  * npvp_split_weights_f16: the same for `count` views in three stream operations; desc is a DEVICE array of records of eight
@@ -349,6 +372,29 @@ int npvp_frameln_act_bwd_apply(const float* dout, const float* h, const float* m
                                const float* b, const float* psum, int nparts, float* dh, float* dw, float* db, int frames,
                                int per_frame, int accumulate, float* dh_amax, void* workspace, long long ws_bytes,
                                npvp_stream_t stream);
+/* ---- three of these launches with the node's DropPath as a FRAME-SKIP spec: (skip_p, skip_salt, skip_fps = frames per sample, seed)
+ * are the (dp_p, dp_salt, frames_per_sample, seed) that the node's last npvp_frameln_act_fwd_parts call multiplies its output by.
+ * The frames of a sample which that call drops are not worked on: no read of the hidden tensor, no GELU, mask hash or tap
+ * arithmetic.  Every output is still written in full - a skipped frame gets what the kernel would produce from a zero input
+ * (forward: h2 = 0 with the partial (0, 0); out = res, or 0 without res) or a zero gradient (backward: dh = 0, no contribution to
+ * dw / db) - so a consumer that skips nothing stays correct on them.  The decision is taken on the device from the device seed
+ * (nothing on the host, no extra launch); skip_p = 0 skips nothing, and the entry points above are exactly that.  In
+ * _fwd_parts_skip the call's `seed` serves the skip as well.  (The fused middle's backward and npvp_frameln_act_bwd_pgrad have no
+ * such form: profiles/droppath_skip.txt.) */
+int npvp_mlpdw_mid_fwd_parts_skip(const float* h1, const float* part1, int J1, float nb1, float* mean1, float* rstd1,
+                                  const float* w1n, const float* b1n, const float* wt, const float* bias, float* h2, float* part2,
+                                  int frames, int H, int W, int Ch, float eps, float skip_p, unsigned int skip_salt, int skip_fps,
+                                  const unsigned long long* seed, npvp_stream_t stream);
+int npvp_frameln_act_fwd_parts_skip(const float* h, const float* part, int J, float nb, float eps, float* mean, float* rstd,
+                                    const float* w, const float* b, const float* res, float* out, int frames, int per_frame,
+                                    float drop_p, unsigned int salt, float dp_p, unsigned int dp_salt, int frames_per_sample,
+                                    const unsigned long long* seed, float* out_amax, float skip_p, unsigned int skip_salt,
+                                    int skip_fps, npvp_stream_t stream);
+int npvp_frameln_act_bwd_apply_skip(const float* dout, const float* h, const float* mean, const float* rstd, const float* w,
+                                    const float* b, const float* psum, int nparts, float* dh, float* dw, float* db, int frames,
+                                    int per_frame, int accumulate, float* dh_amax, void* workspace, long long ws_bytes,
+                                    float skip_p, unsigned int skip_salt, int skip_fps, const unsigned long long* seed,
+                                    npvp_stream_t stream);
 
 /* im2col / col2im of the EventEncoder's dense 3x3 conv (ref/models/submodules.py:376), channels-last:
  * col2im=0: in [F][H*W][C] -> out [F*H*W][9*C] (tap-major columns); col2im=1: the adjoint. */

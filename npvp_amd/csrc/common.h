@@ -259,6 +259,34 @@ inline DropSpec make_drop_spec(float p, unsigned int salt, int mode, int g1, int
   return d;
 }
 
+// The frames whose work a kernel of the MlpDWBN node may leave out: those of a sample that the node's DropPath drops (its
+// whole sub-layer output is multiplied by an exact 0 in norm3's epilogue, and backward starts from an exact 0 gradient for it).
+// The decision is the one fln_frame_scale makes for that epilogue - drop_scale(seed, salt, f / fps, thresh, .) == 0 - taken on the
+// device from the device seed, uniform over a frame's workgroup.  A skipped frame omits reads and arithmetic, never a write: the
+// kernel stores what it would produce from a zero input / a zero gradient, so every tensor of the node stays defined.
+struct FrameSkip {
+  const unsigned long long* seed; unsigned int thresh; unsigned int salt; int fps;      // thresh 0: nothing is skipped
+};
+__device__ __forceinline__ unsigned long long frame_skip_seed(const FrameSkip& s) { return (s.thresh && s.seed) ? *s.seed : 0ull; }
+__device__ __forceinline__ bool frame_skipped(const FrameSkip& s, unsigned long long seed, long long f) {
+  return s.thresh && rng_u32(seed, s.salt, (uint64_t)((unsigned int)f / (unsigned int)s.fps)) < s.thresh;
+}
+// The decisions for the frames f0 .. min(f1, f0 + 64) - 1 as one wave-uniform bit mask (bit i: frame f0 + i is skipped), for a
+// kernel that walks a chunk of frames: lane i of every wave takes frame f0 + i, so the hash and the division by fps are paid once
+// per chunk, not once per frame, and one scalar pair stays live in the loop instead of the spec and its keys.  Every lane of the
+// workgroup must make the call.  Frames past the 64th of a chunk are never skipped (they are computed: correct, only not faster).
+__device__ __forceinline__ unsigned long long frame_skip_mask(const FrameSkip& s, long long f0, long long f1) {
+  if (!s.thresh) return 0ull;
+  const unsigned long long seed = frame_skip_seed(s);
+  const long long f = f0 + (long long)(threadIdx.x & 63);
+  return __builtin_amdgcn_ballot_w64(f < f1 && frame_skipped(s, seed, f));
+}
+inline FrameSkip make_frame_skip(float p, unsigned int salt, int frames_per_sample, const unsigned long long* seed) {
+  FrameSkip s;
+  s.seed = seed; s.thresh = (p > 0.f && seed) ? drop_threshold(p) : 0u; s.salt = salt; s.fps = frames_per_sample > 0 ? frames_per_sample : 1;
+  return s;
+}
+
 __device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
 __device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
 

@@ -31,6 +31,9 @@ struct GemmParams {
   DropSpec drop;
   DropSpec adrop;          // fp16 kernels only: a ROW-GROUP mask (mode 1) on the rows of operand A (dgrad: A = dy [M][K]; weight
                            // gradient: A = dy [K][M]) - the backward of a DropPath site without a masked copy of dy; thresh 0 = off
+  DropSpec rskip;          // fp16 forward / dgrad kernels only: a ROW-GROUP spec (mode 1) of rows whose result the caller multiplies by
+                           // 0 (forward) or whose A rows are 0 (dgrad): a tile wholly inside dropped groups runs its epilogue on zero
+                           // accumulators instead of its K loop (gemm_f16_body); every other kernel ignores it; thresh 0 = off
   int tiles_m, tiles_n;
   int splits;              // >1: raw partial tiles go to C + z*M*ldc (workspace)
   float alpha;

@@ -611,14 +611,17 @@ static int finish_splitk(const GemmParams& p, float* C, long long ldc, float* co
 }
 
 // See include/npvp_hip.h for the contract.
-extern "C" int npvp_gemm_f32(int a_kc, int b_kc, int M, int N, int K, const float* A, long long lda, const float* B,
-                             long long ldb, float* C, long long ldc, const float* bias, int act, const float* aux_in,
-                             float* aux_out, const float* residual, long long ldr, float drop_p, int drop_mode,
-                             int drop_g1, int drop_g2, const unsigned long long* seed, unsigned int salt, float alpha,
-                             int precision, float* colsum_a, const void* b_pre, int accumulate, float* rowstats,
-                             const float* a_amax, const float* b_amax, float* c_amax, unsigned int* range_flag,
-                             float adrop_p, int adrop_g1, int adrop_g2, unsigned int adrop_salt,
-                             void* workspace, long long ws_bytes, hipStream_t stream) {
+extern "C" int npvp_gemm_f32_skip(int a_kc, int b_kc, int M, int N, int K, const float* A, long long lda, const float* B,
+                                  long long ldb, float* C, long long ldc, const float* bias, int act, const float* aux_in,
+                                  float* aux_out, const float* residual, long long ldr, float drop_p, int drop_mode,
+                                  int drop_g1, int drop_g2, const unsigned long long* seed, unsigned int salt, float alpha,
+                                  int precision, float* colsum_a, const void* b_pre, int accumulate, float* rowstats,
+                                  const float* a_amax, const float* b_amax, float* c_amax, unsigned int* range_flag,
+                                  float adrop_p, int adrop_g1, int adrop_g2, unsigned int adrop_salt,
+                                  float skip_p, int skip_g1, int skip_g2, unsigned int skip_salt,
+                                  void* workspace, long long ws_bytes, hipStream_t stream) {
+  NPVP_CHECK_ARG(skip_p >= 0.f && skip_p < 1.f && (skip_p == 0.f || (seed && skip_g1 > 0 && skip_g2 > 0 && a_kc)),
+                 "gemm: the row skip needs a device seed, row groups and a row-major A");
   NPVP_CHECK_ARG(M > 0 && N > 0 && K > 0, "gemm: empty problem");
   NPVP_CHECK_ARG(precision == 0 || precision == 4 || precision == 5 || precision == 6,
                  "gemm: precision must be 0 (exact fp32-input MFMA), 4 (three-term bf16 split, 6 MFMAs per product: "
@@ -659,6 +662,7 @@ extern "C" int npvp_gemm_f32(int a_kc, int b_kc, int M, int N, int K, const floa
   p.seed = seed; p.lda = lda; p.ldb = ldb; p.ldr = ldr; p.M = M; p.N = N; p.act = act;
   p.drop = make_drop_spec(drop_p, salt, drop_mode, drop_g1, drop_g2);
   p.adrop = make_drop_spec(adrop_p, adrop_salt, 1, adrop_g1, adrop_g2);
+  p.rskip = make_drop_spec(skip_p, skip_salt, 1, skip_g1, skip_g2);
   p.alpha = alpha;
   p.rowstats = rowstats;
   p.a_amax = a_amax; p.b_amax = b_amax; p.c_amax = c_amax; p.range_flag = range_flag;
@@ -697,4 +701,17 @@ extern "C" int npvp_gemm_f32(int a_kc, int b_kc, int M, int N, int K, const floa
   }
   NPVP_CHECK_LAUNCH();
   return plan.splits > 1 ? finish_splitk(p, C, ldc, colsum_a, stream) : NPVP_OK;
+}
+
+extern "C" int npvp_gemm_f32(int a_kc, int b_kc, int M, int N, int K, const float* A, long long lda, const float* B,
+                             long long ldb, float* C, long long ldc, const float* bias, int act, const float* aux_in,
+                             float* aux_out, const float* residual, long long ldr, float drop_p, int drop_mode,
+                             int drop_g1, int drop_g2, const unsigned long long* seed, unsigned int salt, float alpha,
+                             int precision, float* colsum_a, const void* b_pre, int accumulate, float* rowstats,
+                             const float* a_amax, const float* b_amax, float* c_amax, unsigned int* range_flag,
+                             float adrop_p, int adrop_g1, int adrop_g2, unsigned int adrop_salt,
+                             void* workspace, long long ws_bytes, hipStream_t stream) {
+  return npvp_gemm_f32_skip(a_kc, b_kc, M, N, K, A, lda, B, ldb, C, ldc, bias, act, aux_in, aux_out, residual, ldr, drop_p, drop_mode,
+                            drop_g1, drop_g2, seed, salt, alpha, precision, colsum_a, b_pre, accumulate, rowstats, a_amax, b_amax, c_amax,
+                            range_flag, adrop_p, adrop_g1, adrop_g2, adrop_salt, 0.f, 1, 1, 0u, workspace, ws_bytes, stream);
 }

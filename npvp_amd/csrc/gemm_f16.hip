@@ -107,6 +107,25 @@ __device__ __forceinline__ void gemm_f16_body(const GemmParams& p, char* lds, co
 
   f32x16 acc[TM][TN];                                 // (written by the first K-step: never zeroed)
 
+  // ROW SKIP (GemmParams::rskip: the DropPath of the node the launch belongs to).  A tile all of whose rows [m0, min(m0 + BM, M))
+  // lie in dropped row groups is not computed: no operand loads, no K loop, no row-guard pass - the accumulators are set to zero
+  // and the tile takes the epilogue as it stands (bias, frame statistics, amax commit), so C is written in full.  The decision is
+  // workgroup-uniform (scalar: m0 comes from the block index), at most three group evaluations; a tile that touches a kept group,
+  // or more than three groups, is computed in full.
+  bool skipped = false;
+  if (p.rskip.thresh) {
+    const unsigned long long sseed = *p.seed;
+    const unsigned int q0 = div_by_magic((unsigned int)m0, p.rskip.m1, p.rskip.s1);
+    const unsigned int q1 = div_by_magic((unsigned int)(min(m0 + BM, p.M) - 1), p.rskip.m1, p.rskip.s1);
+    if (q1 - q0 <= 2u) {
+      skipped = true;
+      for (unsigned int q = q0; q <= q1; ++q) {
+        const unsigned int grp = q - div_by_magic(q, p.rskip.m2, p.rskip.s2) * (unsigned int)p.rskip.g2;
+        skipped = skipped && rng_u32(sseed, p.rskip.salt, (uint64_t)grp) < p.rskip.thresh;
+      }
+    }
+  }
+
   const int quad = t & 3, rl = t >> 2;
   // global addresses = wave-uniform 64-bit base (SGPRs, advanced per K-step by scalar adds) + a per-lane 32-bit byte offset that
   // never changes: no 64-bit vector adds inside the K loop (they were 6 of its 38 VALU per step)
@@ -272,8 +291,13 @@ __device__ __forceinline__ void gemm_f16_body(const GemmParams& p, char* lds, co
   //  any wave turns the stages into the epilogue's scratch or a second pass rewrites stage 0)
   if constexpr (NST == 3) __builtin_amdgcn_s_barrier();
   };
+  if (skipped) {
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+#pragma unroll
+      for (int j = 0; j < TN; ++j) acc[i][j] = zero16;
+  } else {
   run_tile();
-  {
     rm0 = fmaxf(rm0, __shfl_xor(rm0, 1)); rm0 = fmaxf(rm0, __shfl_xor(rm0, 2));       // the four lanes that stage one row
     rm1 = fmaxf(rm1, __shfl_xor(rm1, 1)); rm1 = fmaxf(rm1, __shfl_xor(rm1, 2));
     const int et = (int)((__float_as_uint(sa) >> 23) & 0xffu);                         // sa = 2^(141 - E_bound): exponent field 268 - E_bound
@@ -865,13 +889,16 @@ extern "C" int npvp_linear_bwd_f16_takes(int R, int N, int K) {
   return ((v == 2 || v == 3 || v == 4) && npvp_wgrad_f16_chainable(N, K, R)) ? 1 : 0;
 }
 
-extern "C" int npvp_linear_bwd_f16(int R, int N, int K, const float* dy, long long ldy, const float* dy_amax, const void* w_planes_d,
-                                   const float* w_amax, float* dx, long long ldx, int act, const float* aux_in, const float* residual,
-                                   long long ldr, float drop_p, int drop_mode, int drop_g1, int drop_g2, unsigned int drop_salt,
-                                   float* dx_amax, const float* x, long long ldxx, const float* x_amax, float* dw, long long ldw, float* db,
-                                   unsigned int* range_flag, float adrop_p, int adrop_g1, int adrop_g2, unsigned int adrop_salt,
-                                   const unsigned long long* seed, const void* prev_job, void* my_job, void* workspace,
-                                   long long ws_bytes, hipStream_t stream) {
+extern "C" int npvp_linear_bwd_f16_skip(int R, int N, int K, const float* dy, long long ldy, const float* dy_amax, const void* w_planes_d,
+                                        const float* w_amax, float* dx, long long ldx, int act, const float* aux_in, const float* residual,
+                                        long long ldr, float drop_p, int drop_mode, int drop_g1, int drop_g2, unsigned int drop_salt,
+                                        float* dx_amax, const float* x, long long ldxx, const float* x_amax, float* dw, long long ldw, float* db,
+                                        unsigned int* range_flag, float adrop_p, int adrop_g1, int adrop_g2, unsigned int adrop_salt,
+                                        float skip_p, int skip_g1, int skip_g2, unsigned int skip_salt,
+                                        const unsigned long long* seed, const void* prev_job, void* my_job, void* workspace,
+                                        long long ws_bytes, hipStream_t stream) {
+  NPVP_CHECK_ARG(skip_p >= 0.f && skip_p < 1.f && (skip_p == 0.f || (seed && skip_g1 > 0 && skip_g2 > 0)),
+                 "linear_bwd_f16: the row skip needs a device seed and row groups");
   NPVP_CHECK_ARG(npvp_linear_bwd_f16_takes(R, N, K), "linear_bwd_f16: shape not taken (npvp_linear_bwd_f16_takes tells)");
   NPVP_CHECK_ARG(dy && dy_amax && w_planes_d && w_amax && dx && x && x_amax && dw && my_job, "linear_bwd_f16: null operand / amax slot / job");
   if (!deferred_wgrad_args_ok("linear_bwd_f16", dy, ldy, x, ldxx, dw, ldw, adrop_p, adrop_g1, adrop_g2, seed, workspace, ws_bytes,
@@ -889,6 +916,7 @@ extern "C" int npvp_linear_bwd_f16(int R, int N, int K, const float* dy, long lo
   d.residual = residual; d.ldr = ldr; d.seed = seed; d.splits = 1;
   d.drop = make_drop_spec(drop_p, drop_salt, drop_mode, drop_g1, drop_g2);
   d.adrop = make_drop_spec(adrop_p, adrop_salt, 1, adrop_g1, adrop_g2);
+  d.rskip = make_drop_spec(skip_p, skip_salt, 1, skip_g1, skip_g2);      // (the dgrad's tiles only: the weight gradient runs every K-step)
   d.b_pre = w_planes_d; d.b_pre_plane = (long long)N * K;
   d.a_amax = dy_amax; d.b_amax = w_amax; d.c_amax = dx_amax;
   // problem 1: dW[N][K] += dy^T x over R rows, split-K, reduction handed to a later launch (as npvp_wgrad_f16_chained)
@@ -912,6 +940,18 @@ extern "C" int npvp_linear_bwd_f16(int R, int N, int K, const float* dy, long lo
   NPVP_CHECK_LAUNCH();
   leave_reduce_job(w, dw, ldw, db, my_job);
   return NPVP_OK;
+}
+
+extern "C" int npvp_linear_bwd_f16(int R, int N, int K, const float* dy, long long ldy, const float* dy_amax, const void* w_planes_d,
+                                   const float* w_amax, float* dx, long long ldx, int act, const float* aux_in, const float* residual,
+                                   long long ldr, float drop_p, int drop_mode, int drop_g1, int drop_g2, unsigned int drop_salt,
+                                   float* dx_amax, const float* x, long long ldxx, const float* x_amax, float* dw, long long ldw, float* db,
+                                   unsigned int* range_flag, float adrop_p, int adrop_g1, int adrop_g2, unsigned int adrop_salt,
+                                   const unsigned long long* seed, const void* prev_job, void* my_job, void* workspace,
+                                   long long ws_bytes, hipStream_t stream) {
+  return npvp_linear_bwd_f16_skip(R, N, K, dy, ldy, dy_amax, w_planes_d, w_amax, dx, ldx, act, aux_in, residual, ldr, drop_p, drop_mode,
+                                  drop_g1, drop_g2, drop_salt, dx_amax, x, ldxx, x_amax, dw, ldw, db, range_flag, adrop_p, adrop_g1, adrop_g2,
+                                  adrop_salt, 0.f, 1, 1, 0u, seed, prev_job, my_job, workspace, ws_bytes, stream);
 }
 
 __global__ __launch_bounds__(256) void splitk_reduce_job_kernel(ReduceJob j) {

@@ -134,7 +134,7 @@ __global__ __launch_bounds__(256, 4) void mlpdw_mid_fwd_kernel(const float* __re
                                                             const float* __restrict__ bias, float* __restrict__ h2,
                                                             float* __restrict__ part, int Ch, const float* __restrict__ part1,
                                                             int J1, float nb1, float eps1, float* __restrict__ mean1_out,
-                                                            float* __restrict__ rstd1_out) {
+                                                            float* __restrict__ rstd1_out, FrameSkip skip) {
   constexpr int HH = 8, WW = 8;
   __shared__ float red[4];
   // a block lies inside one frame ((Ch / VEC) % 256 == 0): the frame base is wave-uniform (SGPR pair) and every access is
@@ -147,12 +147,21 @@ __global__ __launch_bounds__(256, 4) void mlpdw_mid_fwd_kernel(const float* __re
     frame_stats_merge(part1, f, J1, nb1, eps1, mu, rs);
     if (blockIdx.x == f * bpf && threadIdx.x == 0) { mean1_out[f] = mu; rstd1_out[f] = rs; }
   } else { mu = mean1[f]; rs = rstd1[f]; }
+  const float* hf = h1 + f * (HH * WW) * Ch;
+  float* of = h2 + f * (HH * WW) * Ch;
+  if (frame_skipped(skip, frame_skip_seed(skip), f)) {          // (workgroup-uniform) a dropped sample's frame: h2 = 0, partial (0, 0)
+    Vec<VEC> z;
+#pragma unroll
+    for (int e = 0; e < VEC; ++e) z.v[e] = 0.f;
+#pragma unroll
+    for (int pix = 0; pix < HH * WW; ++pix) stv<VEC>(of + pix * Ch + c, z);
+    if (threadIdx.x == 0) { part[blockIdx.x * 2] = 0.f; part[blockIdx.x * 2 + 1] = 0.f; }
+    return;
+  }
   Vec<VEC> wv[9];
 #pragma unroll
   for (int t = 0; t < 9; ++t) wv[t] = ldv<VEC>(wt + t * Ch + c);
   const Vec<VEC> bv = ldv<VEC>(bias + c);
-  const float* hf = h1 + f * (HH * WW) * Ch;
-  float* of = h2 + f * (HH * WW) * Ch;
   Vec<VEC> r0[WW], r1[WW], r2[WW];
   auto load_row = [&](Vec<VEC>* row, int hh) {
 #pragma unroll
@@ -578,7 +587,7 @@ extern "C" int npvp_mlpdw_mid_fwd(const float* h1, const float* mean1, const flo
   NPVP_CHECK_ARG(workspace && ws_bytes >= (long long)frames * J * 8, "mlpdw_mid_fwd: workspace too small");
   const long long nthreads = (long long)frames * (Ch / 2);
   NPVP_LAUNCH((mlpdw_mid_fwd_kernel<2>), dim3((unsigned)(nthreads / 256)), dim3(256), 0, stream, h1, mean1, rstd1, w1n, b1n,
-                     wt, bias, h2, (float*)workspace, Ch, (const float*)nullptr, 0, 0.f, 0.f, (float*)nullptr, (float*)nullptr);
+                     wt, bias, h2, (float*)workspace, Ch, (const float*)nullptr, 0, 0.f, 0.f, (float*)nullptr, (float*)nullptr, FrameSkip{});
   NPVP_CHECK_LAUNCH();
   NPVP_LAUNCH(frame_stats_finalize_kernel, dim3((frames + 255) / 256), dim3(256), 0, stream, (const float*)workspace, J,
                      32768.f, mean2, rstd2, frames, eps);
@@ -590,16 +599,28 @@ extern "C" int npvp_mlpdw_mid_fwd(const float* h1, const float* mean1, const flo
 // that the fc1 GEMM's epilogue left (rowstats of npvp_gemm_f32: J1 = Ch / 64, nb1 = 4096) and are merged by every block for its
 // frame (mean1 / rstd1 are OUTPUTS here, for backward); h2's partials part2 [frames][Ch / 512][2] (32 768 values each) are left
 // for npvp_frameln_act_fwd_parts.
+// skip_p / skip_salt / skip_fps / seed: the node's DropPath (see FrameSkip, common.h): the frames of a dropped sample get h2 = 0 and
+// the partial (0, 0) without a read of h1; mean1 / rstd1 are written for every frame.  skip_p = 0: every frame is computed.
+extern "C" int npvp_mlpdw_mid_fwd_parts_skip(const float* h1, const float* part1, int J1, float nb1, float* mean1, float* rstd1,
+                                             const float* w1n, const float* b1n, const float* wt, const float* bias, float* h2,
+                                             float* part2, int frames, int H, int W, int Ch, float eps, float skip_p,
+                                             unsigned int skip_salt, int skip_fps, const unsigned long long* seed, hipStream_t stream) {
+  NPVP_CHECK_ARG(frames > 0 && H == 8 && W == 8 && Ch > 0 && Ch % 512 == 0, "mlpdw_mid_fwd_parts: needs an 8x8 grid and Ch % 512 == 0");
+  NPVP_CHECK_ARG(part1 && J1 > 0 && nb1 > 0.f && mean1 && rstd1 && part2, "mlpdw_mid_fwd_parts: bad arguments");
+  NPVP_CHECK_ARG(skip_p >= 0.f && skip_p < 1.f && (skip_p == 0.f || (seed && skip_fps > 0)), "mlpdw_mid_fwd_parts: bad frame-skip arguments");
+  const long long nthreads = (long long)frames * (Ch / 2);
+  NPVP_LAUNCH((mlpdw_mid_fwd_kernel<2>), dim3((unsigned)(nthreads / 256)), dim3(256), 0, stream, h1, (const float*)nullptr,
+                     (const float*)nullptr, w1n, b1n, wt, bias, h2, part2, Ch, part1, J1, nb1, eps, mean1, rstd1,
+                     make_frame_skip(skip_p, skip_salt, skip_fps, seed));
+  NPVP_CHECK_LAUNCH();
+  return NPVP_OK;
+}
+
 extern "C" int npvp_mlpdw_mid_fwd_parts(const float* h1, const float* part1, int J1, float nb1, float* mean1, float* rstd1,
                                         const float* w1n, const float* b1n, const float* wt, const float* bias, float* h2,
                                         float* part2, int frames, int H, int W, int Ch, float eps, hipStream_t stream) {
-  NPVP_CHECK_ARG(frames > 0 && H == 8 && W == 8 && Ch > 0 && Ch % 512 == 0, "mlpdw_mid_fwd_parts: needs an 8x8 grid and Ch % 512 == 0");
-  NPVP_CHECK_ARG(part1 && J1 > 0 && nb1 > 0.f && mean1 && rstd1 && part2, "mlpdw_mid_fwd_parts: bad arguments");
-  const long long nthreads = (long long)frames * (Ch / 2);
-  NPVP_LAUNCH((mlpdw_mid_fwd_kernel<2>), dim3((unsigned)(nthreads / 256)), dim3(256), 0, stream, h1, (const float*)nullptr,
-                     (const float*)nullptr, w1n, b1n, wt, bias, h2, part2, Ch, part1, J1, nb1, eps, mean1, rstd1);
-  NPVP_CHECK_LAUNCH();
-  return NPVP_OK;
+  return npvp_mlpdw_mid_fwd_parts_skip(h1, part1, J1, nb1, mean1, rstd1, w1n, b1n, wt, bias, h2, part2, frames, H, W, Ch, eps, 0.f, 0u, 1,
+                                       nullptr, stream);
 }
 
 static int mid_chunks(int frames) { return frames < 128 ? frames : 128; }      // 256 / 512 chunks: no change of the c2 step

@@ -608,6 +608,7 @@ struct FlnParams {
   unsigned int drop_thresh; float drop_inv_keep; unsigned int salt;       // elementwise dropout
   unsigned int dp_thresh; float dp_inv_keep; unsigned int dp_salt; int frames_per_sample;   // per-sample drop-path
   int per_frame; long long total4;
+  FrameSkip skip;                   // frames left out by the forward-with-partials and the one-pass backward kernel (common.h); thresh 0: none
 };
 
 // keep-scale of an element = (its frame's DropPath decision) x (its own dropout decision).  The frame's factor is taken ONCE per
@@ -665,6 +666,17 @@ __global__ __launch_bounds__(256) void frameln_act_fwd_parts_kernel(FlnParams p,
   if (e0 == 0 && threadIdx.x == 0) { mean_out[f] = mu; rstd_out[f] = rs; }
   const float fsc = fln_frame_scale(p, seed, f);
   float am = 0.f;
+  if (frame_skipped(p.skip, frame_skip_seed(p.skip), f)) {      // (workgroup-uniform) a dropped sample's frame: out = res (or 0), h is not read
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const long long g0 = f * p.per_frame + e0 + (k * 256 + threadIdx.x) * 4;
+      const float4 o = p.res ? ld4(p.res + g0) : make_float4(0.f, 0.f, 0.f, 0.f);
+      st4(out + g0, o);
+      am = amax4(am, o);
+    }
+    amax_slot_commit_block(amax, am, ared, peek);
+    return;
+  }
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
     const int e = e0 + (k * 256 + threadIdx.x) * 4;
@@ -733,8 +745,10 @@ __global__ void frameln_act_bwd_fused_kernel(FlnParams p, const float* __restric
   float4 aw = zero4, ab = zero4;
   const int f0 = blockIdx.y * frames_per_chunk;
   const int f1 = live ? min(frames, f0 + frames_per_chunk) : f0;
+  const unsigned long long skipped = frame_skip_mask(p.skip, f0, min(frames, f0 + frames_per_chunk));      // (every lane calls)
   for (long long f = f0; f < f1; ++f) {
     const long long g0 = f * p.per_frame + e;
+    if (f - f0 < 64 && ((skipped >> (int)(f - f0)) & 1ull)) { st4(dh + g0, zero4); continue; }      // a dropped sample's frame: dout is 0, so is dh
     const float mu = p.mean[f], rs = p.rstd[f];
     const float fsc = fln_frame_scale(p, seed, f);
     float a1 = 0.f, a2 = 0.f;              // s1 = mean(g), s2 = mean(g*hhat) from the FLN_PARTS partial sums, fixed order
@@ -881,7 +895,10 @@ static void fill_fln(FlnParams& p, const float* h, const float* mean, const floa
   p.dp_inv_keep = dp_p > 0.f ? 1.f / (1.f - dp_p) : 1.f;
   p.dp_salt = dp_salt; p.frames_per_sample = frames_per_sample > 0 ? frames_per_sample : 1;
   p.per_frame = per_frame; p.total4 = (long long)frames * per_frame / 4;
+  p.skip = FrameSkip{};
 }
+#define NPVP_CHECK_FRAME_SKIP(who) \
+  NPVP_CHECK_ARG(skip_p >= 0.f && skip_p < 1.f && (skip_p == 0.f || (seed && skip_fps > 0)), who ": bad frame-skip arguments")
 
 }  // namespace npvp
 
@@ -1097,19 +1114,32 @@ extern "C" int npvp_frameln_act_fwd(const float* h, const float* mean, const flo
 
 // frame statistics from the producer's partials part [frames][J][2] (mean_j, M2_j over nb values each: the rowstats of
 // npvp_gemm_f32 or the part2 of npvp_mlpdw_mid_fwd_parts); mean / rstd [frames] are OUTPUTS (for backward).  per_frame % 4096 == 0.
-extern "C" int npvp_frameln_act_fwd_parts(const float* h, const float* part, int J, float nb, float eps, float* mean, float* rstd,
-                                          const float* w, const float* b, const float* res, float* out, int frames,
-                                          int per_frame, float drop_p, unsigned int salt, float dp_p, unsigned int dp_salt,
-                                          int frames_per_sample, const unsigned long long* seed, float* amax, hipStream_t stream) {
+// skip_p / skip_salt / skip_fps (with `seed`): the DropPath of the node the call belongs to (see FrameSkip, common.h): the frames of a
+// dropped sample become out = res (0 without res) and h is not read; mean / rstd are written for every frame.
+extern "C" int npvp_frameln_act_fwd_parts_skip(const float* h, const float* part, int J, float nb, float eps, float* mean, float* rstd,
+                                               const float* w, const float* b, const float* res, float* out, int frames,
+                                               int per_frame, float drop_p, unsigned int salt, float dp_p, unsigned int dp_salt,
+                                               int frames_per_sample, const unsigned long long* seed, float* amax, float skip_p,
+                                               unsigned int skip_salt, int skip_fps, hipStream_t stream) {
+  NPVP_CHECK_FRAME_SKIP("frameln_act_fwd_parts");
   NPVP_CHECK_ARG(frames > 0 && per_frame % 4096 == 0 && part && J > 0 && nb > 0.f && mean && rstd, "frameln_act_fwd_parts: bad arguments");
   NPVP_CHECK_ARG((drop_p == 0.f && dp_p == 0.f) || seed, "frameln_act: dropout needs a device seed");
   NPVP_CHECK_ARG((long long)frames * (per_frame / 4096) < (1ll << 31), "frameln_act_fwd_parts: too many blocks");
   FlnParams p;
   fill_fln(p, h, nullptr, nullptr, w, b, res, frames, per_frame, drop_p, salt, dp_p, dp_salt, frames_per_sample, seed);
+  p.skip = make_frame_skip(skip_p, skip_salt, skip_fps, seed);
   NPVP_LAUNCH(frameln_act_fwd_parts_kernel, dim3((unsigned)((long long)frames * (per_frame / 4096))), dim3(256), 0, stream, p,
                      part, J, nb, eps, mean, rstd, out, amax);
   NPVP_CHECK_LAUNCH();
   return NPVP_OK;
+}
+
+extern "C" int npvp_frameln_act_fwd_parts(const float* h, const float* part, int J, float nb, float eps, float* mean, float* rstd,
+                                          const float* w, const float* b, const float* res, float* out, int frames,
+                                          int per_frame, float drop_p, unsigned int salt, float dp_p, unsigned int dp_salt,
+                                          int frames_per_sample, const unsigned long long* seed, float* amax, hipStream_t stream) {
+  return npvp_frameln_act_fwd_parts_skip(h, part, J, nb, eps, mean, rstd, w, b, res, out, frames, per_frame, drop_p, salt, dp_p, dp_salt,
+                                         frames_per_sample, seed, amax, 0.f, 0u, 1, stream);
 }
 
 // frame chunks (grid.y) of the backward kernels and of their parameter-gradient partials ([chunks][2 * per_frame] floats, summed
@@ -1163,16 +1193,29 @@ extern "C" int npvp_frameln_act_bwd(const float* dout, const float* h, const flo
 // The same with the statistics supplied by the producer of dout: psum [frames][nparts][2] = partial (sum g, sum g*hhat)
 // (npvp_mlpdw_mid_bwd emits them for norm1) - ONE pass instead of two.  No dropout / drop-path here (norm1 has none).
 // workspace: same layout and size as npvp_frameln_act_bwd (the first frames*2*FLN_PARTS floats stay unused).
-extern "C" int npvp_frameln_act_bwd_apply(const float* dout, const float* h, const float* mean, const float* rstd, const float* w,
-                                          const float* b, const float* psum, int nparts, float* dh, float* dw, float* db,
-                                          int frames, int per_frame, int accumulate, float* amax, void* workspace,
-                                          long long ws_bytes, hipStream_t stream) {
+// skip_p / skip_salt / skip_fps / seed (see FrameSkip, common.h): the frames of a dropped sample, whose dout is an exact 0, get
+// dh = 0 without a read and add nothing to dw / db.
+extern "C" int npvp_frameln_act_bwd_apply_skip(const float* dout, const float* h, const float* mean, const float* rstd, const float* w,
+                                               const float* b, const float* psum, int nparts, float* dh, float* dw, float* db,
+                                               int frames, int per_frame, int accumulate, float* amax, void* workspace,
+                                               long long ws_bytes, float skip_p, unsigned int skip_salt, int skip_fps,
+                                               const unsigned long long* seed, hipStream_t stream) {
+  NPVP_CHECK_FRAME_SKIP("frameln_act_bwd_apply");
   NPVP_CHECK_ARG(frames > 0 && per_frame % 4 == 0 && psum && nparts > 0, "frameln_act_bwd_apply: bad arguments");
   const Partials P = fln_partials(workspace, dw, db, frames, per_frame, accumulate);
   NPVP_CHECK_ARG(workspace && ws_bytes >= P.bytes, "frameln_act_bwd_apply: workspace too small");
   FlnParams p;
   fill_fln(p, h, mean, rstd, w, b, nullptr, frames, per_frame, 0.f, 0u, 0.f, 0u, 1, nullptr);
+  p.skip = make_frame_skip(skip_p, skip_salt, skip_fps, seed);
   return fln_bwd_fused(p, dout, psum, nparts, dh, P, frames, accumulate, amax, stream, "frameln_act_bwd_apply: reduce launch failed");
+}
+
+extern "C" int npvp_frameln_act_bwd_apply(const float* dout, const float* h, const float* mean, const float* rstd, const float* w,
+                                          const float* b, const float* psum, int nparts, float* dh, float* dw, float* db,
+                                          int frames, int per_frame, int accumulate, float* amax, void* workspace,
+                                          long long ws_bytes, hipStream_t stream) {
+  return npvp_frameln_act_bwd_apply_skip(dout, h, mean, rstd, w, b, psum, nparts, dh, dw, db, frames, per_frame, accumulate, amax, workspace,
+                                         ws_bytes, 0.f, 0u, 1, nullptr, stream);
 }
 
 // Statistics and parameter gradients only (see frameln_act_bwd_pgrad_kernel): psum [frames][per_frame / 1024][2] receives the

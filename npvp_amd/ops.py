@@ -322,12 +322,13 @@ class WeightPlanes:
 
 def gemm(a_kc, b_kc, M, N, K, A, lda, B, ldb, out, bias=None, act=0, aux_in=None, aux_out=None, residual=None,
          drop=NO_DROP, alpha=1.0, colsum_a=None, b_pre=None, accumulate=False, rowstats=None, precision=None,
-         replay=False, a_amax=None, b_amax=None, c_amax=None, a_drop=NO_DROP, range_flag=None):
+         replay=False, a_amax=None, b_amax=None, c_amax=None, a_drop=NO_DROP, range_flag=None, row_skip=NO_DROP):
     """replay=True: `drop` replays a forward site's mask in backward (not a new site for ops.DropRecorder).
     b_pre = WeightPlanes.get(...) = (planes, weight amax slot) or None; a_amax / b_amax: the operands' amax slots (f16x3; a
     missing slot of A - or of B for a weight gradient - is filled by the stand-alone reduction); c_amax: slot that receives
     the bound of the values stored to `out`.  a_drop: a row-group (DropPath) mask on the rows of A - fp16 kernels only, see
-    `masked_grad`."""
+    `masked_grad`.  row_skip: the row groups of a DropPath site whose rows of the result are multiplied by 0 later (forward) or
+    whose rows of A are zeros (dgrad): the fp16 forward / dgrad kernels leave out the tiles inside them (npvp_gemm_f32_skip)."""
     # (this wrapper runs for a third of a step's launches: the optional arguments are tested in line instead of through _ptr / _chk,
     # ~3 us of its ~9 us of interpreter time)
     for t in (A, B, out, bias, aux_in, aux_out, residual, colsum_a):
@@ -353,7 +354,7 @@ def gemm(a_kc, b_kc, M, N, K, A, lda, B, ldb, out, bias=None, act=0, aux_in=None
     ws, wsn = (None, 0)
     if wsb > 0:
         ws, wsn = _ws(wsb, A.device)
-    masked = drop.p > 0.0 or a_drop.p > 0.0
+    masked = drop.p > 0.0 or a_drop.p > 0.0 or row_skip.p > 0.0
     seed = _S._cur.rng.seed_tensor(A.device) if masked else None
     if DropRecorder.sites is not None and not replay:
         DropRecorder.note(drop, "elem" if drop.mode == 0 else "group", M * N if drop.mode == 0 else drop.g2)
@@ -363,7 +364,7 @@ def gemm(a_kc, b_kc, M, N, K, A, lda, B, ldb, out, bias=None, act=0, aux_in=None
     if GemmProbe.armed:
         kid = _gemm_kernel_id(a_kc, b_kc, M, N, K, prec, planes is not None)
         pe = GemmProbe.begin(kid)
-    rc = lib().npvp_gemm_f32(
+    rc = lib().npvp_gemm_f32_skip(
         a_kc, b_kc, M, N, K, A.data_ptr(), lda, B.data_ptr(), ldb, out.data_ptr(), out.stride(0),
         None if bias is None else bias.data_ptr(), act, None if aux_in is None else aux_in.data_ptr(),
         None if aux_out is None else aux_out.data_ptr(), None if residual is None else residual.data_ptr(),
@@ -372,9 +373,10 @@ def gemm(a_kc, b_kc, M, N, K, A, lda, B, ldb, out, bias=None, act=0, aux_in=None
         None if planes is None else planes.data_ptr(), 1 if accumulate else 0, None if rowstats is None else rowstats.data_ptr(),
         None if a_amax is None else a_amax.data_ptr(), None if b_amax is None else b_amax.data_ptr(),
         None if c_amax is None else c_amax.data_ptr(), None if range_flag is None else range_flag.data_ptr(),
-        a_drop.p, a_drop.g1, a_drop.g2, a_drop.salt, None if ws is None else ws.data_ptr(), wsn, _stream())
+        a_drop.p, a_drop.g1, a_drop.g2, a_drop.salt, row_skip.p, row_skip.g1, row_skip.g2, row_skip.salt,
+        None if ws is None else ws.data_ptr(), wsn, _stream())
     if rc:
-        check(rc, "npvp_gemm_f32")
+        check(rc, "npvp_gemm_f32_skip")
     if pe is not None:
         GemmProbe.end(pe, 2.0 * M * N * K, 4.0 * (M * K + N * K + M * N), (a_kc, b_kc), kid)
     return out
@@ -470,13 +472,14 @@ def linear_frame_stats_supported(R, N):
 
 
 def linear_dgrad(dy, w, act=0, aux_in=None, drop=NO_DROP, residual=None, dy_amax=None, dx_amax=None, a_drop=NO_DROP, out=None,
-                 accumulate=False):
+                 accumulate=False, row_skip=NO_DROP):
     """dx[R,K] = epilogue((a_drop mask on the rows of dy) dy[R,N] w[N,K]); out / accumulate: into (added to) an existing [R,K] buffer"""
     R, N = dy.shape
     K = w.shape[1]
     dx = torch.empty(R, K, dtype=torch.float32, device=dy.device) if out is None else out
     return gemm(1, 0, R, K, N, dy, dy.stride(0), w, w.stride(0), dx, act=act, aux_in=aux_in, drop=drop, residual=residual,
-                b_pre=_planes(w, "D", R), replay=True, a_amax=dy_amax, c_amax=dx_amax, a_drop=a_drop, accumulate=accumulate)
+                b_pre=_planes(w, "D", R), replay=True, a_amax=dy_amax, c_amax=dx_amax, a_drop=a_drop, accumulate=accumulate,
+                row_skip=row_skip)
 
 
 def masked_grad(dy2, drop, w):
@@ -559,10 +562,12 @@ class FusedLinearBwd:
         return linear_bwd_plan(R, N, K, 6, True, False, True, True, True, True, False, cls.MAX_ROWS).fused
 
 
-def linear_bwd(dy, x, w, b, sk, act=0, aux_in=None, drop=NO_DROP, residual=None, dy_amax=None, dx_amax=None, a_drop=NO_DROP):
+def linear_bwd(dy, x, w, b, sk, act=0, aux_in=None, drop=NO_DROP, residual=None, dy_amax=None, dx_amax=None, a_drop=NO_DROP,
+               row_skip=NO_DROP):
     """The backward of y = x w^T + b given dy [R, N]: -> dx = epilogue((a_drop mask) dy w), gw, gb - the weight (+ bias) gradient goes
     into the sink `sk` (-> None, None) or is returned.  One launch where FusedLinearBwd takes the shape, else the dgrad on this
-    stream and the weight gradient on the gradient stream as before."""
+    stream and the weight gradient on the gradient stream as before.  row_skip: row groups in which dy is zero (see gemm): the
+    dgrad leaves their tiles out; it is used by the dgrad launch made here, never by a deferred one."""
     R, N = dy.shape
     K = w.shape[1]
     has_b = b is not None
@@ -573,7 +578,8 @@ def linear_bwd(dy, x, w, b, sk, act=0, aux_in=None, drop=NO_DROP, residual=None,
                            dy.stride(1) == 1 and x.stride(1) == 1 and (not sunk or sk[0][0].stride(1) == 1), pl is not None,
                            FusedLinearBwd.enabled, FusedLinearBwd.with_gradient_stream, FusedLinearBwd.MAX_ROWS)
     if not plan.fused:
-        dx = linear_dgrad(dy, w, act=act, aux_in=aux_in, drop=drop, residual=residual, dy_amax=dy_amax, dx_amax=dx_amax, a_drop=a_drop)
+        dx = linear_dgrad(dy, w, act=act, aux_in=aux_in, drop=drop, residual=residual, dy_amax=dy_amax, dx_amax=dx_amax, a_drop=a_drop,
+                          row_skip=row_skip)
         gw, gb = _lin_grads(dy, x, w, b, sk, a_drop=a_drop, plan=plan)
         return dx, gw, gb
     planes, w_amax = pl
@@ -583,17 +589,20 @@ def linear_bwd(dy, x, w, b, sk, act=0, aux_in=None, drop=NO_DROP, residual=None,
     dx = torch.empty(R, K, dtype=torch.float32, device=dev)
     ws, wsn = _ws(c.chain.workspace_bytes(N, K, R), dev)
     st = _stream()
-    seed = c.rng.seed_tensor(dev) if (drop.on or a_drop.on) else None
+    seed = c.rng.seed_tensor(dev) if (drop.on or a_drop.on or row_skip.on) else None
     outs = (gw.data_ptr(),) if gb is None else (gw.data_ptr(), gb.data_ptr())
     later = c.chain if plan.reduction == "chained" else c.reduce       # who runs this launch's split-K reduction
     job_addr, prev_addr = later.job_slot(st, outs)
     pe = GemmProbe.begin(8)
-    check(lib().npvp_linear_bwd_f16(R, N, K, dy.data_ptr(), dy.stride(0), dy_amax.data_ptr(), planes.data_ptr(), w_amax.data_ptr(),
-                                    dx.data_ptr(), dx.stride(0), act, _ptr(aux_in), _ptr(residual),
-                                    0 if residual is None else residual.stride(0), drop.p, drop.mode, drop.g1, drop.g2, drop.salt,
-                                    _ptr(dx_amax), x.data_ptr(), x.stride(0), x_amax.data_ptr(), gw.data_ptr(), gw.stride(0),
-                                    _ptr(gb), _ptr(c.range_guard.flag(dev)), a_drop.p, a_drop.g1, a_drop.g2, a_drop.salt, _ptr(seed),
-                                    prev_addr, job_addr, ws.data_ptr(), wsn, st), "npvp_linear_bwd_f16")
+    head = (R, N, K, dy.data_ptr(), dy.stride(0), dy_amax.data_ptr(), planes.data_ptr(), w_amax.data_ptr(), dx.data_ptr(), dx.stride(0),
+            act, _ptr(aux_in), _ptr(residual), 0 if residual is None else residual.stride(0), drop.p, drop.mode, drop.g1, drop.g2,
+            drop.salt, _ptr(dx_amax), x.data_ptr(), x.stride(0), x_amax.data_ptr(), gw.data_ptr(), gw.stride(0), _ptr(gb),
+            _ptr(c.range_guard.flag(dev)), a_drop.p, a_drop.g1, a_drop.g2, a_drop.salt)
+    tail = (_ptr(seed), prev_addr, job_addr, ws.data_ptr(), wsn, st)
+    if row_skip.on:
+        check(lib().npvp_linear_bwd_f16_skip(*head, row_skip.p, row_skip.g1, row_skip.g2, row_skip.salt, *tail), "npvp_linear_bwd_f16_skip")
+    else:
+        check(lib().npvp_linear_bwd_f16(*head, *tail), "npvp_linear_bwd_f16")
     GemmProbe.end(pe, 4.0 * R * N * K, 4.0 * (2 * R * N + 2 * R * K + 2 * N * K), (1, 0), 8)
     later.job_added(st, outs, (ws, gw, gb), sk)
     return dx, None, None
@@ -1334,9 +1343,10 @@ def attn(q, k, v, cfg):
     return _Attn.apply(q, k, v, cfg)
 
 
-def _fln_bwd(dout, h, mean, rstd, w, b, frames, PF, d, dp, T, sk, psum=None, nparts=0, want_amax=True):
+def _fln_bwd(dout, h, mean, rstd, w, b, frames, PF, d, dp, T, sk, psum=None, nparts=0, want_amax=True, skip=None):
     """frame-LN backward (with its own statistics pass, or with the producer's `psum`); parameter gradients into the
-    sink (partials reduced on the gradient stream) or returned; want_amax: dh feeds a GEMM (gets an amax slot)"""
+    sink (partials reduced on the gradient stream) or returned; want_amax: dh feeds a GEMM (gets an amax slot);
+    skip = (Drop, frames per sample) of the node's DropPath (`psum` form only): the frames of dropped samples are not worked on"""
     L = lib()
     dev = h.device
     dh = torch.empty_like(h)
@@ -1351,10 +1361,12 @@ def _fln_bwd(dout, h, mean, rstd, w, b, frames, PF, d, dp, T, sk, psum=None, npa
                                      frames, PF, d.p, d.salt, dp.p, dp.salt, T, _ptr(seed), mode, _ptr(slot), _ptr(ws), wsn,
                                      _stream()), "npvp_frameln_act_bwd")
     else:
+        sd, sT = skip if skip else (NO_DROP, 1)
+        seed = _S._cur.rng.seed_tensor(dev) if sd.on else None
         pe = HbmProbe.begin()
-        check(L.npvp_frameln_act_bwd_apply(_ptr(dout), _ptr(h), _ptr(mean), _ptr(rstd), _ptr(w), _ptr(b), _ptr(psum), nparts,
-                                           _ptr(dh), _ptr(dw), _ptr(db), frames, PF, mode, _ptr(slot), _ptr(ws), wsn, _stream()),
-              "npvp_frameln_act_bwd_apply")
+        check(L.npvp_frameln_act_bwd_apply_skip(_ptr(dout), _ptr(h), _ptr(mean), _ptr(rstd), _ptr(w), _ptr(b), _ptr(psum), nparts,
+                                                _ptr(dh), _ptr(dw), _ptr(db), frames, PF, mode, _ptr(slot), _ptr(ws), wsn, sd.p, sd.salt,
+                                                sT, _ptr(seed), _stream()), "npvp_frameln_act_bwd_apply_skip")
         HbmProbe.end(pe, "npvp::frameln_act_bwd_fused_kernel", 4.0 * 3 * frames * PF)            # reads dout, h; writes dh
     if sk:
         _reduce_partials(sk, ws, dw, db, L.npvp_frameln_act_bwd_reduce, L.npvp_frameln_act_bwd_reduce_job, "npvp_frameln_act_bwd_reduce",
@@ -1492,11 +1504,16 @@ class _MlpDwbn(torch.autograd.Function):
         dev, f32 = x.device, torch.float32
         st = _stream()
         PFh, PFo = 64 * hid, 64 * Co
+        d2, d3, dp = Drop(p_drop), Drop(p_drop), Drop(p_dp, 1)
+        # the samples dp drops: frame kernels write zeros for them, GEMM tiles inside them are not computed (DROP_PATH_SKIP)
+        sk = dp if (DROP_PATH_SKIP and dp.on) else NO_DROP
+        rs = Drop._like(dp, 1, T * 64, frames // T) if (sk.on and frames % T == 0) else NO_DROP      # the same samples as token-row groups
+        seed = _S._cur.rng.seed_tensor(dev) if (d2.on or dp.on) else None
         # fc1 (+ frame statistics of h1)
         h1 = torch.empty(R, hid, dtype=f32, device=dev)
         part = torch.empty(frames * (hid // 64) * 2, dtype=f32, device=dev)
         gemm(1, 1, R, hid, C, x, x.stride(0), w1, w1.stride(0), h1, bias=b1, b_pre=_planes(w1, "F", R),
-             rowstats=part)
+             rowstats=part, row_skip=rs)
         stats = torch.empty(6, frames, dtype=f32, device=dev)               # mean1, rstd1, mean2, rstd2, mean3, rstd3
         # (no statistics launches: each consumer below merges the partial (mean, M2) pairs its producer left and writes
         # mean / rstd into `stats` for backward)
@@ -1513,31 +1530,30 @@ class _MlpDwbn(torch.autograd.Function):
         # fused middle
         h2 = torch.empty(R, hid, dtype=f32, device=dev)
         part2 = torch.empty(frames * (hid // 512) * 2, dtype=f32, device=dev)
-        check(L.npvp_mlpdw_mid_fwd_parts(_ptr(h1), _ptr(part), hid // 64, 4096.0, _row(stats, 0), _row(stats, 1), _ptr(n1w), _ptr(n1b),
-                                         _ptr(wtb), _row(wtb, 9), _ptr(h2), _ptr(part2), frames, 8, 8, hid, 1e-5, st),
-              "npvp_mlpdw_mid_fwd_parts")
-        d2, d3, dp = Drop(p_drop), Drop(p_drop), Drop(p_dp, 1)
+        check(L.npvp_mlpdw_mid_fwd_parts_skip(_ptr(h1), _ptr(part), hid // 64, 4096.0, _row(stats, 0), _row(stats, 1), _ptr(n1w),
+                                              _ptr(n1b), _ptr(wtb), _row(wtb, 9), _ptr(h2), _ptr(part2), frames, 8, 8, hid, 1e-5, sk.p,
+                                              sk.salt, T, _ptr(seed), st), "npvp_mlpdw_mid_fwd_parts_skip")
         DropRecorder.note(d2, "elem", R * hid)
-        seed = _S._cur.rng.seed_tensor(dev) if (d2.on or dp.on) else None
         a2 = torch.empty(R, hid, dtype=f32, device=dev)
         a2_slot = _new_slot(dev)
-        check(L.npvp_frameln_act_fwd_parts(_ptr(h2), _ptr(part2), hid // 512, 32768.0, 1e-5, _row(stats, 2), _row(stats, 3), _ptr(n2w),
-                                           _ptr(n2b), None, _ptr(a2), frames, PFh, d2.p, d2.salt, 0.0, 0, 1, _ptr(seed), _ptr(a2_slot),
-                                           st), "npvp_frameln_act_fwd_parts")
+        check(L.npvp_frameln_act_fwd_parts_skip(_ptr(h2), _ptr(part2), hid // 512, 32768.0, 1e-5, _row(stats, 2), _row(stats, 3),
+                                                _ptr(n2w), _ptr(n2b), None, _ptr(a2), frames, PFh, d2.p, d2.salt, 0.0, 0, 1, _ptr(seed),
+                                                _ptr(a2_slot), sk.p, sk.salt, T, st), "npvp_frameln_act_fwd_parts_skip")
         tag_amax(a2, a2_slot)
         # fc2 (+ statistics), norm3 + GELU + dropout + residual + drop-path
         h3 = torch.empty(R, Co, dtype=f32, device=dev)
         part3 = torch.empty(frames * (Co // 64) * 2, dtype=f32, device=dev)
         gemm(1, 1, R, Co, hid, a2, hid, w2, w2.stride(0), h3, bias=b2, b_pre=_planes(w2, "F", R),
-             rowstats=part3)
+             rowstats=part3, row_skip=rs)
         DropRecorder.note(d3, "elem", R * Co)
         DropRecorder.note(dp, "group", frames // max(1, T))
         out = torch.empty(R, Co, dtype=f32, device=dev)
-        check(L.npvp_frameln_act_fwd_parts(_ptr(h3), _ptr(part3), Co // 64, 4096.0, 1e-5, _row(stats, 4), _row(stats, 5), _ptr(n3w),
-                                           _ptr(n3b), _ptr(res), _ptr(out), frames, PFo, d3.p, d3.salt, dp.p, dp.salt, T, _ptr(seed),
-                                           None, st), "npvp_frameln_act_fwd_parts")
+        check(L.npvp_frameln_act_fwd_parts_skip(_ptr(h3), _ptr(part3), Co // 64, 4096.0, 1e-5, _row(stats, 4), _row(stats, 5),
+                                                _ptr(n3w), _ptr(n3b), _ptr(res), _ptr(out), frames, PFo, d3.p, d3.salt, dp.p, dp.salt, T,
+                                                _ptr(seed), None, sk.p, sk.salt, T, st), "npvp_frameln_act_fwd_parts_skip")
         ctx.save_for_backward(x, h1, h2, a2, h3, stats, wtb, w1, w2, n1w, n1b, n2w, n2b, n3w, n3b)
         ctx.cfg = (frames, T, d2, d3, dp, res is not None, b1 is not None, b2 is not None)
+        ctx.skip = (sk, T, rs) if sk.on else None          # (taken in forward: backward leaves out what forward left out)
         ctx.sinks = (_wb_sink(w1, b1), _wb_sink(w2, b2), _ln_sink(n1w, n1b), _ln_sink(n2w, n2b), _ln_sink(n3w, n3b))
         sd = _wb_sink(dww, dwb) if (dww.is_contiguous() and dwb is not None) else None
         ctx.sink_dw = sd if (sd and sd[1] is not None) else None
@@ -1552,9 +1568,11 @@ class _MlpDwbn(torch.autograd.Function):
         R, hid = h1.shape
         Co = h3.shape[1]
         dev = x.device
+        sk, sT, rs = ctx.skip if ctx.skip else (NO_DROP, 1, NO_DROP)
+        skip = (sk, sT) if sk.on else None
         dout = _c(dout)
         dh3, gn3w, gn3b = _fln_bwd(dout, h3, stats[4], stats[5], n3w, n3b, frames, 64 * Co, d3, dp, T, s_n3)
-        da2, gw2, gb2 = linear_bwd(dh3, a2, w2, True if has_b2 else None, s_fc2)     # (`b` only says whether there is a bias gradient to take)
+        da2, gw2, gb2 = linear_bwd(dh3, a2, w2, True if has_b2 else None, s_fc2, row_skip=rs)     # (`b` only says whether there is a bias gradient to take)
         fuse_n2 = MID_BWD_N2 and hid // 16 <= 256
         if fuse_n2:
             # norm2's backward WITHOUT its input gradient: frame sums (partials) + parameter gradients in one pass over da2 / h2;
@@ -1597,14 +1615,19 @@ class _MlpDwbn(torch.autograd.Function):
             check(L.npvp_transpose(_ptr(dwtb), _ptr(gdww), 1, 9, hid, _stream()), "npvp_transpose")
             gdwb = dwtb[9]
         dh1, gn1w, gn1b = _fln_bwd(da1, h1, stats[0], stats[1], n1w, n1b, frames, 64 * hid, NO_DROP, NO_DROP, 1, s_n1,
-                                      psum=psum, nparts=nparts)
+                                      psum=psum, nparts=nparts, skip=skip)
         del da1
-        dx, gw1, gb1 = linear_bwd(dh1, x, w1, True if has_b1 else None, s_fc1)
+        dx, gw1, gb1 = linear_bwd(dh1, x, w1, True if has_b1 else None, s_fc1, row_skip=rs)
         return (dx, dout if has_res else None, gw1, gb1, gn1w, gn1b, gdww, gdwb, gn2w, gn2b, gw2, gb2, gn3w, gn3b,
                 None, None, None, None)
 
 
 MID_BWD_N2 = True        # (False: norm2's backward as two kernels of its own - the op test compares the two routes)
+# The node leaves out work on the samples its DropPath drops: its forward frame kernels and norm1's backward write zeros for their
+# frames (csrc/common.h FrameSkip) and the fc1 / fc2 forward and dgrad GEMMs run the tiles inside them on zero accumulators
+# (GemmParams::rskip); the decision is taken on the device from the seed.  The fused middle's backward, norm2's parameter-gradient
+# pass and the weight gradients compute every frame (profiles/droppath_skip.txt).  False: nothing is left out (A/B runs, tests).
+DROP_PATH_SKIP = True
 
 
 def mlpdwbn_fused_supported(R, C, hid, Co, H, W):

@@ -1,5 +1,5 @@
 """MlpDWBN forward + backward at a workload's decoder size (frames of 64 tokens, C = 512, hidden = 2048), stand-alone.
-python tools/mlpdw_bench.py [frames]   (NPVP_WGRAD_STREAM=0 for one stream)"""
+python tools/mlpdw_bench.py [frames] [skip|noskip]   (NPVP_WGRAD_STREAM=0 for one stream; noskip: ops.DROP_PATH_SKIP = False)"""
 import os
 import sys
 import torch
@@ -7,6 +7,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from npvp_amd import ops
 
 frames = int(sys.argv[1]) if len(sys.argv) > 1 else 1792
+ops.DROP_PATH_SKIP = not (len(sys.argv) > 2 and sys.argv[2] == "noskip")
 dev = "cuda:0"
 C, hid, P = 512, 2048, 64
 R = frames * P
@@ -36,11 +37,20 @@ def run():
 for _ in range(3):
     run()
 torch.cuda.synchronize()
-ts = []
+ts, fw, dropped = [], [], []
 for _ in range(8):
+    ops.DropRecorder.sites = []
+    f0, f1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    f0.record()
     e0, e1, gr = run()
+    site = [s for s in ops.DropRecorder.sites if s[1] == "group"][0]
+    ops.DropRecorder.sites = None
     torch.cuda.synchronize()
+    dropped.append(int((ops.DropRecorder.mask(site, torch.device(dev)) == 0).sum()))       # samples the layer's DropPath dropped
     ts.append(e0.elapsed_time(e1))
+    fw.append(f0.elapsed_time(e0))
+print(f"DROP_PATH_SKIP={ops.DROP_PATH_SKIP}: per run (forward us, backward us, dropped samples of {frames // 28}): "
+      + ", ".join(f"({a * 1e3:.0f}, {b * 1e3:.0f}, {d})" for a, b, d in zip(fw, ts, dropped)))
 ts.sort()
 print(f"frames={frames}: backward {ts[len(ts) // 2] * 1e3:.0f} us (median of 8); "
       f"checks dx {float(gr[0].double().abs().sum()):.6e} dn2w {float(gr[8].double().abs().sum()):.6e} ddww {float(gr[6].double().abs().sum()):.6e} "
