@@ -508,7 +508,8 @@ int npvp_sum_all(const float* x, long long n, float* out, void* workspace, long 
 
 /* ---- optimiser step of training_step_no_gan (ref/models/Predictor.py:135-136,197): clip_grad_norm_
  * over a flat gradient range, then torch.optim.AdamW semantics on flat buffers.  hyper = {lr, step}
- * and clip = {norm, coef} live in device memory. */
+ * and clip = {norm, coef} live in device memory.  clip may be NULL (nothing is scaled); with a clip,
+ * 0 <= clip_begin <= clip_end <= n.  The flat buffers are 16-byte aligned; the workspace holds 1024 floats. */
 int npvp_grad_norm_clip(const float* g, long long n, float max_norm, float* out2, void* workspace, long long ws_bytes,
                         npvp_stream_t stream);
 int npvp_adamw_step(float* p, float* g, float* m, float* v, long long n, const float* hyper, float beta1, float beta2,

@@ -185,7 +185,7 @@ using namespace npvp;
 
 extern "C" int npvp_drop_apply(const float* x, float* out, long long rows, int ncols, float p, int mode, int g1, int g2,
                                const unsigned long long* seed, unsigned int salt, float* amax, hipStream_t stream) {
-  NPVP_CHECK_ARG(rows > 0 && ncols % 4 == 0, "drop_apply: bad shape");
+  NPVP_CHECK_ARG(x && out && rows > 0 && ncols % 4 == 0, "drop_apply: bad shape or a null buffer");
   NPVP_CHECK_ARG(p > 0.f && p < 1.f && seed, "drop_apply: needs 0 < p < 1 and a device seed");
   const DropSpec d = make_drop_spec(p, salt, mode, g1, g2);
   NPVP_LAUNCH(drop_apply_kernel, dim3(ew_blocks(rows * (ncols / 4), 256)), dim3(256), 0, stream, x, out, rows, ncols,
@@ -195,7 +195,7 @@ extern "C" int npvp_drop_apply(const float* x, float* out, long long rows, int n
 }
 
 extern "C" int npvp_transpose(const float* in, float* out, int batch, int R, int C, hipStream_t stream) {
-  NPVP_CHECK_ARG(batch > 0 && R > 0 && C > 0 && batch <= 65535, "transpose: bad shape");
+  NPVP_CHECK_ARG(in && out && batch > 0 && R > 0 && C > 0 && batch <= 65535, "transpose: bad shape or a null buffer");
   NPVP_LAUNCH(transpose_kernel, dim3((C + 31) / 32, (R + 31) / 32, batch), dim3(256), 0, stream, in, out, R, C);
   NPVP_CHECK_LAUNCH();
   return NPVP_OK;
@@ -240,7 +240,7 @@ extern "C" int npvp_dwtb_accumulate(const float* dwtb, float* gw, float* gb, int
 }
 
 int npvp_reduce_mid_launch(const float* in, float* out, int A, int B, long long Cc, float scale, hipStream_t stream, int accumulate) {
-  NPVP_CHECK_ARG(A > 0 && B > 0 && Cc > 0 && Cc % 4 == 0, "reduce_mid: bad shape");
+  NPVP_CHECK_ARG(in && out && A > 0 && B > 0 && Cc > 0 && Cc % 4 == 0, "reduce_mid: bad shape or a null buffer");
   NPVP_LAUNCH(reduce_mid_kernel, dim3(ew_blocks((long long)A * Cc / 4, 256)), dim3(256), 0, stream, in, out, A, B, Cc,
                      scale, accumulate ? 1 : 0);
   NPVP_CHECK_LAUNCH();
@@ -253,7 +253,7 @@ extern "C" int npvp_reduce_mid(const float* in, float* out, int A, int B, long l
 }
 
 extern "C" int npvp_broadcast_mid(const float* in, float* out, int A, int B, long long Cc, float scale, hipStream_t stream) {
-  NPVP_CHECK_ARG(A > 0 && B > 0 && Cc > 0 && Cc % 4 == 0, "broadcast_mid: bad shape");
+  NPVP_CHECK_ARG(in && out && A > 0 && B > 0 && Cc > 0 && Cc % 4 == 0, "broadcast_mid: bad shape or a null buffer");
   NPVP_LAUNCH(broadcast_mid_kernel, dim3(ew_blocks((long long)A * B * Cc / 4, 256)), dim3(256), 0, stream, in, out, A,
                      B, Cc, scale);
   NPVP_CHECK_LAUNCH();
@@ -272,7 +272,7 @@ extern "C" long long npvp_colsum_workspace_bytes(long long rows, int N) { return
 // out[n] = sum_r x[r][n]
 extern "C" int npvp_colsum(const float* x, long long rows, int N, long long ld, float* out, int accumulate, void* workspace,
                            long long ws_bytes, hipStream_t stream) {
-  NPVP_CHECK_ARG(rows > 0 && N > 0 && N % 4 == 0 && ld % 4 == 0, "colsum: bad shape");
+  NPVP_CHECK_ARG(x && out && rows > 0 && N > 0 && N % 4 == 0 && ld % 4 == 0, "colsum: bad shape or a null buffer");
   NPVP_CHECK_ARG(workspace && ws_bytes >= npvp_colsum_workspace_bytes(rows, N), "colsum: workspace too small");
   const Partials P = colsum_partials(workspace, out, rows, N, accumulate);
   NPVP_LAUNCH(colsum_partial_kernel, dim3((N / 4 + 255) / 256, P.job.nb), dim3(256), 0, stream, x, P.part(), rows, N, ld,
@@ -375,7 +375,7 @@ extern "C" int npvp_sum_all(const float* x, long long n, float* out, void* works
 // out2 = {norm, clip coefficient}; workspace >= 1024 floats
 extern "C" int npvp_grad_norm_clip(const float* g, long long n, float max_norm, float* out2, void* workspace,
                                    long long ws_bytes, hipStream_t stream) {
-  NPVP_CHECK_ARG(n > 0 && ((uintptr_t)g % 16) == 0, "grad_norm_clip: bad buffer");
+  NPVP_CHECK_ARG(g && out2 && n > 0 && ((uintptr_t)g % 16) == 0, "grad_norm_clip: bad buffer");
   NPVP_CHECK_ARG(workspace && ws_bytes >= 1024 * 4, "grad_norm_clip: workspace too small");
   long long nb = (n / 4 + 255) / 256; if (nb > 1024) nb = 1024; if (nb < 1) nb = 1;
   NPVP_LAUNCH(sumsq_partial_kernel, dim3((unsigned)nb), dim3(256), 0, stream, g, n, (float*)workspace);
@@ -388,7 +388,8 @@ extern "C" int npvp_grad_norm_clip(const float* g, long long n, float max_norm, 
 extern "C" int npvp_adamw_step(float* p, float* g, float* m, float* v, long long n, const float* hyper, float beta1,
                                float beta2, float eps, float weight_decay, const float* clip, long long clip_begin,
                                long long clip_end, int write_back_grad, hipStream_t stream) {
-  NPVP_CHECK_ARG(n > 0 && hyper, "adamw: bad arguments");
+  NPVP_CHECK_ARG(p && g && m && v && n > 0 && hyper, "adamw: bad arguments");
+  NPVP_CHECK_ARG(!clip || (0 <= clip_begin && clip_begin <= clip_end && clip_end <= n), "adamw: the clip range must lie in [0, n]");
   NPVP_CHECK_ARG((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0, "adamw: the flat buffers must be 16-byte aligned");
   NPVP_LAUNCH(adamw_kernel, dim3(ew_blocks((n + 3) / 4, 256)), dim3(256), 0, stream, p, g, m, v, n, hyper, beta1, beta2, eps,
                      weight_decay, clip, clip_begin, clip_end, write_back_grad);
