@@ -8,13 +8,27 @@
 //           the enc-dec case; mask_mode 1 = the encoder's "no query but the last sees the last
 //           time-step" mask (:100-102).
 // q/k/v/o carry their own row stride so that the q and k projections can live in one
-// [rows, 2C] buffer.  Sequence lengths are <= 32 and d = 64, so the core is latency bound, not MFMA
-// work: one wavefront per (group, head); the shipped kernels run every 16x16 product on
-// v_mfma_f32_16x16x4_f32 (exact fp32) with operands taken straight from global memory
-// (attn_*_mfma_kernel) or, for the backward of 17..32 query rows, from tiles staged once in LDS
-// (attn_bwd_staged1_kernel); softmax in registers, attention dropout replayed in backward from a counter
-// hash.  (The first-generation LDS kernels and the two-orientation staged backward are in the history of this
-// file: removed in round 4.)  Algorithmic bytes: 4*C*4 B per token fwd (q,k,v read + o write).
+// [rows, 2C] buffer.  d = 64.  Every shipped configuration has sequences of <= 32 rows, where the core is latency
+// bound, not MFMA work: one wavefront per (group, head), every 16x16 product on v_mfma_f32_16x16x4_f32
+// (exact fp32) with operands taken straight from global memory (attn_*_mfma_kernel) or, for the backward
+// of 17..32 query rows, from tiles staged once in LDS (attn_bwd_staged1_kernel); softmax in registers,
+// attention dropout replayed in backward from a counter hash.  33..128 rows take the scalar generic kernels
+// (attn_*_generic_kernel), any length the streaming kernels (attn_long_*_kernel, npvp_attn_long_*).
+// Algorithmic bytes: 4*C*4 B per token fwd (q,k,v read + o write).
+//
+// All kernels compute ONE function.  What they must agree on is written once, below, and every kernel uses it:
+//   attn_dead            the mask predicate: is key j dead for query q
+//   attn_keep            the dropout factor of element (wave id, query, key) - the only place its key is spelled out;
+//                        a backward replays the mask of ANY forward route because both call this
+//   AttnWave / attn_wave what a wave or workgroup resolves from (p, wid): head, token rows, lengths, dropout seed
+//   attn_row_block       the orientation-A softmax row (scores, mask, maximum, exponentials, 1 / sum; backward: dP too) of
+//                        the one- and two-block kernels
+//   attn_fwd_qblock      one 16-query block of the forward (attn_fwd_mfma_kernel, attn_samples_fwd_mfma_kernel)
+//   attn_bwd_row_stats   dropout on dP, normalised P, rs = sum_j dP P (attn_bwd_mfma_kernel, attn_bwd_staged1_kernel)
+// Host side: attn_setup (geometry, limits, dropout), attn_bind_fwd / attn_bind_bwd (operands, strides, amax slots).
+// A new attention kernel uses these; it does not write the mask, the key or the row again.
+#include <cstdio>
+
 #include "common.h"
 
 namespace npvp {
@@ -69,10 +83,33 @@ __device__ __forceinline__ long long attn_row(const AttnRows& r, int m, int Tn) 
   return (r.a * Tn + m) * r.P + r.b;
 }
 
+// THE mask: key j does not exist, or it is the last time-step and query q is not the last (mask_mode 1, the encoder's mask).
+// MASK = false: a kernel that never runs with mask_mode 1 (the sampler) tests the sequence end only.
+template <bool MASK = true>
+__device__ __forceinline__ bool attn_dead(int mask_mode, int L, int S, int q, int j) {
+  return j >= S || (MASK && mask_mode == 1 && j == S - 1 && q < L - 1);
+}
+// THE dropout factor (0 or 1 / keep) of probability (wid, q, j): element [wid][q][j] of the [groups * heads, L, S] weights.
+// Callers guard with p.drop_thresh (and liveness) where that decides whether the hash is evaluated at all.
+__device__ __forceinline__ float attn_keep(const AttnParams& p, unsigned long long seed, unsigned long long wid, int L, int S, int q, int j) {
+  return drop_scale(seed, p.salt, (wid * L + q) * S + j, p.drop_thresh, p.drop_inv_keep);
+}
+// What one wave (MFMA kernels) or workgroup (staged, generic, streaming kernels) resolves from its (group, head) index wid.
+struct AttnWave { int head; AttnRows g; int L, S, Tq, Tk; unsigned long long seed; };
+__device__ __forceinline__ AttnWave attn_wave(const AttnParams& p, unsigned int wid) {
+  AttnWave aw;
+  aw.head = (int)(wid % (unsigned int)p.heads);
+  aw.g = attn_rows(p, wid / (unsigned int)p.heads);
+  aw.L = p.L; aw.S = p.S;
+  aw.Tq = p.mode == 1 ? p.Tq : 0; aw.Tk = p.mode == 1 ? p.Tk : 0;
+  aw.seed = (p.seed && p.drop_thresh) ? *p.seed : 0ull;
+  return aw;
+}
+
 // =====================================================================================================
 // MFMA form (sequences up to 32 = one or two 16-row blocks per side): no LDS at all.
-// The LDS kernels above spend their time on ds_reads (every lane re-reads whole K / V rows for its dot products:
-// ~400 KB of LDS traffic per wave in backward, 21.6 KB of LDS per wave -> 6 waves per CU).  Here every 16x16 product
+// The first-generation LDS kernels (removed) spent their time on ds_reads (every lane re-read whole K / V rows for its dot
+// products: ~400 KB of LDS traffic per wave in backward, 21.6 KB of LDS per wave -> 6 waves per CU).  Here every 16x16 product
 // runs on v_mfma_f32_16x16x4_f32 (exact fp32 products, fp32 accumulate) with operands loaded from global memory
 // straight into the MFMA operand layout.  With lane = 16*c + n the instruction takes A[m=n][k=c], B[k=c][col=n] and
 // returns D[4c+i][n] in register i.  Two tricks make every load a coalesced float4 and remove all transposes:
@@ -146,68 +183,124 @@ __device__ __forceinline__ f32x4_t attn_mm_d(const AttnTileR& a, const AttnTileR
 __device__ __forceinline__ float quad_max(float v) { v = fmaxf(v, __shfl_xor(v, 16, 64)); return fmaxf(v, __shfl_xor(v, 32, 64)); }
 __device__ __forceinline__ float quad_sum(float v) { v += __shfl_xor(v, 16, 64); return v + __shfl_xor(v, 32, 64); }
 
+// ---- THE softmax row of the one- and two-block kernels, orientation A: sc[kb][i] = S[query q][key 16kb + 4c+i] for the NK key
+// blocks, q = 16 qb + n on the lanes.  Leaves sc as UN-normalised exponentials (0 for a dead key), the row maximum in mx and
+// 1 / sum in inv.  BWD: dp[kb][i] = (dO V^T) of the same element, from the same loop (forward: dp, vr, gr null).  ktile(kb)
+// yields the "R" tile of key block kb (registers, or LDS in the staged kernel).  scale, mask_mode, L, S by value: what a kernel
+// holds in registers anyway.
+template <int NK, bool MASK, bool BWD, class KT>
+__device__ __forceinline__ void attn_row_block(float (&sc)[NK][4], float (*dp)[4], float& mx, float& inv, KT&& ktile, const AttnTileR& qr,
+                                               const AttnTileR* vr, const AttnTileR* gr, float scale, int mask_mode, int L, int S, int q, int c) {
+  mx = -INFINITY;
+#pragma unroll
+  for (int kb = 0; kb < NK; ++kb) {
+    const f32x4_t sa = attn_mm_d(ktile(kb), qr);
+    f32x4_t da = {0.f, 0.f, 0.f, 0.f};
+    if constexpr (BWD) da = attn_mm_d(vr[kb], *gr);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      float s = sa[i] * scale;
+      if (attn_dead<MASK>(mask_mode, L, S, q, 16 * kb + 4 * c + i)) s = -INFINITY;
+      sc[kb][i] = s; mx = fmaxf(mx, s);
+      if constexpr (BWD) dp[kb][i] = da[i];
+    }
+  }
+  mx = quad_max(mx);
+  float sum = 0.f;
+#pragma unroll
+  for (int kb = 0; kb < NK; ++kb)
+#pragma unroll
+    for (int i = 0; i < 4; ++i) { sc[kb][i] = (sc[kb][i] == -INFINITY) ? 0.f : __expf(sc[kb][i] - mx); sum += sc[kb][i]; }
+  sum = quad_sum(sum);
+  inv = 1.f / sum;
+}
+
+// ---- one 16-query block of the forward on K / V tiles held in registers: load Q, the softmax row, normalise, dropout, P V, store.
+// gq = the token rows of the QUERY side (the sampler's are another clip's than aw.g).  PLAIN: a kernel without mask and dropout
+// (the sampler) tests neither.
+template <int NK, bool PLAIN>
+__device__ __forceinline__ void attn_fwd_qblock(const AttnParams& p, const AttnWave& aw, const AttnRows& gq, unsigned long long wid,
+                                                const AttnTileR (&kr)[NK], const AttnTileG (&vg)[NK], int qb, int n, int c, float& am_o) {
+  const int L = aw.L, S = aw.S;
+  AttnTileR qr;
+  attn_load_r(qr, p.q, p.ld_q, p, gq, L, aw.Tq, aw.head, n, c, qb);
+  __builtin_amdgcn_sched_barrier(0);      // all tile loads in flight before the first MFMA waits for one of them
+  const int q = 16 * qb + n, qn = min(q, L - 1);
+  float sc[NK][4], mx, inv;
+  attn_row_block<NK, !PLAIN, false>(sc, nullptr, mx, inv, [&](int kb) -> const AttnTileR& { return kr[kb]; }, qr, nullptr, nullptr, p.scale,
+                                    p.mask_mode, L, S, q, c);
+  f32x4_t o[4];
+  attn_zero(o);
+#pragma unroll
+  for (int kb = 0; kb < NK; ++kb) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int j = 16 * kb + 4 * c + i;
+      sc[kb][i] *= inv;
+      if constexpr (!PLAIN)      // (expect 0: stays a branch, so the hash is not evaluated with dropout off or past the last key)
+        if (__builtin_expect(p.drop_thresh && j < S, 0)) sc[kb][i] *= attn_keep(p, aw.seed, wid, L, S, qn, j);
+    }
+    attn_mm_rows(o, sc[kb], vg[kb]);
+  }
+  attn_store_d(o, p.o, p.ld_o, p, gq, L, aw.Tq, aw.head, n, c, qb, am_o);
+}
+
+// a product that is rounded once: never contracted into a later sum, wherever the compiler puts the two
+__device__ __forceinline__ float mul_rounded(float a, float b) {
+#pragma clang fp contract(off)
+  return a * b;
+}
+// ---- dropout on dP, P normalised, rs = sum_j dP P of query row qn (all lanes of the quad), shared by the two backward kernels.
+// dS = sc (dp - rs) scale is left to the caller.  STAGED (attn_bwd_staged1_kernel): also pm = P with the dropout mask (what
+// multiplies dO in dV), and dP m is rounded before dS subtracts rs from it, where the MFMA kernel leaves that pair to the
+// compiler's contraction - the last bit of dQ / dK each kernel has always produced; one form for both would change it.
+template <int NK, bool STAGED>
+__device__ __forceinline__ float attn_bwd_row_stats(float (&sc)[NK][4], float (&dp)[NK][4], float (*pm)[4], float inv, const AttnParams& p,
+                                                    unsigned long long seed, unsigned long long wid, int L, int S, int qn, int c) {
+  float rs = 0.f, m[NK][4];
+#pragma unroll
+  for (int kb = 0; kb < NK; ++kb)
+#pragma unroll
+    for (int i = 0; i < 4; ++i) m[kb][i] = 1.f;
+  if (p.drop_thresh) {      // the uniform switch once, around all hashes: nothing of them runs with dropout off
+#pragma unroll
+    for (int kb = 0; kb < NK; ++kb)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int j = 16 * kb + 4 * c + i;
+        if (j < S) m[kb][i] = attn_keep(p, seed, wid, L, S, qn, j);
+      }
+  }
+#pragma unroll
+  for (int kb = 0; kb < NK; ++kb)
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      sc[kb][i] *= inv;
+      if constexpr (STAGED) pm[kb][i] = sc[kb][i] * m[kb][i];
+      dp[kb][i] = STAGED ? mul_rounded(dp[kb][i], m[kb][i]) : dp[kb][i] * m[kb][i];
+      rs += dp[kb][i] * sc[kb][i];
+    }
+  return quad_sum(rs);
+}
+
 // NQ / NK = number of 16-row blocks of the query / key sequence (1 or 2)
 template <int NQ, int NK>
 __global__ __launch_bounds__(256) void attn_fwd_mfma_kernel(AttnParams p) {
   const int lane = threadIdx.x & 63, n = lane & 15, c = lane >> 4;
   const long long wid = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (wid >= p.total) return;                      // waves are independent: no barriers in this kernel
-  const int head = (int)((unsigned int)wid % (unsigned int)p.heads);
-  const AttnRows g = attn_rows(p, (unsigned int)wid / (unsigned int)p.heads);
-  const int L = p.L, S = p.S;
-  const int Tq = p.mode == 1 ? p.Tq : 0, Tk = p.mode == 1 ? p.Tk : 0;
-  const unsigned long long seed = (p.seed && p.drop_thresh) ? *p.seed : 0ull;
+  const AttnWave aw = attn_wave(p, (unsigned int)wid);
   AttnTileR kr[NK];
   AttnTileG vg[NK];
   float am_o = 0.f;
   const unsigned int pk_o = amax_peek_wave(p.o_amax);
 #pragma unroll
   for (int kb = 0; kb < NK; ++kb) {
-    attn_load_r(kr[kb], p.k, p.ld_k, p, g, S, Tk, head, n, c, kb);
-    attn_load_g(vg[kb], p.v, p.ld_v, p, g, S, Tk, head, n, c, kb);
+    attn_load_r(kr[kb], p.k, p.ld_k, p, aw.g, aw.S, aw.Tk, aw.head, n, c, kb);
+    attn_load_g(vg[kb], p.v, p.ld_v, p, aw.g, aw.S, aw.Tk, aw.head, n, c, kb);
   }
 #pragma unroll
-  for (int qb = 0; qb < NQ; ++qb) {
-    AttnTileR qr;
-    attn_load_r(qr, p.q, p.ld_q, p, g, L, Tq, head, n, c, qb);
-    __builtin_amdgcn_sched_barrier(0);      // all tile loads in flight before the first MFMA waits for one of them
-    const int q = 16 * qb + n, qn = min(q, L - 1);
-    // orientation A: sc[kb][i] = S[query q][key 16kb + 4c+i]
-    float sc[NK][4], mx = -INFINITY;
-#pragma unroll
-    for (int kb = 0; kb < NK; ++kb) {
-      const f32x4_t sa = attn_mm_d(kr[kb], qr);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int j = 16 * kb + 4 * c + i;
-        float s = sa[i] * p.scale;
-        if (j >= S || (p.mask_mode == 1 && j == S - 1 && q < L - 1)) s = -INFINITY;
-        sc[kb][i] = s; mx = fmaxf(mx, s);
-      }
-    }
-    mx = quad_max(mx);
-    float sum = 0.f;
-#pragma unroll
-    for (int kb = 0; kb < NK; ++kb)
-#pragma unroll
-      for (int i = 0; i < 4; ++i) { sc[kb][i] = (sc[kb][i] == -INFINITY) ? 0.f : __expf(sc[kb][i] - mx); sum += sc[kb][i]; }
-    sum = quad_sum(sum);
-    const float inv = 1.f / sum;
-    f32x4_t o[4];
-    attn_zero(o);
-#pragma unroll
-    for (int kb = 0; kb < NK; ++kb) {
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int j = 16 * kb + 4 * c + i;
-        sc[kb][i] *= inv;
-        if (p.drop_thresh && j < S)
-          sc[kb][i] *= drop_scale(seed, p.salt, ((unsigned long long)wid * L + qn) * S + j, p.drop_thresh, p.drop_inv_keep);
-      }
-      attn_mm_rows(o, sc[kb], vg[kb]);
-    }
-    attn_store_d(o, p.o, p.ld_o, p, g, L, Tq, head, n, c, qb, am_o);
-  }
+  for (int qb = 0; qb < NQ; ++qb) attn_fwd_qblock<NK, false>(p, aw, aw.g, wid, kr, vg, qb, n, c, am_o);
   amax_slot_commit(p.o_amax, am_o, pk_o);
 }
 
@@ -215,68 +308,33 @@ __global__ __launch_bounds__(256) void attn_fwd_mfma_kernel(AttnParams p) {
 // (mode 1) geometry, no mask, no dropout.  The decoder of the sampler runs on S * N clips (sample-major: clip s * N + n), the memory
 // and its K / V projections stay at N clips.  One wave owns (clip n, pixel, head, a chunk of samples): it loads that group's K and
 // V tiles into registers once - exactly the tiles attn_fwd_mfma_kernel loads - and then runs that kernel's query-block body
-// (attn_load_r, attn_mm_d, the same scale / maximum / __expf / sum / normalise order, attn_mm_rows, attn_store_d) once per sample
-// of its chunk, so a sample's output is bit for bit what attn_fwd_mfma_kernel writes for that sample's slab of q against the same
-// K / V, whatever the chunk.  The query side's clip index s * N + n is resolved here (gq); AttnRows / attn_row are as they were.
+// (attn_fwd_qblock, in its form without mask and dropout) once per sample of its chunk, so a sample's output is bit for bit what
+// attn_fwd_mfma_kernel writes for that sample's slab of q against the same K / V, whatever the chunk.  The query side's clip index
+// s * N + n is resolved here (gq); AttnRows / attn_row are as they were.
 template <int NQ, int NK>
 __global__ __launch_bounds__(256) void attn_samples_fwd_mfma_kernel(AttnParams p, int nsamp, int nclip, int chunk) {
   const int lane = threadIdx.x & 63, n = lane & 15, c = lane >> 4;
   const long long wid = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (wid >= p.total) return;                      // waves are independent: no barriers in this kernel
-  const int head = (int)((unsigned int)wid % (unsigned int)p.heads);
   const unsigned int gi = (unsigned int)wid / (unsigned int)p.heads, ngroup = (unsigned int)nclip * (unsigned int)p.P;
   const unsigned int ck = gi / ngroup;             // which chunk of samples
-  AttnRows gk = attn_rows(p, gi - ck * ngroup);    // a = clip n, b = pixel
-  AttnRows gq = gk;
-  const int L = p.L, S = p.S, Tq = p.Tq, Tk = p.Tk;
+  // the key side's wave (a = clip n, b = pixel): mode 1, no dropout seed
+  const AttnWave aw = {(int)((unsigned int)wid % (unsigned int)p.heads), attn_rows(p, gi - ck * ngroup), p.L, p.S, p.Tq, p.Tk, 0ull};
+  AttnRows gq = aw.g;
   AttnTileR kr[NK];
   AttnTileG vg[NK];
   float am_o = 0.f;
   const unsigned int pk_o = amax_peek_wave(p.o_amax);
 #pragma unroll
   for (int kb = 0; kb < NK; ++kb) {
-    attn_load_r(kr[kb], p.k, p.ld_k, p, gk, S, Tk, head, n, c, kb);
-    attn_load_g(vg[kb], p.v, p.ld_v, p, gk, S, Tk, head, n, c, kb);
+    attn_load_r(kr[kb], p.k, p.ld_k, p, aw.g, aw.S, aw.Tk, aw.head, n, c, kb);
+    attn_load_g(vg[kb], p.v, p.ld_v, p, aw.g, aw.S, aw.Tk, aw.head, n, c, kb);
   }
   const int s_end = min(nsamp, ((int)ck + 1) * chunk);
   for (int s = (int)ck * chunk; s < s_end; ++s) {
-    gq.a = s * nclip + gk.a;
+    gq.a = s * nclip + aw.g.a;
 #pragma unroll
-    for (int qb = 0; qb < NQ; ++qb) {
-      AttnTileR qr;
-      attn_load_r(qr, p.q, p.ld_q, p, gq, L, Tq, head, n, c, qb);
-      __builtin_amdgcn_sched_barrier(0);      // all tile loads in flight before the first MFMA waits for one of them
-      // orientation A: sc[kb][i] = S[query 16qb + n][key 16kb + 4c+i]
-      float sc[NK][4], mx = -INFINITY;
-#pragma unroll
-      for (int kb = 0; kb < NK; ++kb) {
-        const f32x4_t sa = attn_mm_d(kr[kb], qr);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const int j = 16 * kb + 4 * c + i;
-          float sv = sa[i] * p.scale;
-          if (j >= S) sv = -INFINITY;
-          sc[kb][i] = sv; mx = fmaxf(mx, sv);
-        }
-      }
-      mx = quad_max(mx);
-      float sum = 0.f;
-#pragma unroll
-      for (int kb = 0; kb < NK; ++kb)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) { sc[kb][i] = (sc[kb][i] == -INFINITY) ? 0.f : __expf(sc[kb][i] - mx); sum += sc[kb][i]; }
-      sum = quad_sum(sum);
-      const float inv = 1.f / sum;
-      f32x4_t o[4];
-      attn_zero(o);
-#pragma unroll
-      for (int kb = 0; kb < NK; ++kb) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) sc[kb][i] *= inv;
-        attn_mm_rows(o, sc[kb], vg[kb]);
-      }
-      attn_store_d(o, p.o, p.ld_o, p, gq, L, Tq, head, n, c, qb, am_o);
-    }
+    for (int qb = 0; qb < NQ; ++qb) attn_fwd_qblock<NK, true>(p, aw, gq, 0ull, kr, vg, qb, n, c, am_o);
   }
   amax_slot_commit(p.o_amax, am_o, pk_o);
 }
@@ -286,11 +344,8 @@ __global__ __launch_bounds__(256) void attn_bwd_mfma_kernel(AttnParams p) {
   const int lane = threadIdx.x & 63, n = lane & 15, c = lane >> 4;
   const long long wid = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (wid >= p.total) return;
-  const int head = (int)((unsigned int)wid % (unsigned int)p.heads);
-  const AttnRows g = attn_rows(p, (unsigned int)wid / (unsigned int)p.heads);
-  const int L = p.L, S = p.S;
-  const int Tq = p.mode == 1 ? p.Tq : 0, Tk = p.mode == 1 ? p.Tk : 0;
-  const unsigned long long seed = (p.seed && p.drop_thresh) ? *p.seed : 0ull;
+  const AttnWave aw = attn_wave(p, (unsigned int)wid);
+  const AttnRows& g = aw.g; const int head = aw.head, L = aw.L, S = aw.S, Tq = aw.Tq, Tk = aw.Tk;
   AttnTileR kr[NK], vr[NK];
 #pragma unroll
   for (int kb = 0; kb < NK; ++kb) {
@@ -310,40 +365,9 @@ __global__ __launch_bounds__(256) void attn_bwd_mfma_kernel(AttnParams p) {
     for (int kb = 0; kb < NK; ++kb) attn_load_g(kg[kb], p.k, p.ld_k, p, g, S, Tk, head, n, c, kb);
     __builtin_amdgcn_sched_barrier(0);      // all tile loads in flight before the first MFMA waits for one of them
     const int q = 16 * qb + n, qn = min(q, L - 1);
-    float sc[NK][4], dp[NK][4], mx = -INFINITY;
-#pragma unroll
-    for (int kb = 0; kb < NK; ++kb) {
-      const f32x4_t sa = attn_mm_d(kr[kb], qr), da = attn_mm_d(vr[kb], gr);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int j = 16 * kb + 4 * c + i;
-        float s = sa[i] * p.scale;
-        if (j >= S || (p.mask_mode == 1 && j == S - 1 && q < L - 1)) s = -INFINITY;
-        sc[kb][i] = s; dp[kb][i] = da[i]; mx = fmaxf(mx, s);
-      }
-    }
-    mx = quad_max(mx);
-    float sum = 0.f;
-#pragma unroll
-    for (int kb = 0; kb < NK; ++kb)
-#pragma unroll
-      for (int i = 0; i < 4; ++i) { sc[kb][i] = (sc[kb][i] == -INFINITY) ? 0.f : __expf(sc[kb][i] - mx); sum += sc[kb][i]; }
-    sum = quad_sum(sum);
-    const float inv = 1.f / sum;
-    float rs = 0.f;
-#pragma unroll
-    for (int kb = 0; kb < NK; ++kb)
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int j = 16 * kb + 4 * c + i;
-        float m = 1.f;
-        if (p.drop_thresh && j < S)
-          m = drop_scale(seed, p.salt, ((unsigned long long)wid * L + qn) * S + j, p.drop_thresh, p.drop_inv_keep);
-        sc[kb][i] *= inv;
-        dp[kb][i] *= m;
-        rs += dp[kb][i] * sc[kb][i];
-      }
-    rs = quad_sum(rs);
+    float sc[NK][4], dp[NK][4], mx, inv;
+    attn_row_block<NK, true, true>(sc, dp, mx, inv, [&](int kb) -> const AttnTileR& { return kr[kb]; }, qr, vr, &gr, p.scale, p.mask_mode, L, S, q, c);
+    const float rs = attn_bwd_row_stats<NK, false>(sc, dp, nullptr, inv, p, aw.seed, wid, L, S, qn, c);
     mxs[qb] = mx; invs[qb] = inv; rss[qb] = rs;
     f32x4_t dq[4];
     attn_zero(dq);
@@ -378,11 +402,10 @@ __global__ __launch_bounds__(256) void attn_bwd_mfma_kernel(AttnParams p) {
       for (int i = 0; i < 4; ++i) {
         const int ql = 4 * c + i, q = 16 * qb + ql;             // statistics of query q live in lane ql of block qb
         const float mxq = __shfl(mxs[qb], ql, 64), invq = __shfl(invs[qb], ql, 64), rsq = __shfl(rss[qb], ql, 64);
-        const bool dead = key >= S || q >= L || (p.mask_mode == 1 && key == S - 1 && q < L - 1);
+        const bool dead = q >= L || attn_dead(p.mask_mode, L, S, q, key);
         const float pr = dead ? 0.f : __expf(sb[i] * p.scale - mxq) * invq;
         float m = 1.f;
-        if (p.drop_thresh && !dead)
-          m = drop_scale(seed, p.salt, ((unsigned long long)wid * L + q) * S + key, p.drop_thresh, p.drop_inv_keep);
+        if (p.drop_thresh && !dead) m = attn_keep(p, aw.seed, wid, L, S, q, key);
         pd[i] = pr * m;
         ds[i] = pr * (db[i] * m - rsq) * p.scale;
       }
@@ -447,12 +470,9 @@ template <int NQ, int NK>
 __global__ __launch_bounds__(64, 2) void attn_bwd_staged1_kernel(AttnParams p) {      // (2 waves / SIMD: <= 256 registers, VGPR + AGPR)
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int lane = threadIdx.x, n = lane & 15, c = lane >> 4;
-  const long long wid = blockIdx.x;
-  const int head = (int)((unsigned int)wid % (unsigned int)p.heads);
-  const AttnRows g = attn_rows(p, (unsigned int)wid / (unsigned int)p.heads);
-  const int L = p.L, S = p.S;
-  const int Tq = p.mode == 1 ? p.Tq : 0, Tk = p.mode == 1 ? p.Tk : 0;
-  const unsigned long long seed = (p.seed && p.drop_thresh) ? *p.seed : 0ull;
+  const unsigned int wid = blockIdx.x;
+  const AttnWave aw = attn_wave(p, wid);
+  const AttnRows& g = aw.g; const int head = aw.head, L = aw.L, S = aw.S, Tq = aw.Tq, Tk = aw.Tk;
   float* Qs = smem;
   float* Gs = Qs + L * LDT;
   float* Ks = Gs + L * LDT;
@@ -483,43 +503,10 @@ __global__ __launch_bounds__(64, 2) void attn_bwd_staged1_kernel(AttnParams p) {
     attn_lds_r(qr, Qs, L, n, c, qb);
     attn_lds_r(gr, Gs, L, n, c, qb);
     const int q = 16 * qb + n, qn = min(q, L - 1);
-    float sc[NK][4], dp[NK][4], mx = -INFINITY;
-#pragma unroll
-    for (int kb = 0; kb < NK; ++kb) {
-      AttnTileR kr;
-      attn_lds_r(kr, Ks, S, n, c, kb);
-      const f32x4_t sa = attn_mm_d(kr, qr), da = attn_mm_d(vr[kb], gr);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int j = 16 * kb + 4 * c + i;
-        float s = sa[i] * p.scale;
-        if (j >= S || (p.mask_mode == 1 && j == S - 1 && q < L - 1)) s = -INFINITY;
-        sc[kb][i] = s; dp[kb][i] = da[i]; mx = fmaxf(mx, s);
-      }
-    }
-    mx = quad_max(mx);
-    float sum = 0.f;
-#pragma unroll
-    for (int kb = 0; kb < NK; ++kb)
-#pragma unroll
-      for (int i = 0; i < 4; ++i) { sc[kb][i] = (sc[kb][i] == -INFINITY) ? 0.f : __expf(sc[kb][i] - mx); sum += sc[kb][i]; }
-    sum = quad_sum(sum);
-    const float inv = 1.f / sum;
-    float rs = 0.f, pm[NK][4];
-#pragma unroll
-    for (int kb = 0; kb < NK; ++kb)
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int j = 16 * kb + 4 * c + i;
-        float m = 1.f;
-        if (p.drop_thresh && j < S)
-          m = drop_scale(seed, p.salt, ((unsigned long long)wid * L + qn) * S + j, p.drop_thresh, p.drop_inv_keep);
-        sc[kb][i] *= inv;
-        pm[kb][i] = sc[kb][i] * m;              // P with the dropout mask: what multiplies dO in dV
-        dp[kb][i] *= m;
-        rs += dp[kb][i] * sc[kb][i];
-      }
-    rs = quad_sum(rs);
+    float sc[NK][4], dp[NK][4], pm[NK][4], mx, inv;
+    attn_row_block<NK, true, true>(sc, dp, mx, inv, [&](int kb) { AttnTileR kr; attn_lds_r(kr, Ks, S, n, c, kb); return kr; }, qr, vr, &gr,
+                                   p.scale, p.mask_mode, L, S, q, c);
+    const float rs = attn_bwd_row_stats<NK, true>(sc, dp, pm, inv, p, aw.seed, wid, L, S, qn, c);
     const bool live = q < L;                    // rows past the end (clamped loads) must not reach dK / dV
     f32x4_t dq[4];
     attn_zero(dq);
@@ -584,12 +571,9 @@ __device__ __forceinline__ float gen_dot(const float* a, const float* b) {      
 
 __global__ __launch_bounds__(GEN_THREADS) void attn_fwd_generic_kernel(AttnParams p) {
   extern __shared__ __attribute__((aligned(16))) float gsm[];
-  const long long wid = blockIdx.x;
-  const int head = (int)((unsigned int)wid % (unsigned int)p.heads);
-  const AttnRows g = attn_rows(p, (unsigned int)wid / (unsigned int)p.heads);
-  const int L = p.L, S = p.S;
-  const int Tq = p.mode == 1 ? p.Tq : 0, Tk = p.mode == 1 ? p.Tk : 0;
-  const unsigned long long seed = (p.seed && p.drop_thresh) ? *p.seed : 0ull;
+  const unsigned int wid = blockIdx.x;
+  const AttnWave aw = attn_wave(p, wid);
+  const AttnRows& g = aw.g; const int head = aw.head, L = aw.L, S = aw.S, Tq = aw.Tq, Tk = aw.Tk;
   float* Ks = gsm; float* Vs = gsm + S * HD;
   gen_stage(Ks, p.k, p.ld_k, p, g, S, Tk, head);
   gen_stage(Vs, p.v, p.ld_v, p, g, S, Tk, head);
@@ -603,12 +587,12 @@ __global__ __launch_bounds__(GEN_THREADS) void attn_fwd_generic_kernel(AttnParam
     for (int d = 0; d < HD; d += 4) { const float4 t = ld4(qp + d); qr[d] = t.x; qr[d + 1] = t.y; qr[d + 2] = t.z; qr[d + 3] = t.w; }
     float mx = -INFINITY;
     for (int j = 0; j < S; ++j) {
-      if (p.mask_mode == 1 && j == S - 1 && q < L - 1) continue;
+      if (attn_dead(p.mask_mode, L, S, q, j)) continue;
       mx = fmaxf(mx, gen_dot(qr, Ks + j * HD) * p.scale);
     }
     float sum = 0.f;
     for (int j = 0; j < S; ++j) {
-      if (p.mask_mode == 1 && j == S - 1 && q < L - 1) continue;
+      if (attn_dead(p.mask_mode, L, S, q, j)) continue;
       sum += __expf(gen_dot(qr, Ks + j * HD) * p.scale - mx);
     }
     const float inv = 1.f / sum;
@@ -616,17 +600,18 @@ __global__ __launch_bounds__(GEN_THREADS) void attn_fwd_generic_kernel(AttnParam
 #pragma unroll
     for (int d = 0; d < HD; ++d) o[d] = 0.f;
     for (int j = 0; j < S; ++j) {
-      if (p.mask_mode == 1 && j == S - 1 && q < L - 1) continue;
+      if (attn_dead(p.mask_mode, L, S, q, j)) continue;
       float pj = __expf(gen_dot(qr, Ks + j * HD) * p.scale - mx) * inv;
-      if (p.drop_thresh) pj *= drop_scale(seed, p.salt, ((unsigned long long)wid * L + q) * S + j, p.drop_thresh, p.drop_inv_keep);
+      if (p.drop_thresh) pj *= attn_keep(p, aw.seed, wid, L, S, q, j);
 #pragma unroll
       for (int d = 0; d < HD; ++d) o[d] += pj * Vs[j * HD + d];
     }
     float* op = p.o + attn_row(g, q, Tq) * p.ld_o + head * HD;
 #pragma unroll
     for (int d = 0; d < HD; d += 4) {
-      st4(op + d, make_float4(o[d], o[d + 1], o[d + 2], o[d + 3]));
-      am_o = fmaxf(fmaxf(am_o, fmaxf(fabsf(o[d]), fabsf(o[d + 1]))), fmaxf(fabsf(o[d + 2]), fabsf(o[d + 3])));
+      const float4 t = make_float4(o[d], o[d + 1], o[d + 2], o[d + 3]);
+      st4(op + d, t);
+      am_o = amax4(am_o, t);
     }
   }
   amax_slot_commit(p.o_amax, am_o, pk_o);
@@ -634,12 +619,9 @@ __global__ __launch_bounds__(GEN_THREADS) void attn_fwd_generic_kernel(AttnParam
 
 __global__ __launch_bounds__(GEN_THREADS) void attn_bwd_generic_kernel(AttnParams p) {
   extern __shared__ __attribute__((aligned(16))) float gsm[];
-  const long long wid = blockIdx.x;
-  const int head = (int)((unsigned int)wid % (unsigned int)p.heads);
-  const AttnRows g = attn_rows(p, (unsigned int)wid / (unsigned int)p.heads);
-  const int L = p.L, S = p.S;
-  const int Tq = p.mode == 1 ? p.Tq : 0, Tk = p.mode == 1 ? p.Tk : 0;
-  const unsigned long long seed = (p.seed && p.drop_thresh) ? *p.seed : 0ull;
+  const unsigned int wid = blockIdx.x;
+  const AttnWave aw = attn_wave(p, wid);
+  const AttnRows& g = aw.g; const int head = aw.head, L = aw.L, S = aw.S, Tq = aw.Tq, Tk = aw.Tk;
   float* Qs = gsm; float* Gs = Qs + L * HD; float* Ks = Gs + L * HD; float* Vs = Ks + S * HD; float* st = Vs + S * HD;   // st [L][3]
   gen_stage(Qs, p.q, p.ld_q, p, g, L, Tq, head);
   gen_stage(Gs, p.go, p.ld_o, p, g, L, Tq, head);
@@ -648,31 +630,27 @@ __global__ __launch_bounds__(GEN_THREADS) void attn_bwd_generic_kernel(AttnParam
   __syncthreads();
   float am_q = 0.f, am_k = 0.f, am_v = 0.f;
   const unsigned int pk_q = amax_peek_wave(p.dq_amax), pk_k = amax_peek_wave(p.dk_amax), pk_v = amax_peek_wave(p.dv_amax);
-  auto dead = [&](int q, int j) { return p.mask_mode == 1 && j == S - 1 && q < L - 1; };
-  auto mask = [&](int q, int j) {
-    return p.drop_thresh ? drop_scale(seed, p.salt, ((unsigned long long)wid * L + q) * S + j, p.drop_thresh, p.drop_inv_keep) : 1.f;
-  };
   // phase A: one thread per query row - softmax statistics, delta = sum_j P dP, dQ = scale * sum_j dS K
   for (int q = threadIdx.x; q < L; q += GEN_THREADS) {
     const float* qr = Qs + q * HD; const float* gr = Gs + q * HD;
     float mx = -INFINITY;
-    for (int j = 0; j < S; ++j) if (!dead(q, j)) mx = fmaxf(mx, gen_dot(qr, Ks + j * HD) * p.scale);
+    for (int j = 0; j < S; ++j) if (!attn_dead(p.mask_mode, L, S, q, j)) mx = fmaxf(mx, gen_dot(qr, Ks + j * HD) * p.scale);
     float sum = 0.f;
-    for (int j = 0; j < S; ++j) if (!dead(q, j)) sum += __expf(gen_dot(qr, Ks + j * HD) * p.scale - mx);
+    for (int j = 0; j < S; ++j) if (!attn_dead(p.mask_mode, L, S, q, j)) sum += __expf(gen_dot(qr, Ks + j * HD) * p.scale - mx);
     const float inv = 1.f / sum;
     float delta = 0.f;
     for (int j = 0; j < S; ++j) {
-      if (dead(q, j)) continue;
+      if (attn_dead(p.mask_mode, L, S, q, j)) continue;
       const float pj = __expf(gen_dot(qr, Ks + j * HD) * p.scale - mx) * inv;
-      delta += pj * gen_dot(gr, Vs + j * HD) * mask(q, j);
+      delta += pj * gen_dot(gr, Vs + j * HD) * (p.drop_thresh ? attn_keep(p, aw.seed, wid, L, S, q, j) : 1.f);
     }
     float dq[HD];
 #pragma unroll
     for (int d = 0; d < HD; ++d) dq[d] = 0.f;
     for (int j = 0; j < S; ++j) {
-      if (dead(q, j)) continue;
+      if (attn_dead(p.mask_mode, L, S, q, j)) continue;
       const float pj = __expf(gen_dot(qr, Ks + j * HD) * p.scale - mx) * inv;
-      const float ds = pj * (gen_dot(gr, Vs + j * HD) * mask(q, j) - delta) * p.scale;
+      const float ds = pj * (gen_dot(gr, Vs + j * HD) * (p.drop_thresh ? attn_keep(p, aw.seed, wid, L, S, q, j) : 1.f) - delta) * p.scale;
 #pragma unroll
       for (int d = 0; d < HD; ++d) dq[d] += ds * Ks[j * HD + d];
     }
@@ -680,8 +658,9 @@ __global__ __launch_bounds__(GEN_THREADS) void attn_bwd_generic_kernel(AttnParam
     float* dp = p.dq + attn_row(g, q, Tq) * p.ld_dq + head * HD;
 #pragma unroll
     for (int d = 0; d < HD; d += 4) {
-      st4(dp + d, make_float4(dq[d], dq[d + 1], dq[d + 2], dq[d + 3]));
-      am_q = fmaxf(fmaxf(am_q, fmaxf(fabsf(dq[d]), fabsf(dq[d + 1]))), fmaxf(fabsf(dq[d + 2]), fabsf(dq[d + 3])));
+      const float4 t = make_float4(dq[d], dq[d + 1], dq[d + 2], dq[d + 3]);
+      st4(dp + d, t);
+      am_q = amax4(am_q, t);
     }
   }
   __syncthreads();
@@ -692,9 +671,9 @@ __global__ __launch_bounds__(GEN_THREADS) void attn_bwd_generic_kernel(AttnParam
 #pragma unroll
     for (int d = 0; d < HD; ++d) { dk[d] = 0.f; dv[d] = 0.f; }
     for (int q = 0; q < L; ++q) {
-      if (dead(q, j)) continue;
+      if (attn_dead(p.mask_mode, L, S, q, j)) continue;
       const float pj = __expf(gen_dot(Qs + q * HD, kr) * p.scale - st[q * 3]) * st[q * 3 + 1];
-      const float m = mask(q, j);
+      const float m = (p.drop_thresh ? attn_keep(p, aw.seed, wid, L, S, q, j) : 1.f);
       const float ds = pj * (gen_dot(Gs + q * HD, vr) * m - st[q * 3 + 2]) * p.scale, pd = pj * m;
 #pragma unroll
       for (int d = 0; d < HD; ++d) { dv[d] += pd * Gs[q * HD + d]; dk[d] += ds * Qs[q * HD + d]; }
@@ -703,10 +682,11 @@ __global__ __launch_bounds__(GEN_THREADS) void attn_bwd_generic_kernel(AttnParam
     float* vp = p.dv + attn_row(g, j, Tk) * p.ld_dv + head * HD;
 #pragma unroll
     for (int d = 0; d < HD; d += 4) {
-      st4(kp + d, make_float4(dk[d], dk[d + 1], dk[d + 2], dk[d + 3]));
-      st4(vp + d, make_float4(dv[d], dv[d + 1], dv[d + 2], dv[d + 3]));
-      am_k = fmaxf(fmaxf(am_k, fmaxf(fabsf(dk[d]), fabsf(dk[d + 1]))), fmaxf(fabsf(dk[d + 2]), fabsf(dk[d + 3])));
-      am_v = fmaxf(fmaxf(am_v, fmaxf(fabsf(dv[d]), fabsf(dv[d + 1]))), fmaxf(fabsf(dv[d + 2]), fabsf(dv[d + 3])));
+      const float4 tk = make_float4(dk[d], dk[d + 1], dk[d + 2], dk[d + 3]), tv = make_float4(dv[d], dv[d + 1], dv[d + 2], dv[d + 3]);
+      st4(kp + d, tk);
+      st4(vp + d, tv);
+      am_k = amax4(am_k, tk);
+      am_v = amax4(am_v, tv);
     }
   }
   amax_slot_commit(p.dq_amax, am_q, pk_q);
@@ -765,20 +745,14 @@ __device__ __forceinline__ void long_scale_rows(f32x4_t (&acc)[4], float f, int 
     for (int b = 0; b < 4; ++b) acc[b][i] *= fi;
   }
 }
-__device__ __forceinline__ bool long_dead(const AttnParams& p, int q, int j) {
-  return j >= p.S || (p.mask_mode == 1 && j == p.S - 1 && q < p.L - 1);
-}
 
 __global__ __launch_bounds__(LONG_THREADS) void attn_long_fwd_kernel(AttnParams p, unsigned int ntile) {
   __shared__ __attribute__((aligned(16))) float Ks[LONG_T * LDT], Vs[LONG_T * LDT];
   __shared__ float red[4];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, n = lane & 15, c = lane >> 4;
   const unsigned int wid = blockIdx.x / ntile, qblk = 4 * (blockIdx.x - wid * ntile) + w;
-  const int head = (int)(wid % (unsigned int)p.heads);
-  const AttnRows g = attn_rows(p, wid / (unsigned int)p.heads);
-  const int L = p.L, S = p.S;
-  const int Tq = p.mode == 1 ? p.Tq : 0, Tk = p.mode == 1 ? p.Tk : 0;
-  const unsigned long long seed = (p.seed && p.drop_thresh) ? *p.seed : 0ull;
+  const AttnWave aw = attn_wave(p, wid);
+  const AttnRows& g = aw.g; const int head = aw.head, L = aw.L, S = aw.S, Tq = aw.Tq, Tk = aw.Tk;
   const unsigned int pk_o = amax_peek_block(p.o_amax);
   LongStage st;
   long_stage_load(st, p.k, p.ld_k, p.v, p.ld_v, g, S, Tk, head, 0);
@@ -805,7 +779,7 @@ __global__ __launch_bounds__(LONG_THREADS) void attn_long_fwd_kernel(AttnParams 
       float s[4], bm = -INFINITY;
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
-        s[i] = long_dead(p, q, k0 + 16 * kb + 4 * c + i) ? -INFINITY : sa[i] * p.scale;
+        s[i] = attn_dead(p.mask_mode, L, S, q, k0 + 16 * kb + 4 * c + i) ? -INFINITY : sa[i] * p.scale;
         bm = fmaxf(bm, s[i]);
       }
       const float mn = fmaxf(mx, quad_max(bm));
@@ -817,7 +791,7 @@ __global__ __launch_bounds__(LONG_THREADS) void attn_long_fwd_kernel(AttnParams 
         float pr = s[i] == -INFINITY ? 0.f : __expf(s[i] - mn);
         bs += pr;
         if (p.drop_thresh && j < S)
-          pr *= drop_scale(seed, p.salt, ((unsigned long long)wid * L + qn) * S + j, p.drop_thresh, p.drop_inv_keep);
+          pr *= attn_keep(p, aw.seed, wid, L, S, qn, j);
         s[i] = pr;
       }
       sum = sum * al + quad_sum(bs);
@@ -839,11 +813,8 @@ __global__ __launch_bounds__(LONG_THREADS) void attn_long_bwd_q_kernel(AttnParam
   __shared__ float red[4];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, n = lane & 15, c = lane >> 4;
   const unsigned int wid = blockIdx.x / ntile, qblk = 4 * (blockIdx.x - wid * ntile) + w;
-  const int head = (int)(wid % (unsigned int)p.heads);
-  const AttnRows g = attn_rows(p, wid / (unsigned int)p.heads);
-  const int L = p.L, S = p.S;
-  const int Tq = p.mode == 1 ? p.Tq : 0, Tk = p.mode == 1 ? p.Tk : 0;
-  const unsigned long long seed = (p.seed && p.drop_thresh) ? *p.seed : 0ull;
+  const AttnWave aw = attn_wave(p, wid);
+  const AttnRows& g = aw.g; const int head = aw.head, L = aw.L, S = aw.S, Tq = aw.Tq, Tk = aw.Tk;
   const unsigned int pk_q = amax_peek_block(p.dq_amax);
   LongStage st;
   long_stage_load(st, p.k, p.ld_k, p.v, p.ld_v, g, S, Tk, head, 0);
@@ -875,10 +846,10 @@ __global__ __launch_bounds__(LONG_THREADS) void attn_long_bwd_q_kernel(AttnParam
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
           const int j = k0 + 16 * kb + 4 * c + i;
-          s[i] = long_dead(p, q, j) ? -INFINITY : sa[i] * p.scale;
+          s[i] = attn_dead(p.mask_mode, L, S, q, j) ? -INFINITY : sa[i] * p.scale;
           dp[i] = da[i];
           if (p.drop_thresh && j < S)
-            dp[i] *= drop_scale(seed, p.salt, ((unsigned long long)wid * L + qn) * S + j, p.drop_thresh, p.drop_inv_keep);
+            dp[i] *= attn_keep(p, aw.seed, wid, L, S, qn, j);
         }
         if (pass == 0) {
           const float mn = fmaxf(mx, quad_max(fmaxf(fmaxf(s[0], s[1]), fmaxf(s[2], s[3]))));
@@ -920,11 +891,8 @@ __global__ __launch_bounds__(LONG_THREADS) void attn_long_bwd_kv_kernel(AttnPara
   __shared__ float Ss[3 * LONG_T], red[8];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, n = lane & 15, c = lane >> 4;
   const unsigned int wid = blockIdx.x / ntile, kblk = 4 * (blockIdx.x - wid * ntile) + w;
-  const int head = (int)(wid % (unsigned int)p.heads);
-  const AttnRows g = attn_rows(p, wid / (unsigned int)p.heads);
-  const int L = p.L, S = p.S;
-  const int Tq = p.mode == 1 ? p.Tq : 0, Tk = p.mode == 1 ? p.Tk : 0;
-  const unsigned long long seed = (p.seed && p.drop_thresh) ? *p.seed : 0ull;
+  const AttnWave aw = attn_wave(p, wid);
+  const AttnRows& g = aw.g; const int head = aw.head, L = aw.L, S = aw.S, Tq = aw.Tq, Tk = aw.Tk;
   const unsigned int pk_k = amax_peek_block(p.dk_amax), pk_v = amax_peek_block(p.dv_amax);
   // threads 0 .. 191 also carry the statistics of the query tile: thread 64 a + r the a-th statistic of its row r
   const float* sp = stat + (threadIdx.x >> 6) * nstat + (long long)wid * L;
@@ -961,10 +929,10 @@ __global__ __launch_bounds__(LONG_THREADS) void attn_long_bwd_kv_kernel(AttnPara
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         const int ql = 16 * qb + 4 * c + i, q = q0 + ql;
-        const float pr = (q >= L || long_dead(p, q, key)) ? 0.f : __expf(sb[i] * p.scale - Ss[ql]) * Ss[LONG_T + ql];
+        const float pr = (q >= L || attn_dead(p.mask_mode, L, S, q, key)) ? 0.f : __expf(sb[i] * p.scale - Ss[ql]) * Ss[LONG_T + ql];
         float m = 1.f;
         if (p.drop_thresh && q < L && key < S)
-          m = drop_scale(seed, p.salt, ((unsigned long long)wid * L + q) * S + key, p.drop_thresh, p.drop_inv_keep);
+          m = attn_keep(p, aw.seed, wid, L, S, q, key);
         pd[i] = pr * m;
         ds[i] = pr * (db[i] * m - Ss[2 * LONG_T + ql]) * p.scale;
       }
@@ -983,15 +951,24 @@ __global__ __launch_bounds__(LONG_THREADS) void attn_long_bwd_kv_kernel(AttnPara
   amax_slot_commit_block(p.dv_amax, am_v, red + 4, pk_v);
 }
 
-static int attn_setup(AttnParams& p, int mode, int heads, int head_dim, int frames_or_N, int P, int W, int ws, int Tq,
-                      int Tk, int mask_mode, float drop_p, const unsigned long long* seed, unsigned int salt, bool bwd,
-                      bool any_length = false) {
-  if (head_dim != HD) { npvp_set_error("attn: head_dim must be 64"); return NPVP_ERR_ARG; }
-  if (drop_p < 0.f || drop_p >= 1.f || (drop_p > 0.f && !seed)) { npvp_set_error("attn: bad dropout arguments"); return NPVP_ERR_ARG; }
+// =====================================================================================================
+// Host side.  The error of an entry point reads "<who>: <what>"; who is the prefix its messages have always had.
+static int attn_fail(const char* who, const char* what, int rc = NPVP_ERR_ARG) {
+  char msg[256];
+  snprintf(msg, sizeof(msg), "%s: %s", who, what);
+  npvp_set_error(msg);
+  return rc;
+}
+
+// geometry, limits and dropout of one call -> p (everything but operands, strides and amax slots: attn_bind_*)
+static int attn_setup(AttnParams& p, const char* who, int mode, int heads, int head_dim, int frames_or_N, int P, int W, int ws, int Tq,
+                      int Tk, int mask_mode, float drop_p, const unsigned long long* seed, unsigned int salt, bool any_length = false) {
+  if (head_dim != HD) return attn_fail(who, "head_dim must be 64");
+  if (drop_p < 0.f || drop_p >= 1.f || (drop_p > 0.f && !seed)) return attn_fail(who, "bad dropout arguments");
   p.mode = mode; p.heads = heads; p.P = P; p.W = W; p.ws = ws; p.Tq = Tq; p.Tk = Tk; p.mask_mode = mask_mode;
   long long groups;
   if (mode == 0) {
-    if (ws <= 0 || W % ws != 0 || P % W != 0 || (P / W) % ws != 0) { npvp_set_error("attn: window must tile the grid"); return NPVP_ERR_ARG; }
+    if (ws <= 0 || W % ws != 0 || P % W != 0 || (P / W) % ws != 0) return attn_fail(who, "window must tile the grid");
     p.nww = W / ws; p.nwin = p.nww * ((P / W) / ws); p.L = p.S = ws * ws;
     groups = (long long)frames_or_N * p.nwin;
   } else {
@@ -999,9 +976,9 @@ static int attn_setup(AttnParams& p, int mode, int heads, int head_dim, int fram
     groups = (long long)frames_or_N * P;
   }
   if (any_length) {        // the streaming kernels (npvp_attn_long_*)
-    if (p.L < 1 || p.S < 1) { npvp_set_error("attn_long: sequence length must be at least 1"); return NPVP_ERR_ARG; }
-    if (mode == 0 && ws > 1024) { npvp_set_error("attn_long: window size must be at most 1024 (attn_row)"); return NPVP_ERR_ARG; }
-  } else if (p.L < 1 || p.S < 1 || p.L > GEN_MAX || p.S > GEN_MAX) { npvp_set_error("attn: sequence length must be in [1,128]"); return NPVP_ERR_ARG; }
+    if (p.L < 1 || p.S < 1) return attn_fail("attn_long", "sequence length must be at least 1");
+    if (mode == 0 && ws > 1024) return attn_fail("attn_long", "window size must be at most 1024 (attn_row)");
+  } else if (p.L < 1 || p.S < 1 || p.L > GEN_MAX || p.S > GEN_MAX) return attn_fail(who, "sequence length must be in [1,128]");
   p.scale = 0.125f;   // 1/sqrt(64)
   p.drop_thresh = drop_p > 0.f ? drop_threshold(drop_p) : 0u;
   p.drop_inv_keep = drop_p > 0.f ? 1.f / (1.f - drop_p) : 1.f;
@@ -1009,8 +986,24 @@ static int attn_setup(AttnParams& p, int mode, int heads, int head_dim, int fram
   p.total = groups * heads;
   // the kernels resolve (group, head) and token rows in 32-bit arithmetic (AttnRows)
   const long long rows = mode == 0 ? (long long)frames_or_N * P : (long long)frames_or_N * P * (Tq > Tk ? Tq : Tk);
-  if (p.total >= (1ll << 31) || rows >= (1ll << 31)) { npvp_set_error("attn: too many token rows / (group, head) pairs for one launch"); return NPVP_ERR_ARG; }
-  (void)bwd;
+  if (p.total >= (1ll << 31) || rows >= (1ll << 31)) return attn_fail(who, "too many token rows / (group, head) pairs for one launch");
+  return NPVP_OK;
+}
+
+// the operands of a forward / a backward call -> p
+static int attn_bind_fwd(AttnParams& p, const char* who, const float* q, long long ld_q, const float* k, long long ld_k, const float* v,
+                         long long ld_v, float* o, long long ld_o, float* o_amax) {
+  if (ld_q % 4 || ld_k % 4 || ld_v % 4 || ld_o % 4) return attn_fail(who, "row strides must be multiples of 4");
+  p.q = q; p.k = k; p.v = v; p.o = o; p.ld_q = ld_q; p.ld_k = ld_k; p.ld_v = ld_v; p.ld_o = ld_o; p.o_amax = o_amax;
+  return NPVP_OK;
+}
+static int attn_bind_bwd(AttnParams& p, const char* who, const float* q, long long ld_q, const float* k, long long ld_k, const float* v,
+                         long long ld_v, const float* go, long long ld_o, float* dq, long long ld_dq, float* dk, long long ld_dk, float* dv,
+                         long long ld_dv, float* dq_amax, float* dk_amax, float* dv_amax) {
+  if (ld_q % 4 || ld_k % 4 || ld_v % 4 || ld_o % 4 || ld_dq % 4 || ld_dk % 4 || ld_dv % 4) return attn_fail(who, "row strides must be multiples of 4");
+  p.q = q; p.k = k; p.v = v; p.go = go; p.dq = dq; p.dk = dk; p.dv = dv;
+  p.ld_q = ld_q; p.ld_k = ld_k; p.ld_v = ld_v; p.ld_o = ld_o; p.ld_dq = ld_dq; p.ld_dk = ld_dk; p.ld_dv = ld_dv;
+  p.dq_amax = dq_amax; p.dk_amax = dk_amax; p.dv_amax = dv_amax;
   return NPVP_OK;
 }
 
@@ -1024,19 +1017,15 @@ extern "C" int npvp_attn_fwd(const float* q, long long ld_q, const float* k, lon
                              int head_dim, int mask_mode, float drop_p, const unsigned long long* seed, unsigned int salt,
                              float* o_amax, hipStream_t stream) {
   AttnParams p = {};
-  const int rc = attn_setup(p, mode, heads, head_dim, dim0, P, W, ws, Tq, Tk, mask_mode, drop_p, seed, salt, false);
-  if (rc) return rc;
-  p.o_amax = o_amax;
+  if (const int rc = attn_setup(p, "attn", mode, heads, head_dim, dim0, P, W, ws, Tq, Tk, mask_mode, drop_p, seed, salt)) return rc;
   NPVP_CHECK_ARG(dim0 > 0, "attn: empty batch");
-  NPVP_CHECK_ARG(ld_q % 4 == 0 && ld_k % 4 == 0 && ld_v % 4 == 0 && ld_o % 4 == 0, "attn: row strides must be multiples of 4");
-  p.q = q; p.k = k; p.v = v; p.o = o; p.ld_q = ld_q; p.ld_k = ld_k; p.ld_v = ld_v; p.ld_o = ld_o;
+  if (const int rc = attn_bind_fwd(p, "attn", q, ld_q, k, ld_k, v, ld_v, o, ld_o, o_amax)) return rc;
   const dim3 mg((unsigned)((p.total + 3) / 4)), mb(256);
   const int nq = (p.L + 15) / 16, nk = (p.S + 15) / 16;
   if (nq > 2 || nk > 2) {                  // 33 .. 128: the generic kernels (K, V of one head in LDS)
     const size_t lds = (size_t)2 * p.S * HD * sizeof(float);
-    if (lds > 64 * 1024 && hipFuncSetAttribute((const void*)attn_fwd_generic_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-      npvp_set_error("attn: could not reserve LDS for the generic kernel"); return NPVP_ERR_LAUNCH;
-    }
+    if (lds > 64 * 1024 && hipFuncSetAttribute((const void*)attn_fwd_generic_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+      return attn_fail("attn", "could not reserve LDS for the generic kernel", NPVP_ERR_LAUNCH);
     NPVP_LAUNCH(attn_fwd_generic_kernel, dim3((unsigned)p.total), dim3(GEN_THREADS), lds, stream, p);
     NPVP_CHECK_LAUNCH();
     return NPVP_OK;
@@ -1049,17 +1038,16 @@ extern "C" int npvp_attn_fwd(const float* q, long long ld_q, const float* k, lon
   return NPVP_OK;
 }
 
-// S query sets per clip on one clip's K / V (see include/npvp_hip.h and attn_samples_fwd_mfma_kernel).
+// S query sets per clip on one clip's K / V (see include/npvp_hip.h and attn_samples_fwd_mfma_kernel): attn_setup's temporal
+// geometry on the N clips of the memory, without mask and dropout, plus what is this entry point's own.
 extern "C" int npvp_attn_samples_fwd(const float* q, long long ld_q, const float* k, long long ld_k, const float* v, long long ld_v,
                                      float* o, long long ld_o, int S, int N, int P, int Tq, int Tk, int heads, int head_dim,
                                      int sample_chunk, float* o_amax, hipStream_t stream) {
-  NPVP_CHECK_ARG(head_dim == HD, "attn_samples: head_dim must be 64");
   NPVP_CHECK_ARG(S > 0 && N > 0 && P > 0 && heads > 0, "attn_samples: empty batch");
   NPVP_CHECK_ARG(Tq >= 1 && Tk >= 1 && Tq <= 32 && Tk <= 32,
                  "attn_samples: sequence length must be in [1,32] (longer: npvp_attn_fwd / npvp_attn_long_fwd per sample)");
   NPVP_CHECK_ARG(sample_chunk >= 0, "attn_samples: sample_chunk must be 0 (the library chooses) or positive");
   NPVP_CHECK_ARG(q && k && v && o, "attn_samples: null operand");
-  NPVP_CHECK_ARG(ld_q % 4 == 0 && ld_k % 4 == 0 && ld_v % 4 == 0 && ld_o % 4 == 0, "attn_samples: row strides must be multiples of 4");
   const long long base = (long long)N * P * heads;          // waves at one chunk: (clip, pixel, head)
   // Samples per wave.  A larger chunk amortises a wave's K / V tile loads over more query sets, but those run one after the other
   // in the wave, and this kernel is bound by the latency of its loads, which only other resident waves hide: the chip has
@@ -1076,15 +1064,13 @@ extern "C" int npvp_attn_samples_fwd(const float* q, long long ld_q, const float
   if (chunk > S) chunk = S;
   const long long nchunk = (S + chunk - 1) / chunk;
   AttnParams p = {};
-  p.mode = 1; p.heads = heads; p.P = P; p.Tq = Tq; p.Tk = Tk; p.L = Tq; p.S = Tk; p.nww = p.nwin = 1;
-  p.scale = 0.125f;   // 1/sqrt(64)
+  if (const int rc = attn_bind_fwd(p, "attn_samples", q, ld_q, k, ld_k, v, ld_v, o, ld_o, o_amax)) return rc;
+  // (group, head) and token rows are resolved in 32-bit arithmetic (AttnRows); the query side has S * N clips, and there is a
+  // wave per chunk: this bound contains attn_setup's for the N clips
+  if (base * nchunk >= (1ll << 31) || (long long)S * N * P * Tq >= (1ll << 31) || (long long)N * P * Tk >= (1ll << 31))
+    return attn_fail("attn_samples", "too many token rows / (group, head, chunk) waves for one launch");
+  if (const int rc = attn_setup(p, "attn_samples", 1, heads, head_dim, N, P, 0, 0, Tq, Tk, 0, 0.f, nullptr, 0)) return rc;
   p.total = base * nchunk;
-  // (group, head) and token rows are resolved in 32-bit arithmetic (AttnRows); the query side has S * N clips
-  const long long rows_q = (long long)S * N * P * Tq, rows_k = (long long)N * P * Tk;
-  if (p.total >= (1ll << 31) || rows_q >= (1ll << 31) || rows_k >= (1ll << 31)) {
-    npvp_set_error("attn_samples: too many token rows / (group, head, chunk) waves for one launch"); return NPVP_ERR_ARG;
-  }
-  p.q = q; p.k = k; p.v = v; p.o = o; p.ld_q = ld_q; p.ld_k = ld_k; p.ld_v = ld_v; p.ld_o = ld_o; p.o_amax = o_amax;
   const dim3 mg((unsigned)((p.total + 3) / 4)), mb(256);
   const int nq = (Tq + 15) / 16, nk = (Tk + 15) / 16, ck = (int)chunk;
   if (nq == 1 && nk == 1) NPVP_LAUNCH((attn_samples_fwd_mfma_kernel<1, 1>), mg, mb, 0, stream, p, S, N, ck);
@@ -1101,22 +1087,17 @@ extern "C" int npvp_attn_bwd(const float* q, long long ld_q, const float* k, lon
                              int heads, int head_dim, int mask_mode, float drop_p, const unsigned long long* seed,
                              unsigned int salt, float* dq_amax, float* dk_amax, float* dv_amax, hipStream_t stream) {
   AttnParams p = {};
-  const int rc = attn_setup(p, mode, heads, head_dim, dim0, P, W, ws, Tq, Tk, mask_mode, drop_p, seed, salt, true);
-  if (rc) return rc;
-  p.dq_amax = dq_amax; p.dk_amax = dk_amax; p.dv_amax = dv_amax;
+  if (const int rc = attn_setup(p, "attn", mode, heads, head_dim, dim0, P, W, ws, Tq, Tk, mask_mode, drop_p, seed, salt)) return rc;
   NPVP_CHECK_ARG(dim0 > 0, "attn_bwd: empty batch");
-  NPVP_CHECK_ARG(ld_q % 4 == 0 && ld_k % 4 == 0 && ld_v % 4 == 0 && ld_o % 4 == 0 && ld_dq % 4 == 0 && ld_dk % 4 == 0 &&
-                     ld_dv % 4 == 0, "attn_bwd: row strides must be multiples of 4");
-  p.q = q; p.k = k; p.v = v; p.go = go; p.dq = dq; p.dk = dk; p.dv = dv;
-  p.ld_q = ld_q; p.ld_k = ld_k; p.ld_v = ld_v; p.ld_o = ld_o; p.ld_dq = ld_dq; p.ld_dk = ld_dk; p.ld_dv = ld_dv;
+  if (const int rc = attn_bind_bwd(p, "attn_bwd", q, ld_q, k, ld_k, v, ld_v, go, ld_o, dq, ld_dq, dk, ld_dk, dv, ld_dv, dq_amax, dk_amax, dv_amax))
+    return rc;
   const size_t staged1_lds = (size_t)(2 * p.L + p.S) * LDT * sizeof(float) + 2 * 16 * LDX * sizeof(float);
   const dim3 mg((unsigned)((p.total + 3) / 4)), mb(256);
   const int nq = (p.L + 15) / 16, nk = (p.S + 15) / 16;
   if (nq > 2 || nk > 2) {                  // 33 .. 128: the generic kernels (Q, dO, K, V of one head + the row statistics in LDS)
     const size_t lds = ((size_t)2 * (p.L + p.S) * HD + 3 * (size_t)p.L) * sizeof(float);
-    if (lds > 64 * 1024 && hipFuncSetAttribute((const void*)attn_bwd_generic_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-      npvp_set_error("attn_bwd: could not reserve LDS for the generic kernel"); return NPVP_ERR_LAUNCH;
-    }
+    if (lds > 64 * 1024 && hipFuncSetAttribute((const void*)attn_bwd_generic_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+      return attn_fail("attn_bwd", "could not reserve LDS for the generic kernel", NPVP_ERR_LAUNCH);
     NPVP_LAUNCH(attn_bwd_generic_kernel, dim3((unsigned)p.total), dim3(GEN_THREADS), lds, stream, p);
     NPVP_CHECK_LAUNCH();
     return NPVP_OK;
@@ -1136,7 +1117,7 @@ extern "C" int npvp_attn_bwd(const float* q, long long ld_q, const float* k, lon
 static int attn_long_grid(const AttnParams& p, int rows_n, unsigned int& ntile, unsigned int& blocks) {
   ntile = (unsigned int)((rows_n + LONG_T - 1) / LONG_T);
   const long long nb = p.total * (long long)ntile;
-  if (nb >= (1ll << 31)) { npvp_set_error("attn_long: too many (group, head, tile) workgroups for one launch"); return NPVP_ERR_ARG; }
+  if (nb >= (1ll << 31)) return attn_fail("attn_long", "too many (group, head, tile) workgroups for one launch");
   blocks = (unsigned int)nb;
   return NPVP_OK;
 }
@@ -1146,12 +1127,9 @@ extern "C" int npvp_attn_long_fwd(const float* q, long long ld_q, const float* k
                                   int head_dim, int mask_mode, float drop_p, const unsigned long long* seed, unsigned int salt,
                                   float* o_amax, hipStream_t stream) {
   AttnParams p = {};
-  const int rc = attn_setup(p, mode, heads, head_dim, dim0, P, W, ws, Tq, Tk, mask_mode, drop_p, seed, salt, false, true);
-  if (rc) return rc;
-  p.o_amax = o_amax;
+  if (const int rc = attn_setup(p, "attn", mode, heads, head_dim, dim0, P, W, ws, Tq, Tk, mask_mode, drop_p, seed, salt, true)) return rc;
   NPVP_CHECK_ARG(dim0 > 0, "attn_long: empty batch");
-  NPVP_CHECK_ARG(ld_q % 4 == 0 && ld_k % 4 == 0 && ld_v % 4 == 0 && ld_o % 4 == 0, "attn_long: row strides must be multiples of 4");
-  p.q = q; p.k = k; p.v = v; p.o = o; p.ld_q = ld_q; p.ld_k = ld_k; p.ld_v = ld_v; p.ld_o = ld_o;
+  if (const int rc = attn_bind_fwd(p, "attn_long", q, ld_q, k, ld_k, v, ld_v, o, ld_o, o_amax)) return rc;
   unsigned int ntile, blocks;
   if (attn_long_grid(p, p.L, ntile, blocks)) return NPVP_ERR_ARG;
   NPVP_LAUNCH(attn_long_fwd_kernel, dim3(blocks), dim3(LONG_THREADS), 0, stream, p, ntile);
@@ -1175,18 +1153,14 @@ extern "C" int npvp_attn_long_bwd(const float* q, long long ld_q, const float* k
                                   unsigned int salt, float* dq_amax, float* dk_amax, float* dv_amax, void* workspace,
                                   long long ws_bytes, hipStream_t stream) {
   AttnParams p = {};
-  const int rc = attn_setup(p, mode, heads, head_dim, dim0, P, W, ws, Tq, Tk, mask_mode, drop_p, seed, salt, true, true);
-  if (rc) return rc;
-  p.dq_amax = dq_amax; p.dk_amax = dk_amax; p.dv_amax = dv_amax;
+  if (const int rc = attn_setup(p, "attn", mode, heads, head_dim, dim0, P, W, ws, Tq, Tk, mask_mode, drop_p, seed, salt, true)) return rc;
   NPVP_CHECK_ARG(dim0 > 0, "attn_long_bwd: empty batch");
-  NPVP_CHECK_ARG(ld_q % 4 == 0 && ld_k % 4 == 0 && ld_v % 4 == 0 && ld_o % 4 == 0 && ld_dq % 4 == 0 && ld_dk % 4 == 0 &&
-                     ld_dv % 4 == 0, "attn_long_bwd: row strides must be multiples of 4");
+  if (const int rc = attn_bind_bwd(p, "attn_long_bwd", q, ld_q, k, ld_k, v, ld_v, go, ld_o, dq, ld_dq, dk, ld_dk, dv, ld_dv, dq_amax, dk_amax,
+                                   dv_amax))
+    return rc;
   const long long nstat = p.total * p.L;
-  if (!workspace || ws_bytes < 3 * nstat * (long long)sizeof(float)) {
-    npvp_set_error("attn_long_bwd: workspace too small (npvp_attn_long_bwd_workspace_bytes)"); return NPVP_ERR_WORKSPACE;
-  }
-  p.q = q; p.k = k; p.v = v; p.go = go; p.dq = dq; p.dk = dk; p.dv = dv;
-  p.ld_q = ld_q; p.ld_k = ld_k; p.ld_v = ld_v; p.ld_o = ld_o; p.ld_dq = ld_dq; p.ld_dk = ld_dk; p.ld_dv = ld_dv;
+  if (!workspace || ws_bytes < 3 * nstat * (long long)sizeof(float))
+    return attn_fail("attn_long_bwd", "workspace too small (npvp_attn_long_bwd_workspace_bytes)", NPVP_ERR_WORKSPACE);
   unsigned int qtile, qblocks, ktile, kblocks;
   if (attn_long_grid(p, p.L, qtile, qblocks) || attn_long_grid(p, p.S, ktile, kblocks)) return NPVP_ERR_ARG;
   float* stat = static_cast<float*>(workspace);

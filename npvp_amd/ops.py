@@ -1217,8 +1217,18 @@ def _attn_len(cfg):
     return (cfg.ws * cfg.ws, cfg.ws * cfg.ws) if cfg.mode == 0 else (cfg.Tq, cfg.Tk)
 
 
+def _attn_groups(cfg):
+    """attention groups: (frame, window) pairs or (sample, pixel) pairs (attn_setup of csrc/attn.hip)"""
+    return cfg.dim0 * (cfg.P // (cfg.ws * cfg.ws)) if cfg.mode == 0 else cfg.dim0 * cfg.P
+
+
 def _attn_long(cfg):
     return max(_attn_len(cfg)) >= ATTN_LONG_MIN
+
+
+def _attn_fwd_entry(cfg):
+    """(function, its name) of the forward entry point that takes cfg's sequence lengths"""
+    return (lib().npvp_attn_long_fwd, "npvp_attn_long_fwd") if _attn_long(cfg) else (lib().npvp_attn_fwd, "npvp_attn_fwd")
 
 
 def _attn_fwd(q, k, v, o, cfg):
@@ -1226,10 +1236,9 @@ def _attn_fwd(q, k, v, o, cfg):
     seed = _S._cur.rng.seed_tensor(q.device) if cfg.drop.on else None
     if DropRecorder.sites is not None and cfg.drop.on:      # weights tensor [groups, heads, L, S]
         L_, S_ = _attn_len(cfg)
-        groups = cfg.dim0 * (cfg.P // (cfg.ws * cfg.ws)) if cfg.mode == 0 else cfg.dim0 * cfg.P
-        DropRecorder.note(cfg.drop, "elem", groups * cfg.heads * L_ * S_)
+        DropRecorder.note(cfg.drop, "elem", _attn_groups(cfg) * cfg.heads * L_ * S_)
     slot = _new_slot(q.device)
-    fn, what = (lib().npvp_attn_long_fwd, "npvp_attn_long_fwd") if _attn_long(cfg) else (lib().npvp_attn_fwd, "npvp_attn_fwd")
+    fn, what = _attn_fwd_entry(cfg)
     check(fn(_ptr(q), q.stride(0), _ptr(k), k.stride(0), _ptr(v), v.stride(0), _ptr(o), o.stride(0),
              cfg.mode, cfg.dim0, cfg.P, cfg.W, cfg.ws, cfg.Tq, cfg.Tk, cfg.heads, hd, cfg.mask_mode,
              cfg.drop.p, _ptr(seed), cfg.drop.salt, _ptr(slot), _stream()), what)
@@ -1254,7 +1263,7 @@ def _attn_samples_fwd(q, k, v, o, cfg, S, sample_chunk=0):
                                           S, cfg.dim0, cfg.P, cfg.Tq, cfg.Tk, cfg.heads, hd, sample_chunk, _ptr(slot), _stream()),
               "npvp_attn_samples_fwd")
     else:
-        fn, what = (lib().npvp_attn_long_fwd, "npvp_attn_long_fwd") if _attn_long(cfg) else (lib().npvp_attn_fwd, "npvp_attn_fwd")
+        fn, what = _attn_fwd_entry(cfg)
         rows = cfg.dim0 * cfg.Tq * cfg.P          # query rows of one sample
         for s in range(S):
             check(fn(q.data_ptr() + 4 * s * rows * q.stride(0), q.stride(0), _ptr(k), k.stride(0), _ptr(v), v.stride(0),

@@ -192,9 +192,12 @@ def test_short_sequences_through_the_streaming_kernels(K, Tq, Tk, mask):
         K.ATTN_LONG_MIN = old
 
 
-def test_dropout_mask_is_the_one_of_the_existing_route(K):
-    T, p = 40, 0.1
-    (q, k, v, cot), _ = temporal_ref(T, T, 0)
+@pytest.mark.parametrize("Tq,Tk,mask", [(40, 40, 0), (10, 10, 1), (18, 18, 1), (28, 2, 0), (40, 40, 1)])
+def test_dropout_mask_is_the_one_of_the_existing_route(K, Tq, Tk, mask):
+    """one dropout key and one mask for every route: the generic kernels (40 rows), the MFMA backward (10), the staged backward
+    <2,2> (18) and <2,1> (28 x 2), each against the streaming kernels under the same seed and salt"""
+    p = 0.1
+    (q, k, v, cot), _ = temporal_ref(Tq, Tk, mask)
     outs = []
     old = K.ATTN_LONG_MIN
     for lo in (old, 1):
@@ -202,7 +205,7 @@ def test_dropout_mask_is_the_one_of_the_existing_route(K):
         ins = [g(q), g(k), g(v)]
         try:
             K.ATTN_LONG_MIN = lo                              # (the route is chosen when a node runs: backward inside the try too)
-            y, masks = record(K, lambda: K.attn(ins[0], ins[1], ins[2], cfg_t(T, T, 0, p)))
+            y, masks = record(K, lambda: K.attn(ins[0], ins[1], ins[2], cfg_t(Tq, Tk, mask, p)))
             grads = torch.autograd.grad((y * cot.to(DEV)).sum(), ins)
         finally:
             K.ATTN_LONG_MIN = old
