@@ -116,7 +116,8 @@ int npvp_gemm_f32(int a_kc, int b_kc, int M, int N, int K, const float* A, long 
                   const void* b_pre, int accumulate, float* rowstats, const float* a_amax, const float* b_amax,
                   float* c_amax, unsigned int* range_flag, float adrop_p, int adrop_g1, int adrop_g2, unsigned int adrop_salt,
                   void* workspace, long long ws_bytes, npvp_stream_t stream);
-/* npvp_gemm_f32 with a ROW-SKIP spec (a_kc = 1 only): (skip_p, skip_g1, skip_g2, skip_salt) name, like adrop, the row groups
+/* npvp_gemm_f32 with a ROW-SKIP spec (a_kc = 1; a weight gradient, a_kc = b_kc = 0, on the precision-6 kernel id 6 takes the spec
+ * over its K rows as npvp_wgrad_f16_chained_skip does and under its conditions): (skip_p, skip_g1, skip_g2, skip_salt) name, like adrop, the row groups
  * (row / g1) % g2 that a DropPath site drops - rows whose result the caller multiplies by an exact 0 (forward) or whose rows of A
  * are exact zeros (dgrad).  On the precision-6 forward / dgrad kernels (ids 5 / 7) a tile all of whose rows lie in dropped groups
  * is not computed - no operand loads, no K loop, no row-guard pass - and runs its usual epilogue on zero accumulators, so C, the
@@ -185,6 +186,17 @@ int npvp_wgrad_f16_chained(int M, int N, int K, const float* dy, long long lda, 
                            unsigned int* range_flag, float adrop_p, int adrop_g1, int adrop_g2, unsigned int adrop_salt,
                            const unsigned long long* seed, const void* prev_job, void* my_job, void* workspace,
                            long long ws_bytes, npvp_stream_t stream);
+/* the same with a ROW SKIP: skip_* is the row-group spec of a DropPath site (probability, rows per group, groups, salt; the decision
+ * for group g is the site's own, taken on the device from `seed`).  Contract: the rows of dy in dropped groups ARE ZERO; the launch
+ * then leaves their K-steps out - x is not read there (it may hold anything) - and deals the kept K-steps evenly over the splits, so
+ * dw / db are what the launch without the skip gives up to the order of the split-K sum.  Taken when K == skip_g1 * skip_g2 (each
+ * group once), skip_g1 % 16 == 0, skip_g1 >= 256 and skip_g2 <= 64; any other spec runs every K-step, exactly as skip_p = 0 does. */
+int npvp_wgrad_f16_chained_skip(int M, int N, int K, const float* dy, long long lda, const float* x, long long ldb, float* dw,
+                                long long ldc, float* db, int accumulate, const float* a_amax, const float* b_amax,
+                                unsigned int* range_flag, float adrop_p, int adrop_g1, int adrop_g2, unsigned int adrop_salt,
+                                float skip_p, int skip_g1, int skip_g2, unsigned int skip_salt,
+                                const unsigned long long* seed, const void* prev_job, void* my_job, void* workspace,
+                                long long ws_bytes, npvp_stream_t stream);
 int npvp_splitk_reduce_job(const void* job, npvp_stream_t stream);
 /* n job records (64 bytes each, back to back in HOST memory at `jobs`) in ceil(n / 32) launches; two records of one launch must not
  * name the same `out`. */
@@ -207,7 +219,8 @@ int npvp_linear_bwd_f16(int R, int N, int K, const float* dy, long long ldy, con
                         unsigned int* range_flag, float adrop_p, int adrop_g1, int adrop_g2, unsigned int adrop_salt,
                         const unsigned long long* seed, const void* prev_job, void* my_job, void* workspace, long long ws_bytes,
                         npvp_stream_t stream);
-/* the same with the row-skip spec of npvp_gemm_f32_skip on the dgrad's tiles (the weight gradient's K-steps all run) */
+/* the same with the row-skip spec of npvp_gemm_f32_skip on the dgrad's tiles and, where npvp_wgrad_f16_chained_skip takes the spec
+ * (K there = R here), on the weight gradient's K-steps: the rows of dy in dropped groups are zero, x is not read there */
 int npvp_linear_bwd_f16_skip(int R, int N, int K, const float* dy, long long ldy, const float* dy_amax, const void* w_planes_d,
                              const float* w_amax, float* dx, long long ldx, int act, const float* aux_in, const float* residual,
                              long long ldr, float drop_p, int drop_mode, int drop_g1, int drop_g2, unsigned int drop_salt,

@@ -3,6 +3,7 @@
 #pragma once
 #include <type_traits>
 #include "common.h"
+#include "kept_runs.h"
 
 namespace npvp {
 
@@ -31,9 +32,11 @@ struct GemmParams {
   DropSpec drop;
   DropSpec adrop;          // fp16 kernels only: a ROW-GROUP mask (mode 1) on the rows of operand A (dgrad: A = dy [M][K]; weight
                            // gradient: A = dy [K][M]) - the backward of a DropPath site without a masked copy of dy; thresh 0 = off
-  DropSpec rskip;          // fp16 forward / dgrad kernels only: a ROW-GROUP spec (mode 1) of rows whose result the caller multiplies by
+  DropSpec rskip;          // fp16 kernels only: a ROW-GROUP spec (mode 1).  Forward / dgrad: rows whose result the caller multiplies by
                            // 0 (forward) or whose A rows are 0 (dgrad): a tile wholly inside dropped groups runs its epilogue on zero
-                           // accumulators instead of its K loop (gemm_f16_body); every other kernel ignores it; thresh 0 = off
+                           // accumulators instead of its K loop (gemm_f16_body).  Weight gradient (gemm_wgrad_f16_body; wgrad_row_skip_ok
+                           // below): rows of A = dy [K][M] that are 0: the K-steps of dropped groups are left out, B is not read there,
+                           // and the kept K-steps are dealt evenly over the splits.  Every other kernel ignores it; thresh 0 = off
   int tiles_m, tiles_n;
   int splits;              // >1: raw partial tiles go to C + z*M*ldc (workspace)
   float alpha;
@@ -373,6 +376,13 @@ inline int f16_wgrad_splits(int M, int N, int K) { return wgrad_splits(M, N, K, 
 // inside its amax scale -, and with p > 0 a device seed and whole groups (rows16: of a multiple of 16 rows - a weight gradient's K-steps)
 inline bool adrop_args_ok(float p, int g1, int g2, const unsigned long long* seed, bool rows16) {
   return p >= 0.f && p < 0.5f && (p == 0.f || (seed && g1 > 0 && g2 > 0 && (!rows16 || g1 % 16 == 0)));
+}
+
+// a row skip as the fp16 weight-gradient kernel takes it, over R = g1 g2 token rows (each group once): whole K-steps per group, groups
+// of at least 256 rows (a run of kept K-steps pays one pipeline fill: the enc-dec site's 64-row time-step groups would pay it every 4
+// K-steps and are left out on purpose), at most 64 groups (one lane and one mask bit each).  Anything else: the launch runs every K-step.
+inline bool wgrad_row_skip_ok(const DropSpec& s, const unsigned long long* seed, long long R) {
+  return s.thresh && seed && s.mode == 1 && s.g1 % 16 == 0 && s.g1 >= 256 && s.g2 <= 64 && (long long)s.g1 * s.g2 == R;
 }
 
 // The launchers run what the planner of gemm.hip (plan_gemm) chose: they set p.tiles_* / p.colgroups for their tiles and launch.

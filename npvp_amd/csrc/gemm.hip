@@ -620,8 +620,8 @@ extern "C" int npvp_gemm_f32_skip(int a_kc, int b_kc, int M, int N, int K, const
                                   float adrop_p, int adrop_g1, int adrop_g2, unsigned int adrop_salt,
                                   float skip_p, int skip_g1, int skip_g2, unsigned int skip_salt,
                                   void* workspace, long long ws_bytes, hipStream_t stream) {
-  NPVP_CHECK_ARG(skip_p >= 0.f && skip_p < 1.f && (skip_p == 0.f || (seed && skip_g1 > 0 && skip_g2 > 0 && a_kc)),
-                 "gemm: the row skip needs a device seed, row groups and a row-major A");
+  NPVP_CHECK_ARG(skip_p >= 0.f && skip_p < 1.f && (skip_p == 0.f || (seed && skip_g1 > 0 && skip_g2 > 0 && (a_kc || !b_kc))),
+                 "gemm: the row skip needs a device seed, row groups and a row-major A or a weight gradient's layout");
   NPVP_CHECK_ARG(M > 0 && N > 0 && K > 0, "gemm: empty problem");
   NPVP_CHECK_ARG(precision == 0 || precision == 4 || precision == 5 || precision == 6,
                  "gemm: precision must be 0 (exact fp32-input MFMA), 4 (three-term bf16 split, 6 MFMAs per product: "
@@ -680,7 +680,7 @@ extern "C" int npvp_gemm_f32_skip(int a_kc, int b_kc, int M, int N, int K, const
   const dim3 grid(p.tiles_m * p.tiles_n, plan.splits), block(GEMM_THREADS);
   switch (plan.id) {
     case 5: case 7: launch_gemm_f16(p, plan.variant, stream); break;
-    case 6: launch_gemm_wgrad_f16(p, stream); break;
+    case 6: launch_gemm_wgrad_f16(p, stream); break;      // (takes the row skip as npvp_wgrad_f16_chained_skip does: same kernel, same slabs)
     case 2: case 4: launch_gemm_wide(p, plan.variant, stream); break;
     case 3: launch_gemm_wgrad_wide(p, stream); break;
     case 0:

@@ -436,12 +436,24 @@ __device__ __forceinline__ void gemm_wgrad_f16_body(const GemmParams& p, char* l
   }
   const int tile_m = tl / p.tiles_n, tile_n = tl - tile_m * p.tiles_n;
   const int m0 = tile_m * BM, n0 = tile_n * BN;
-  const float* A = p.A + (long long)z * p.K * p.lda;
-  const float* B = p.B + (long long)z * p.K * p.ldb;
   const int t = threadIdx.x, lane = t & 63, wave = __builtin_amdgcn_readfirstlane(t >> 6);
   const int wm = wave / WN, wn = wave % WN, r = lane & 31, h = lane >> 5;
-  const int nk = p.K >> 4;
   const float sa = amax_scale(amax_slot_read(p.a_amax)), sb = amax_scale(amax_slot_read(p.b_amax));
+  // THE K-STEPS OF SPLIT z, as runs of consecutive real K-steps (kept_runs.h).  Without a row skip: the one run [z K/16, (z + 1) K/16).
+  // ROW SKIP (GemmParams::rskip: the DropPath of the site whose gradient dy is; K == g1 g2, g2 <= 64, settled by the launcher): the
+  // rows of A = dy in dropped groups are zero, so their K-steps add nothing to dW or the column sums, and B = x is not read there.
+  // Lane g decides group g from the device seed - the function the site's epilogue used -, one ballot makes the wave-uniform kept
+  // mask, and the KEPT K-steps are dealt evenly over the splits: the launch is one round of workgroups, it gets shorter only if
+  // every workgroup does.  The pipeline below runs once per run, on the base pointers and step count of that run; the accumulators,
+  // cs and cm4 carry over.  A split whose share is empty runs nothing and stores a zero slab and zero column sums.
+  unsigned long long keep = 1ull;
+  int spg = (p.K >> 4) * p.splits;
+  if (p.rskip.thresh) {
+    const unsigned long long sseed = *p.seed;
+    keep = __builtin_amdgcn_ballot_w64(lane < p.rskip.g2 && rng_u32(sseed, p.rskip.salt, (uint64_t)lane) >= p.rskip.thresh);
+    spg = p.rskip.g1 >> 4;
+  }
+  KeptRuns runs = kept_runs_of_split(keep, spg, p.splits, z);
 
   f32x16 acc[TM][TN];
 #pragma unroll
@@ -454,8 +466,9 @@ __device__ __forceinline__ void gemm_wgrad_f16_body(const GemmParams& p, char* l
   const int ka = t >> 5, cqa = t & 31, kb = t >> 6, cqb = t & 63;
   // global addresses = wave-uniform base (advanced per K-step and per row group by scalar adds) + one 32-bit lane offset per
   // operand: the loads take the scalar-base form and the loop has no 64-bit vector adds
-  const char* a_base = reinterpret_cast<const char*>(A);
-  const char* b_base = reinterpret_cast<const char*>(B);
+  const char* a_base; const char* b_base;                  // of the run
+  int nk;                                                  // K-steps of the run
+  long long arow0;                                         // its first row
   const unsigned int a_voff = (unsigned int)(((long long)ka * p.lda + min(m0 + 4 * cqa, p.M - 4)) * 4);
   const unsigned int b_voff = (unsigned int)(((long long)kb * p.ldb + min(n0 + 4 * cqb, p.N - 4)) * 4);
   const long long a_row8 = 32 * p.lda, b_row4 = 16 * p.ldb, a_step = 64 * p.lda, b_step = 64 * p.ldb;      // bytes
@@ -492,22 +505,12 @@ __device__ __forceinline__ void gemm_wgrad_f16_body(const GemmParams& p, char* l
   // a row-group mask on A = dy [K][M]: the 16 rows of a K-step belong to ONE group (g1 % 16 == 0, checked by the launcher), so the
   // step's mask is one wave-uniform factor folded into the scale (and into the bias-gradient sums); am_ = mask of the tile in ra
   const unsigned long long aseed = p.adrop.thresh ? *p.seed : 0ull;
-  const long long arow0 = (long long)z * p.K;
   float am_ = 1.f;
 #define NPVP_G_AMASK(KT) { if (p.adrop.thresh) am_ = drop_spec_scale(p.adrop, aseed, arow0 + 16ll * min((KT), nk - 1), 0, 1); }
 #define NPVP_G_STORE_A(ST) { const float sam_ = sa * am_;                                                                        \
     if (p.range_flag) cm4 = __builtin_elementwise_max(cm4, __builtin_elementwise_max(__builtin_elementwise_abs(ra[0]), __builtin_elementwise_abs(ra[1]))); \
     NPVP_G_STORE((ST) + a_dst, ra[0], sam_, A_PLANE) NPVP_G_STORE((ST) + a_dst + 8 * ROWA, ra[1], sam_, A_PLANE) }
 #define NPVP_G_STORE_B(ST, I) NPVP_G_STORE((ST) + b_dst + (I) * 4 * ROWB, rb[I], sb, B_PLANE)
-
-  NPVP_G_LOAD(0)
-  NPVP_G_AMASK(0)
-  NPVP_G_WAIT(0, "+v"(ra[0]), "+v"(ra[1]), "+v"(rb[0]), "+v"(rb[1]), "+v"(rb[2]), "+v"(rb[3]))
-  if (want_cs) cs += (ra[0] + ra[1]) * am_;
-  NPVP_G_STORE_A(lds)
-  NPVP_G_STORE_B(lds, 0) NPVP_G_STORE_B(lds, 1) NPVP_G_STORE_B(lds, 2) NPVP_G_STORE_B(lds, 3)
-  NPVP_G_LOAD(1)
-  __syncthreads();
 
 #define NPVP_G_STEP(KT, CUR, NXT)                                                                            \
   {                                                                                                          \
@@ -535,15 +538,38 @@ __device__ __forceinline__ void gemm_wgrad_f16_body(const GemmParams& p, char* l
     __builtin_amdgcn_s_barrier();                                                                            \
   }
 
-  int kt = 0;
-  for (; kt + 1 < nk; kt += 2) {
-    NPVP_G_STEP(kt, 0, 1)
-    NPVP_G_STEP(kt + 1, 1, 0)
+  // one pass of the pipeline per run: the loop around it is scalar code.  (A run ends on the step's barrier with every wave's LDS
+  // reads done and on vmcnt(0): the next run's prologue may overwrite stage 0.)  BOTTOM-TESTED on purpose: as `while (next run)`
+  // the loop leaves from its header with the accumulators live, and the register allocator then shuffles their eight 16-register
+  // tuples through scratch memory (255 VGPRs + 96 spilled; with scratch every launch pays ~33 us of set-up: 309 -> 289 TF
+  // stand-alone with nothing dropped).  In this form the kernel has the 210 VGPRs and no scratch of the body without the loop.
+  int k0, klen;
+  if (kept_runs_next(runs, k0, klen)) {
+#pragma nounroll
+  do {
+    a_base = reinterpret_cast<const char*>(p.A + 16ll * k0 * p.lda);
+    b_base = reinterpret_cast<const char*>(p.B + 16ll * k0 * p.ldb);
+    nk = klen; arow0 = 16ll * k0;
+    NPVP_G_LOAD(0)
+    NPVP_G_AMASK(0)
+    NPVP_G_WAIT(0, "+v"(ra[0]), "+v"(ra[1]), "+v"(rb[0]), "+v"(rb[1]), "+v"(rb[2]), "+v"(rb[3]))
+    if (want_cs) cs += (ra[0] + ra[1]) * am_;
+    NPVP_G_STORE_A(lds)
+    NPVP_G_STORE_B(lds, 0) NPVP_G_STORE_B(lds, 1) NPVP_G_STORE_B(lds, 2) NPVP_G_STORE_B(lds, 3)
+    NPVP_G_LOAD(1)
+    __syncthreads();
+
+    int kt = 0;
+    for (; kt + 1 < nk; kt += 2) {
+      NPVP_G_STEP(kt, 0, 1)
+      NPVP_G_STEP(kt + 1, 1, 0)
+    }
+    if (kt < nk) NPVP_G_STEP(kt, 0, 1)
+    // (the clamped loads past the last tile still target ra / rb: TIED to the wait - a dead asm output may be given a register that
+    //  the code between the load and this wait uses for something else, and the load then lands in it; see gemm_f16_kernel)
+    asm volatile("s_waitcnt vmcnt(0)" : "+v"(ra[0]), "+v"(ra[1]), "+v"(rb[0]), "+v"(rb[1]), "+v"(rb[2]), "+v"(rb[3]) :: "memory");
+  } while (kept_runs_next(runs, k0, klen));
   }
-  if (kt < nk) NPVP_G_STEP(kt, 0, 1)
-  // (the clamped loads past the last tile still target ra / rb: TIED to the wait - a dead asm output may be given a register that
-  //  the code between the load and this wait uses for something else, and the load then lands in it; see gemm_f16_kernel)
-  asm volatile("s_waitcnt vmcnt(0)" : "+v"(ra[0]), "+v"(ra[1]), "+v"(rb[0]), "+v"(rb[1]), "+v"(rb[2]), "+v"(rb[3]) :: "memory");
   if (p.range_flag) {
     // column maxima of the chunk: 8 threads (ka = 0..7, all four waves) hold partial maxima of the same four columns
     float* red = reinterpret_cast<float*>(lds);            // (the stages are idle: the loop ended on a barrier)
@@ -646,7 +672,9 @@ static int reduce_rows_for(const ReduceJob& j, int tiles) {
 }
 
 // the grid of gemm_wgrad_f16_body for p: x = its 128 x 256 tiles, y = p's splits + the rows that reduce p.prev; sets p.tiles_* / p.prev.blocks
+// (and settles p.rskip: off unless the body takes it, wgrad_row_skip_ok)
 static dim3 size_gemm_wgrad_f16(GemmParams& p) {
+  if (!wgrad_row_skip_ok(p.rskip, p.seed, (long long)p.K * p.splits)) p.rskip.thresh = 0u;
   p.tiles_m = (p.M + 127) / 128;
   p.tiles_n = (p.N + 255) / 256;
   const int tiles = p.tiles_m * p.tiles_n, rr = reduce_rows_for(p.prev, tiles);
@@ -673,13 +701,13 @@ static bool deferred_wgrad_args_ok(const char* who, const float* dy, long long l
 
 // dw[M][N] (+)= dy[K][M]^T x[K][N] on the fp16 kernel, its split-K slabs (and column sums) left in `workspace`; prev_job rides along
 static GemmParams deferred_wgrad_params(int M, int N, int K, const float* dy, long long lda, const float* x, long long ldb, const float* a_amax, const float* b_amax,
-                                        unsigned int* range_flag, const DropSpec& adrop, const unsigned long long* seed, const void* prev_job, void* workspace,
-                                        bool want_db, int accumulate) {
+                                        unsigned int* range_flag, const DropSpec& adrop, const DropSpec& rskip, const unsigned long long* seed,
+                                        const void* prev_job, void* workspace, bool want_db, int accumulate) {
   GemmParams p = {};
   p.A = dy; p.B = x; p.lda = lda; p.ldb = ldb; p.M = M; p.N = N; p.alpha = 1.f;
   p.splits = f16_wgrad_splits(M, N, K); p.colgroups = 1; p.accum = accumulate ? 1 : 0;
   aim_at_workspace(p, K, p.splits, workspace, want_db);
-  p.seed = seed; p.drop = make_drop_spec(0.f, 0u, 0, 1, 1); p.adrop = adrop;
+  p.seed = seed; p.drop = make_drop_spec(0.f, 0u, 0, 1, 1); p.adrop = adrop; p.rskip = rskip;
   p.a_amax = a_amax; p.b_amax = b_amax; p.range_flag = range_flag;
   if (prev_job) p.prev = *reinterpret_cast<const ReduceJob*>(prev_job);
   return p;
@@ -865,22 +893,34 @@ extern "C" long long npvp_wgrad_f16_chain_workspace_bytes(int M, int N, int K) {
   return s > 1 ? splitk_workspace_bytes(s, M, N) : 0;
 }
 
-extern "C" int npvp_wgrad_f16_chained(int M, int N, int K, const float* dy, long long lda, const float* x, long long ldb, float* dw,
-                                      long long ldc, float* db, int accumulate, const float* a_amax, const float* b_amax,
-                                      unsigned int* range_flag, float adrop_p, int adrop_g1, int adrop_g2, unsigned int adrop_salt,
-                                      const unsigned long long* seed, const void* prev_job, void* my_job, void* workspace,
-                                      long long ws_bytes, hipStream_t stream) {
+extern "C" int npvp_wgrad_f16_chained_skip(int M, int N, int K, const float* dy, long long lda, const float* x, long long ldb, float* dw,
+                                           long long ldc, float* db, int accumulate, const float* a_amax, const float* b_amax,
+                                           unsigned int* range_flag, float adrop_p, int adrop_g1, int adrop_g2, unsigned int adrop_salt,
+                                           float skip_p, int skip_g1, int skip_g2, unsigned int skip_salt,
+                                           const unsigned long long* seed, const void* prev_job, void* my_job, void* workspace,
+                                           long long ws_bytes, hipStream_t stream) {
+  NPVP_CHECK_ARG(skip_p >= 0.f && skip_p < 1.f && (skip_p == 0.f || (seed && skip_g1 > 0 && skip_g2 > 0)),
+                 "wgrad_f16_chained: the row skip needs a device seed and row groups");
   NPVP_CHECK_ARG(npvp_wgrad_f16_chainable(M, N, K), "wgrad_f16_chained: shape not taken (npvp_wgrad_f16_chainable tells)");
   NPVP_CHECK_ARG(dy && x && dw && a_amax && b_amax && my_job, "wgrad_f16_chained: null operand / amax slot / job");
   if (!deferred_wgrad_args_ok("wgrad_f16_chained", dy, lda, x, ldb, dw, ldc, adrop_p, adrop_g1, adrop_g2, seed, workspace, ws_bytes,
                               npvp_wgrad_f16_chain_workspace_bytes(M, N, K))) return NPVP_ERR_ARG;
   NPVP_CHECK_ARG(!db || ((uintptr_t)db % 16) == 0, "wgrad_f16_chained: the bias gradient must be 16-byte aligned");
   GemmParams p = deferred_wgrad_params(M, N, K, dy, lda, x, ldb, a_amax, b_amax, range_flag, make_drop_spec(adrop_p, adrop_salt, 1, adrop_g1, adrop_g2),
-                                       seed, prev_job, workspace, db != nullptr, accumulate);
+                                       make_drop_spec(skip_p, skip_salt, 1, skip_g1, skip_g2), seed, prev_job, workspace, db != nullptr, accumulate);
   launch_gemm_wgrad_f16(p, stream);
   NPVP_CHECK_LAUNCH();
   leave_reduce_job(p, dw, ldc, db, my_job);
   return NPVP_OK;
+}
+
+extern "C" int npvp_wgrad_f16_chained(int M, int N, int K, const float* dy, long long lda, const float* x, long long ldb, float* dw,
+                                      long long ldc, float* db, int accumulate, const float* a_amax, const float* b_amax,
+                                      unsigned int* range_flag, float adrop_p, int adrop_g1, int adrop_g2, unsigned int adrop_salt,
+                                      const unsigned long long* seed, const void* prev_job, void* my_job, void* workspace,
+                                      long long ws_bytes, hipStream_t stream) {
+  return npvp_wgrad_f16_chained_skip(M, N, K, dy, lda, x, ldb, dw, ldc, db, accumulate, a_amax, b_amax, range_flag, adrop_p, adrop_g1, adrop_g2,
+                                     adrop_salt, 0.f, 1, 1, 0u, seed, prev_job, my_job, workspace, ws_bytes, stream);
 }
 
 // ---- dgrad + weight gradient of one linear layer in ONE launch (gemm_f16_group_kernel; include/npvp_hip.h) ---------------------------
@@ -916,11 +956,11 @@ extern "C" int npvp_linear_bwd_f16_skip(int R, int N, int K, const float* dy, lo
   d.residual = residual; d.ldr = ldr; d.seed = seed; d.splits = 1;
   d.drop = make_drop_spec(drop_p, drop_salt, drop_mode, drop_g1, drop_g2);
   d.adrop = make_drop_spec(adrop_p, adrop_salt, 1, adrop_g1, adrop_g2);
-  d.rskip = make_drop_spec(skip_p, skip_salt, 1, skip_g1, skip_g2);      // (the dgrad's tiles only: the weight gradient runs every K-step)
+  d.rskip = make_drop_spec(skip_p, skip_salt, 1, skip_g1, skip_g2);      // (the dgrad's tiles; the weight gradient's K-steps where its body takes the spec)
   d.b_pre = w_planes_d; d.b_pre_plane = (long long)N * K;
   d.a_amax = dy_amax; d.b_amax = w_amax; d.c_amax = dx_amax;
   // problem 1: dW[N][K] += dy^T x over R rows, split-K, reduction handed to a later launch (as npvp_wgrad_f16_chained)
-  GemmParams& w = g.p[1] = deferred_wgrad_params(N, K, R, dy, ldy, x, ldxx, dy_amax, x_amax, range_flag, d.adrop, seed, prev_job, workspace, db != nullptr, 1);
+  GemmParams& w = g.p[1] = deferred_wgrad_params(N, K, R, dy, ldy, x, ldxx, dy_amax, x_amax, range_flag, d.adrop, d.rskip, seed, prev_job, workspace, db != nullptr, 1);
   const dim3 wgrid = size_gemm_wgrad_f16(w);
   // the dgrad's tiles: 64 x 128 where the launch then still fits the chip's 512 workgroup slots with the weight gradient's
   // workgroups beside it, else 128 x 128 (8 192 rows: 256 + 256 workgroups in one round beat 512 + 256 in one and a half -

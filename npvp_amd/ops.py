@@ -505,10 +505,12 @@ def masked_grad(dy2, drop, w):
 DROP_PATH_IN_GEMM_ROWS = 1 << 30
 
 
-def linear_wgrad(dy, x, with_bias_grad=False, into=None, into_b=None, dy_amax=None, x_amax=None, a_drop=NO_DROP):
+def linear_wgrad(dy, x, with_bias_grad=False, into=None, into_b=None, dy_amax=None, x_amax=None, a_drop=NO_DROP, row_skip=NO_DROP):
     """dw[N,K] = dy[R,N]^T x[R,K]; with_bias_grad also returns db[N] = column sums of dy, accumulated by the same
     kernel while it stages dy (no separate reduction pass).  into / into_b: ACCUMULATE into these existing
-    gradient slices instead of allocating results (GradSink).  Range of the fp16 arithmetic: RangeGuard."""
+    gradient slices instead of allocating results (GradSink).  Range of the fp16 arithmetic: RangeGuard.  row_skip: row groups in
+    which dy is zero (WGRAD_ROW_SKIP): the fp16 weight-gradient kernel - chained, or with a reduction launch of its own - leaves
+    their K-steps out; every other route ignores it."""
     R, N = dy.shape
     K = x.shape[1]
     acc = into is not None
@@ -534,10 +536,16 @@ def linear_wgrad(dy, x, with_bias_grad=False, into=None, into_b=None, dy_amax=No
         else:
             dw, db = tw, tb
     elif plan.route == "chained":
-        c.chain.launch(dy, x, dw, db, amax_of(dy, dy_amax), amax_of(x, x_amax), a_drop, flag)
+        c.chain.row_skip = row_skip if (WGRAD_ROW_SKIP and row_skip.on) else None
+        try:
+            c.chain.launch(dy, x, dw, db, amax_of(dy, dy_amax), amax_of(x, x_amax), a_drop, flag)
+        finally:
+            c.chain.row_skip = None
     else:
         gemm(0, 0, N, K, R, dy, dy.stride(0), x, x.stride(0), dw, colsum_a=db, accumulate=acc, precision=plan.precision, a_amax=dy_amax,
-             b_amax=x_amax, a_drop=a_drop, range_flag=flag)
+             b_amax=x_amax, a_drop=a_drop, range_flag=flag, row_skip=row_skip if WGRAD_ROW_SKIP else NO_DROP)
+        # (the same fp16 kernel with a reduction launch of its own takes the spec as the chained launch does: the two routes stay
+        #  bit-identical - chain on / off, eager / segmented data-parallel step; the bf16x6 kernels ignore it)
     return (dw, db) if with_bias_grad else dw
 
 
@@ -563,11 +571,14 @@ class FusedLinearBwd:
 
 
 def linear_bwd(dy, x, w, b, sk, act=0, aux_in=None, drop=NO_DROP, residual=None, dy_amax=None, dx_amax=None, a_drop=NO_DROP,
-               row_skip=NO_DROP):
+               row_skip=NO_DROP, wgrad_skip=None):
     """The backward of y = x w^T + b given dy [R, N]: -> dx = epilogue((a_drop mask) dy w), gw, gb - the weight (+ bias) gradient goes
     into the sink `sk` (-> None, None) or is returned.  One launch where FusedLinearBwd takes the shape, else the dgrad on this
     stream and the weight gradient on the gradient stream as before.  row_skip: row groups in which dy is zero (see gemm): the
-    dgrad leaves their tiles out; it is used by the dgrad launch made here, never by a deferred one."""
+    dgrad leaves their tiles out.  wgrad_skip: the same for the weight gradient alone (None: row_skip) - with WGRAD_ROW_SKIP its
+    chained fp16 launch leaves the K-steps of those rows out and does not read x there.  The fused launch takes ONE spec for both
+    halves (row_skip, else wgrad_skip: a dgrad tile it then leaves out would have summed the same zeros)."""
+    ws_ = (row_skip if wgrad_skip is None else wgrad_skip) if WGRAD_ROW_SKIP else NO_DROP
     R, N = dy.shape
     K = w.shape[1]
     has_b = b is not None
@@ -580,7 +591,7 @@ def linear_bwd(dy, x, w, b, sk, act=0, aux_in=None, drop=NO_DROP, residual=None,
     if not plan.fused:
         dx = linear_dgrad(dy, w, act=act, aux_in=aux_in, drop=drop, residual=residual, dy_amax=dy_amax, dx_amax=dx_amax, a_drop=a_drop,
                           row_skip=row_skip)
-        gw, gb = _lin_grads(dy, x, w, b, sk, a_drop=a_drop, plan=plan)
+        gw, gb = _lin_grads(dy, x, w, b, sk, a_drop=a_drop, plan=plan, row_skip=ws_)
         return dx, gw, gb
     planes, w_amax = pl
     gw, gb = sk[0][0], (sk[1][0] if has_b else None)
@@ -589,6 +600,8 @@ def linear_bwd(dy, x, w, b, sk, act=0, aux_in=None, drop=NO_DROP, residual=None,
     dx = torch.empty(R, K, dtype=torch.float32, device=dev)
     ws, wsn = _ws(c.chain.workspace_bytes(N, K, R), dev)
     st = _stream()
+    if not row_skip.on:
+        row_skip = ws_
     seed = c.rng.seed_tensor(dev) if (drop.on or a_drop.on or row_skip.on) else None
     outs = (gw.data_ptr(),) if gb is None else (gw.data_ptr(), gb.data_ptr())
     later = c.chain if plan.reduction == "chained" else c.reduce       # who runs this launch's split-K reduction
@@ -1075,18 +1088,18 @@ class _Linear(torch.autograd.Function):
         return dx, dw, db, dres, None, None
 
 
-def _lin_grads(dy, x, w, b, sk, a_drop=NO_DROP, plan=None):
+def _lin_grads(dy, x, w, b, sk, a_drop=NO_DROP, plan=None, row_skip=NO_DROP):
     """weight (+ bias) gradient of y = x w^T + b (`b` only says whether there is a bias gradient to take): accumulated into the
-    sink `sk` (-> None, None) - on the gradient stream when there is one - or returned"""
+    sink `sk` (-> None, None) - on the gradient stream when there is one - or returned.  row_skip: see linear_wgrad"""
     has_b = b is not None
     if plan is None:
         plan = linear_bwd_plan(dy.shape[0], dy.shape[1], x.shape[1], GEMM_PRECISION, _sunk(sk, has_b), _S._cur.wgrad.enabled)
     if not plan.sunk:
-        g = linear_wgrad(dy, x, has_b, a_drop=a_drop)
+        g = linear_wgrad(dy, x, has_b, a_drop=a_drop, row_skip=row_skip)
         return (g[0], g[1]) if has_b else (g, None)
     a1, a2 = (amax_of(dy), amax_of(x)) if plan.fill_slots else (None, None)
-    fn = lambda dy=dy, x=x, gw=sk[0][0], gb=(sk[1][0] if has_b else None), a1=a1, a2=a2, ad=a_drop: \
-        linear_wgrad(dy, x, has_b, into=gw, into_b=gb, dy_amax=a1, x_amax=a2, a_drop=ad)
+    fn = lambda dy=dy, x=x, gw=sk[0][0], gb=(sk[1][0] if has_b else None), a1=a1, a2=a2, ad=a_drop, rs=row_skip: \
+        linear_wgrad(dy, x, has_b, into=gw, into_b=gb, dy_amax=a1, x_amax=a2, a_drop=ad, row_skip=rs)
     if plan.on_grad_stream:
         _S._cur.wgrad.run(fn, dy, x, wrote=sk, urgent=plan.urgent)
     else:
@@ -1634,9 +1647,16 @@ class _MlpDwbn(torch.autograd.Function):
 MID_BWD_N2 = True        # (False: norm2's backward as two kernels of its own - the op test compares the two routes)
 # The node leaves out work on the samples its DropPath drops: its forward frame kernels and norm1's backward write zeros for their
 # frames (csrc/common.h FrameSkip) and the fc1 / fc2 forward and dgrad GEMMs run the tiles inside them on zero accumulators
-# (GemmParams::rskip); the decision is taken on the device from the seed.  The fused middle's backward, norm2's parameter-gradient
-# pass and the weight gradients compute every frame (profiles/droppath_skip.txt).  False: nothing is left out (A/B runs, tests).
+# (GemmParams::rskip); the decision is taken on the device from the seed.  The fused middle's backward and norm2's parameter-gradient
+# pass compute every frame (profiles/droppath_skip.txt); the weight gradients have a switch of their own, below.  False: nothing is left out (A/B runs, tests).
 DROP_PATH_SKIP = True
+# The fp16 weight gradients of a per-sample DropPath site - fc1 / fc2 of this node, the three projections of the spatial
+# self-attention sub-layer - leave out the K-steps of dropped samples (their rows of dy are exact zeros) and deal the kept ones evenly
+# over the split-K workgroups (npvp_wgrad_f16_chained_skip, and the same kernel behind npvp_gemm_f32_skip where the reduction is not
+# chained: same slabs, same bits; csrc/kept_runs.h).  The kernel takes samples of at least 256 token rows, at most 64 of them; every
+# other route (bf16x6, the RangeGuard fallback and strict routes, small shapes) ignores the spec.  False: every K-step runs in those
+# launches (the fused dgrad + weight-gradient launch keeps the one spec DROP_PATH_SKIP gives it).  profiles/wgrad_row_skip.txt
+WGRAD_ROW_SKIP = True
 
 
 def mlpdwbn_fused_supported(R, C, hid, Co, H, W):
@@ -1895,7 +1915,11 @@ class _SelfAttnSublayer(torch.autograd.Function):
         C = x2.shape[1]
         dy2 = _c(dy).reshape(-1, C)
         dz, ad = masked_grad(dy2, drop, wo)
-        do, gwo, gbo = linear_bwd(dz, o, wo, bo, s_o, a_drop=ad)
+        # a per-sample DropPath (the spatial site) leaves dz - masked here or inside the GEMMs -, hence do, dqk and dv (attention
+        # stays inside a sample) zero in the rows of dropped samples: the three weight gradients leave them out (WGRAD_ROW_SKIP).
+        # The tiling route only: the centre-pad route's projections run on padded rows, where the samples are no row groups
+        rs = drop if (drop.on and drop.mode == 1 and cfg.tiles and drop.g1 * drop.g2 == dy2.shape[0]) else NO_DROP
+        do, gwo, gbo = linear_bwd(dz, o, wo, bo, s_o, a_drop=ad, wgrad_skip=rs)
         if not cfg.tiles:
             do = _raw_grid_pad(do, cfg, want_amax=False)            # the pad queries' outputs were cut away: their gradient is 0
         dqk, dv = torch.empty_like(qk), torch.empty_like(v)
@@ -1904,13 +1928,13 @@ class _SelfAttnSublayer(torch.autograd.Function):
             _zero_tail(cfg, dqk, dv)
         # (centre-pad route: `fused` holds the padded rows, see forward - the bias gradients sum the pad rows too, they are keys of
         # their windows, and the weight gradients see their zero rows)
-        dfused, gwqk, gbqk = linear_bwd(dqk, fused, wqk, bqk, s_qk)
+        dfused, gwqk, gbqk = linear_bwd(dqk, fused, wqk, bqk, s_qk, wgrad_skip=rs)
         if not cfg.tiles:
             dfused = _raw_grid_cut(dfused, cfg)
         du, dadd, dbeta, dgamma = _raw_posfuse_bwd(dfused, x1, add, beta_shape, gamma, pst, N, T, ctx.needs_input_grad[6], ctx.act_sinks)
         if cfg.tiles:
             # dx1 = dv Wv + du: the second consumer's gradient rides in as the dgrad GEMM's residual input (no separate add)
-            dx1, gwv, gbv = linear_bwd(dv, x1, wv, bv, s_v, residual=du)
+            dx1, gwv, gbv = linear_bwd(dv, x1, wv, bv, s_v, residual=du, wgrad_skip=rs)
         else:
             dx1, gwv, gbv = linear_bwd(dv, _raw_grid_pad(x1, cfg), wv, bv, s_v)
             dx1 = _raw_grid_cut(dx1, cfg, addend=du)                # ... here the shapes differ: du rides in as the cut's addend

@@ -595,8 +595,11 @@ class WgradChainState:
     a weight gradient accumulated in place on the gradient stream leaves its `splits` partial slabs in a workspace and a 64-byte
     job; the NEXT weight-gradient launch on that stream does the sum with extra workgroups (no launch of its own: 110 of the 170
     reduction launches of an 8-clip step; HBM-bound work beside MFMA-bound work), WgradStream.join() runs the last one.  Same
-    summation order as the stand-alone reduction, so results are bit-identical.  `enabled = False`: one reduction launch each."""
+    summation order as the stand-alone reduction, so results are bit-identical.  `enabled = False`: one reduction launch each.
+    `row_skip`: set by ops.linear_wgrad around launch() - the row groups of a DropPath site in which dy is zero; the launch then goes
+    through npvp_wgrad_f16_chained_skip, which leaves their K-steps out (the arguments of launch() stay what they are)."""
     enabled = True
+    row_skip = None
 
     def __init__(self, ctx):
         self.ctx = ctx
@@ -635,11 +638,16 @@ class WgradChainState:
         st = _stream()
         ws, wsn = _ws(self.workspace_bytes(N, K, R), dy.device)
         job_addr, prev_addr = self.job_slot(st)
-        seed = self.ctx.rng.seed_tensor(dy.device) if a_drop.on else None
+        rs = self.row_skip if (self.row_skip is not None and self.row_skip.on) else None
+        seed = self.ctx.rng.seed_tensor(dy.device) if (a_drop.on or rs is not None) else None
         pe = GemmProbe.begin(6)
-        check(lib().npvp_wgrad_f16_chained(N, K, R, _ptr(dy), dy.stride(0), _ptr(x), x.stride(0), _ptr(dw), dw.stride(0), _ptr(db), 1,
-                                           _ptr(dy_amax), _ptr(x_amax), _ptr(flag), a_drop.p, a_drop.g1, a_drop.g2, a_drop.salt,
-                                           _ptr(seed), prev_addr, job_addr, _ptr(ws), wsn, st), "npvp_wgrad_f16_chained")
+        head = (N, K, R, _ptr(dy), dy.stride(0), _ptr(x), x.stride(0), _ptr(dw), dw.stride(0), _ptr(db), 1, _ptr(dy_amax), _ptr(x_amax),
+                _ptr(flag), a_drop.p, a_drop.g1, a_drop.g2, a_drop.salt)
+        tail = (_ptr(seed), prev_addr, job_addr, _ptr(ws), wsn, st)
+        if rs is not None:
+            check(lib().npvp_wgrad_f16_chained_skip(*head, rs.p, rs.g1, rs.g2, rs.salt, *tail), "npvp_wgrad_f16_chained_skip")
+        else:
+            check(lib().npvp_wgrad_f16_chained(*head, *tail), "npvp_wgrad_f16_chained")
         GemmProbe.end(pe, 2.0 * N * K * R, 4.0 * (N * R + K * R + N * K), (0, 0), 6)
         self.job_added(st, None, (ws, dw, db), None)
 
