@@ -84,6 +84,26 @@ class Drop:
 
 
 NO_DROP = Drop(0.0)
+SkipRoles = namedtuple("SkipRoles", "frames forward dgrad wgrad fused")      # (what `skip_roles`, below, returns)
+FrameSkip = namedtuple("FrameSkip", "p salt fps")
+
+
+class SampleSkip(namedtuple("SampleSkip", "frame forward dgrad wgrad fused")):
+    """The samples a node's per-sample DropPath (a row-group Drop) drops, for the launches that leave their work out: built once by the node
+    (`of`) and handed down as a default-off keyword.  frame: the (p, salt, frames per sample) of the frame kernels; forward, dgrad, wgrad,
+    fused: the site as row groups of one sample's token rows - the skip words of the GEMM entry points - where skip_roles gives that launch
+    the spec, else NO_DROP.  The switches are read where the node builds it (forward or backward), not where a deferred weight gradient is flushed."""
+    __slots__ = ()
+
+    @classmethod
+    def of(cls, roles, drop, rows_per_sample, samples, rows):
+        on = drop.on and drop.mode == 1
+        rs = Drop._like(drop, 1, rows_per_sample, samples) if (on and rows_per_sample * samples == rows) else NO_DROP     # (they cover the rows once)
+        frame = FrameSkip(drop.p, drop.salt, rows_per_sample // 64) if (on and roles.frames) else NO_SKIP.frame          # (a frame: 64 token rows)
+        return cls(frame, *(rs if r else NO_DROP for r in roles[1:]))
+
+
+NO_SKIP = SampleSkip(FrameSkip(0.0, 0, 1), NO_DROP, NO_DROP, NO_DROP, NO_DROP)
 
 
 class DropRecorder:
@@ -327,8 +347,8 @@ def gemm(a_kc, b_kc, M, N, K, A, lda, B, ldb, out, bias=None, act=0, aux_in=None
     b_pre = WeightPlanes.get(...) = (planes, weight amax slot) or None; a_amax / b_amax: the operands' amax slots (f16x3; a
     missing slot of A - or of B for a weight gradient - is filled by the stand-alone reduction); c_amax: slot that receives
     the bound of the values stored to `out`.  a_drop: a row-group (DropPath) mask on the rows of A - fp16 kernels only, see
-    `masked_grad`.  row_skip: the row groups of a DropPath site whose rows of the result are multiplied by 0 later (forward) or
-    whose rows of A are zeros (dgrad): the fp16 forward / dgrad kernels leave out the tiles inside them (npvp_gemm_f32_skip)."""
+    `masked_grad`.  row_skip (SampleSkip): the row groups of a DropPath site whose rows of the result are multiplied by 0 later (forward)
+    or whose rows of A are zeros (backward): the fp16 kernels leave out the tiles (forward, dgrad) or K-steps (weight gradient) inside them."""
     # (this wrapper runs for a third of a step's launches: the optional arguments are tested in line instead of through _ptr / _chk,
     # ~3 us of its ~9 us of interpreter time)
     for t in (A, B, out, bias, aux_in, aux_out, residual, colsum_a):
@@ -354,8 +374,7 @@ def gemm(a_kc, b_kc, M, N, K, A, lda, B, ldb, out, bias=None, act=0, aux_in=None
     ws, wsn = (None, 0)
     if wsb > 0:
         ws, wsn = _ws(wsb, A.device)
-    masked = drop.p > 0.0 or a_drop.p > 0.0 or row_skip.p > 0.0
-    seed = _S._cur.rng.seed_tensor(A.device) if masked else None
+    seed = _S._cur.rng.seed_for(A.device, drop, a_drop, row_skip)
     if DropRecorder.sites is not None and not replay:
         DropRecorder.note(drop, "elem" if drop.mode == 0 else "group", M * N if drop.mode == 0 else drop.g2)
     # every launch is timed on the stream it runs on, also those that share the device with a kernel of another stream:
@@ -456,6 +475,14 @@ def wgrad_plan(N, K, R, precision, wgrad_precision, accumulate, masked, fallback
     return WgradPlan("gemm", prec, watch)
 
 
+@functools.lru_cache(maxsize=None)
+def skip_roles(node, dp, wg):
+    """Which launches of a node take its SampleSkip under DROP_PATH_SKIP = dp and WGRAD_ROW_SKIP = wg ("DropPath skip").  frames:
+    the MlpDWBN frame kernels; forward, dgrad: its fp16 GEMM tiles; wgrad: the K-steps of an unfused fp16 weight gradient, chained or not;
+    fused: the fused dgrad + weight-gradient launch, one spec for both halves.  "self_attn": the spatial sub-layer, whose dgrads take none."""
+    return {"mlpdwbn": SkipRoles(dp, dp, dp, dp and wg, dp), "self_attn": SkipRoles(False, False, False, wg, wg)}[node]
+
+
 def linear_fwd(x, w, b, act=0, aux_out=None, residual=None, drop=NO_DROP, rowstats=None, x_amax=None, y_amax=None):
     """y[R,N] = epilogue(x[R,K] w[N,K]^T); rowstats [R/64, N/64, 2] receives the frame-statistics partials of y;
     x_amax: x's amax slot if its producer filled one; y_amax: slot to receive the bound of y"""
@@ -508,9 +535,8 @@ DROP_PATH_IN_GEMM_ROWS = 1 << 30
 def linear_wgrad(dy, x, with_bias_grad=False, into=None, into_b=None, dy_amax=None, x_amax=None, a_drop=NO_DROP, row_skip=NO_DROP):
     """dw[N,K] = dy[R,N]^T x[R,K]; with_bias_grad also returns db[N] = column sums of dy, accumulated by the same
     kernel while it stages dy (no separate reduction pass).  into / into_b: ACCUMULATE into these existing
-    gradient slices instead of allocating results (GradSink).  Range of the fp16 arithmetic: RangeGuard.  row_skip: row groups in
-    which dy is zero (WGRAD_ROW_SKIP): the fp16 weight-gradient kernel - chained, or with a reduction launch of its own - leaves
-    their K-steps out; every other route ignores it."""
+    gradient slices instead of allocating results (GradSink).  Range of the fp16 arithmetic: RangeGuard.  row_skip (SampleSkip): row groups
+    in which dy is zero - the fp16 weight-gradient kernel leaves their K-steps out, chained or not (same bits); every other route ignores it."""
     R, N = dy.shape
     K = x.shape[1]
     acc = into is not None
@@ -536,16 +562,10 @@ def linear_wgrad(dy, x, with_bias_grad=False, into=None, into_b=None, dy_amax=No
         else:
             dw, db = tw, tb
     elif plan.route == "chained":
-        c.chain.row_skip = row_skip if (WGRAD_ROW_SKIP and row_skip.on) else None
-        try:
-            c.chain.launch(dy, x, dw, db, amax_of(dy, dy_amax), amax_of(x, x_amax), a_drop, flag)
-        finally:
-            c.chain.row_skip = None
+        c.chain.launch(dy, x, dw, db, amax_of(dy, dy_amax), amax_of(x, x_amax), a_drop, flag, row_skip)
     else:
         gemm(0, 0, N, K, R, dy, dy.stride(0), x, x.stride(0), dw, colsum_a=db, accumulate=acc, precision=plan.precision, a_amax=dy_amax,
-             b_amax=x_amax, a_drop=a_drop, range_flag=flag, row_skip=row_skip if WGRAD_ROW_SKIP else NO_DROP)
-        # (the same fp16 kernel with a reduction launch of its own takes the spec as the chained launch does: the two routes stay
-        #  bit-identical - chain on / off, eager / segmented data-parallel step; the bf16x6 kernels ignore it)
+             b_amax=x_amax, a_drop=a_drop, range_flag=flag, row_skip=row_skip)
     return (dw, db) if with_bias_grad else dw
 
 
@@ -570,15 +590,11 @@ class FusedLinearBwd:
         return linear_bwd_plan(R, N, K, 6, True, False, True, True, True, True, False, cls.MAX_ROWS).fused
 
 
-def linear_bwd(dy, x, w, b, sk, act=0, aux_in=None, drop=NO_DROP, residual=None, dy_amax=None, dx_amax=None, a_drop=NO_DROP,
-               row_skip=NO_DROP, wgrad_skip=None):
+def linear_bwd(dy, x, w, b, sk, act=0, aux_in=None, drop=NO_DROP, residual=None, dy_amax=None, dx_amax=None, a_drop=NO_DROP, skip=NO_SKIP):
     """The backward of y = x w^T + b given dy [R, N]: -> dx = epilogue((a_drop mask) dy w), gw, gb - the weight (+ bias) gradient goes
     into the sink `sk` (-> None, None) or is returned.  One launch where FusedLinearBwd takes the shape, else the dgrad on this
-    stream and the weight gradient on the gradient stream as before.  row_skip: row groups in which dy is zero (see gemm): the
-    dgrad leaves their tiles out.  wgrad_skip: the same for the weight gradient alone (None: row_skip) - with WGRAD_ROW_SKIP its
-    chained fp16 launch leaves the K-steps of those rows out and does not read x there.  The fused launch takes ONE spec for both
-    halves (row_skip, else wgrad_skip: a dgrad tile it then leaves out would have summed the same zeros)."""
-    ws_ = (row_skip if wgrad_skip is None else wgrad_skip) if WGRAD_ROW_SKIP else NO_DROP
+    stream and the weight gradient on the gradient stream as before.  skip (SampleSkip): samples in whose rows dy is zero - where its roles say
+    so, the dgrad leaves their tiles out, the fp16 weight gradient their K-steps (x is not read there), the fused launch both with ONE spec."""
     R, N = dy.shape
     K = w.shape[1]
     has_b = b is not None
@@ -590,9 +606,8 @@ def linear_bwd(dy, x, w, b, sk, act=0, aux_in=None, drop=NO_DROP, residual=None,
                            FusedLinearBwd.enabled, FusedLinearBwd.with_gradient_stream, FusedLinearBwd.MAX_ROWS)
     if not plan.fused:
         dx = linear_dgrad(dy, w, act=act, aux_in=aux_in, drop=drop, residual=residual, dy_amax=dy_amax, dx_amax=dx_amax, a_drop=a_drop,
-                          row_skip=row_skip)
-        gw, gb = _lin_grads(dy, x, w, b, sk, a_drop=a_drop, plan=plan, row_skip=ws_)
-        return dx, gw, gb
+                          row_skip=skip.dgrad)
+        return (dx, *_lin_grads(dy, x, w, b, sk, a_drop=a_drop, plan=plan, row_skip=skip.wgrad))
     planes, w_amax = pl
     gw, gb = sk[0][0], (sk[1][0] if has_b else None)
     dev = dy.device
@@ -600,22 +615,17 @@ def linear_bwd(dy, x, w, b, sk, act=0, aux_in=None, drop=NO_DROP, residual=None,
     dx = torch.empty(R, K, dtype=torch.float32, device=dev)
     ws, wsn = _ws(c.chain.workspace_bytes(N, K, R), dev)
     st = _stream()
-    if not row_skip.on:
-        row_skip = ws_
-    seed = c.rng.seed_tensor(dev) if (drop.on or a_drop.on or row_skip.on) else None
+    rs = skip.fused
     outs = (gw.data_ptr(),) if gb is None else (gw.data_ptr(), gb.data_ptr())
     later = c.chain if plan.reduction == "chained" else c.reduce       # who runs this launch's split-K reduction
     job_addr, prev_addr = later.job_slot(st, outs)
     pe = GemmProbe.begin(8)
-    head = (R, N, K, dy.data_ptr(), dy.stride(0), dy_amax.data_ptr(), planes.data_ptr(), w_amax.data_ptr(), dx.data_ptr(), dx.stride(0),
-            act, _ptr(aux_in), _ptr(residual), 0 if residual is None else residual.stride(0), drop.p, drop.mode, drop.g1, drop.g2,
-            drop.salt, _ptr(dx_amax), x.data_ptr(), x.stride(0), x_amax.data_ptr(), gw.data_ptr(), gw.stride(0), _ptr(gb),
-            _ptr(c.range_guard.flag(dev)), a_drop.p, a_drop.g1, a_drop.g2, a_drop.salt)
-    tail = (_ptr(seed), prev_addr, job_addr, ws.data_ptr(), wsn, st)
-    if row_skip.on:
-        check(lib().npvp_linear_bwd_f16_skip(*head, row_skip.p, row_skip.g1, row_skip.g2, row_skip.salt, *tail), "npvp_linear_bwd_f16_skip")
-    else:
-        check(lib().npvp_linear_bwd_f16(*head, *tail), "npvp_linear_bwd_f16")
+    check(lib().npvp_linear_bwd_f16_skip(
+        R, N, K, dy.data_ptr(), dy.stride(0), dy_amax.data_ptr(), planes.data_ptr(), w_amax.data_ptr(), dx.data_ptr(), dx.stride(0),
+        act, _ptr(aux_in), _ptr(residual), 0 if residual is None else residual.stride(0), drop.p, drop.mode, drop.g1, drop.g2,
+        drop.salt, _ptr(dx_amax), x.data_ptr(), x.stride(0), x_amax.data_ptr(), gw.data_ptr(), gw.stride(0), _ptr(gb),
+        _ptr(c.range_guard.flag(dev)), a_drop.p, a_drop.g1, a_drop.g2, a_drop.salt, rs.p, rs.g1, rs.g2, rs.salt,
+        _ptr(c.rng.seed_for(dev, drop, a_drop, rs)), prev_addr, job_addr, ws.data_ptr(), wsn, st), "npvp_linear_bwd_f16_skip")
     GemmProbe.end(pe, 4.0 * R * N * K, 4.0 * (2 * R * N + 2 * R * K + 2 * N * K), (1, 0), 8)
     later.job_added(st, outs, (ws, gw, gb), sk)
     return dx, None, None
@@ -1246,7 +1256,7 @@ def _attn_fwd_entry(cfg):
 
 def _attn_fwd(q, k, v, o, cfg):
     hd = o.shape[1] // cfg.heads
-    seed = _S._cur.rng.seed_tensor(q.device) if cfg.drop.on else None
+    seed = _S._cur.rng.seed_for(q.device, cfg.drop)
     if DropRecorder.sites is not None and cfg.drop.on:      # weights tensor [groups, heads, L, S]
         L_, S_ = _attn_len(cfg)
         DropRecorder.note(cfg.drop, "elem", _attn_groups(cfg) * cfg.heads * L_ * S_)
@@ -1288,7 +1298,7 @@ def _attn_samples_fwd(q, k, v, o, cfg, S, sample_chunk=0):
 def _attn_bwd(q, k, v, go, dq, dk, dv, cfg, packed=None):
     """packed: the [R, 2C] tensor dq and dk are the halves of (one amax slot for both, tagged on it)"""
     hd = go.shape[1] // cfg.heads
-    seed = _S._cur.rng.seed_tensor(q.device) if cfg.drop.on else None
+    seed = _S._cur.rng.seed_for(q.device, cfg.drop)
     sq = _new_slot(q.device)
     sk = sq if packed is not None else _new_slot(q.device)
     sv = _new_slot(q.device)
@@ -1365,10 +1375,10 @@ def attn(q, k, v, cfg):
     return _Attn.apply(q, k, v, cfg)
 
 
-def _fln_bwd(dout, h, mean, rstd, w, b, frames, PF, d, dp, T, sk, psum=None, nparts=0, want_amax=True, skip=None):
+def _fln_bwd(dout, h, mean, rstd, w, b, frames, PF, d, dp, T, sk, psum=None, nparts=0, want_amax=True, skip=NO_SKIP):
     """frame-LN backward (with its own statistics pass, or with the producer's `psum`); parameter gradients into the
     sink (partials reduced on the gradient stream) or returned; want_amax: dh feeds a GEMM (gets an amax slot);
-    skip = (Drop, frames per sample) of the node's DropPath (`psum` form only): the frames of dropped samples are not worked on"""
+    skip: the SampleSkip of the node's DropPath (`psum` form only): the frames of dropped samples are not worked on"""
     L = lib()
     dev = h.device
     dh = torch.empty_like(h)
@@ -1378,17 +1388,15 @@ def _fln_bwd(dout, h, mean, rstd, w, b, frames, PF, d, dp, T, sk, psum=None, npa
     ws, wsn = _ws(L.npvp_frameln_act_bwd_workspace_bytes(frames, PF), dev)
     mode = _sink_mode(sk)
     if psum is None:
-        seed = _S._cur.rng.seed_tensor(dev) if (d.on or dp.on) else None
+        seed = _S._cur.rng.seed_for(dev, d, dp)
         check(L.npvp_frameln_act_bwd(_ptr(dout), _ptr(h), _ptr(mean), _ptr(rstd), _ptr(w), _ptr(b), _ptr(dh), _ptr(dw), _ptr(db),
                                      frames, PF, d.p, d.salt, dp.p, dp.salt, T, _ptr(seed), mode, _ptr(slot), _ptr(ws), wsn,
                                      _stream()), "npvp_frameln_act_bwd")
     else:
-        sd, sT = skip if skip else (NO_DROP, 1)
-        seed = _S._cur.rng.seed_tensor(dev) if sd.on else None
         pe = HbmProbe.begin()
         check(L.npvp_frameln_act_bwd_apply_skip(_ptr(dout), _ptr(h), _ptr(mean), _ptr(rstd), _ptr(w), _ptr(b), _ptr(psum), nparts,
-                                                _ptr(dh), _ptr(dw), _ptr(db), frames, PF, mode, _ptr(slot), _ptr(ws), wsn, sd.p, sd.salt,
-                                                sT, _ptr(seed), _stream()), "npvp_frameln_act_bwd_apply_skip")
+                                                _ptr(dh), _ptr(dw), _ptr(db), frames, PF, mode, _ptr(slot), _ptr(ws), wsn, *skip.frame,
+                                                _ptr(_S._cur.rng.seed_for(dev, skip.frame)), _stream()), "npvp_frameln_act_bwd_apply_skip")
         HbmProbe.end(pe, "npvp::frameln_act_bwd_fused_kernel", 4.0 * 3 * frames * PF)            # reads dout, h; writes dh
     if sk:
         _reduce_partials(sk, ws, dw, db, L.npvp_frameln_act_bwd_reduce, L.npvp_frameln_act_bwd_reduce_job, "npvp_frameln_act_bwd_reduce",
@@ -1405,7 +1413,7 @@ def _fln_pgrad(dout, h, mean, rstd, w, b, frames, PF, d, sk):
     psum = torch.empty(frames * (PF // 1024) * 2, dtype=torch.float32, device=dev)
     dw, db = (sk[0][0], sk[1][0]) if sk else (torch.empty_like(w), torch.empty_like(b))
     ws, wsn = _ws(L.npvp_frameln_act_bwd_workspace_bytes(frames, PF), dev)
-    seed = _S._cur.rng.seed_tensor(dev) if d.on else None
+    seed = _S._cur.rng.seed_for(dev, d)
     check(L.npvp_frameln_act_bwd_pgrad(_ptr(dout), _ptr(h), mean, rstd, _ptr(w), _ptr(b), _ptr(psum), _ptr(dw), _ptr(db),
                                        frames, PF, d.p, d.salt, 0.0, 0, 1, _ptr(seed), _sink_mode(sk), _ptr(ws), wsn, _stream()),
           "npvp_frameln_act_bwd_pgrad")
@@ -1436,7 +1444,7 @@ class _FrameLnAct(torch.autograd.Function):
         DropRecorder.note(d, "elem", h.numel())
         DropRecorder.note(dp, "group", frames // max(1, frames_per_sample))
         out = torch.empty_like(h)
-        seed = _S._cur.rng.seed_tensor(h.device) if (d.on or dp.on) else None
+        seed = _S._cur.rng.seed_for(h.device, d, dp)
         slot = _new_slot(h.device)
         check(L.npvp_frameln_act_fwd(_ptr(h), _ptr(mean), _ptr(rstd), _ptr(w_cl), _ptr(b_cl), _ptr(res_c), _ptr(out), frames,
                                      PF, d.p, d.salt, dp.p, dp.salt, frames_per_sample, _ptr(seed), _ptr(slot), _stream()),
@@ -1527,15 +1535,14 @@ class _MlpDwbn(torch.autograd.Function):
         st = _stream()
         PFh, PFo = 64 * hid, 64 * Co
         d2, d3, dp = Drop(p_drop), Drop(p_drop), Drop(p_dp, 1)
-        # the samples dp drops: frame kernels write zeros for them, GEMM tiles inside them are not computed (DROP_PATH_SKIP)
-        sk = dp if (DROP_PATH_SKIP and dp.on) else NO_DROP
-        rs = Drop._like(dp, 1, T * 64, frames // T) if (sk.on and frames % T == 0) else NO_DROP      # the same samples as token-row groups
-        seed = _S._cur.rng.seed_tensor(dev) if (d2.on or dp.on) else None
+        # the samples dp drops: frame kernels write zeros for them, GEMM tiles inside them are not computed (DROP_PATH_SKIP) - taken in
+        # forward: backward leaves out what forward left out
+        ctx.skip = skip = SampleSkip.of(skip_roles("mlpdwbn", DROP_PATH_SKIP, WGRAD_ROW_SKIP), dp, T * 64, frames // max(1, T), R)
+        seed = _S._cur.rng.seed_for(dev, d2, dp)
         # fc1 (+ frame statistics of h1)
         h1 = torch.empty(R, hid, dtype=f32, device=dev)
         part = torch.empty(frames * (hid // 64) * 2, dtype=f32, device=dev)
-        gemm(1, 1, R, hid, C, x, x.stride(0), w1, w1.stride(0), h1, bias=b1, b_pre=_planes(w1, "F", R),
-             rowstats=part, row_skip=rs)
+        gemm(1, 1, R, hid, C, x, x.stride(0), w1, w1.stride(0), h1, bias=b1, b_pre=_planes(w1, "F", R), rowstats=part, row_skip=skip.forward)
         stats = torch.empty(6, frames, dtype=f32, device=dev)               # mean1, rstd1, mean2, rstd2, mean3, rstd3
         # (no statistics launches: each consumer below merges the partial (mean, M2) pairs its producer left and writes
         # mean / rstd into `stats` for backward)
@@ -1553,29 +1560,27 @@ class _MlpDwbn(torch.autograd.Function):
         h2 = torch.empty(R, hid, dtype=f32, device=dev)
         part2 = torch.empty(frames * (hid // 512) * 2, dtype=f32, device=dev)
         check(L.npvp_mlpdw_mid_fwd_parts_skip(_ptr(h1), _ptr(part), hid // 64, 4096.0, _row(stats, 0), _row(stats, 1), _ptr(n1w),
-                                              _ptr(n1b), _ptr(wtb), _row(wtb, 9), _ptr(h2), _ptr(part2), frames, 8, 8, hid, 1e-5, sk.p,
-                                              sk.salt, T, _ptr(seed), st), "npvp_mlpdw_mid_fwd_parts_skip")
+                                              _ptr(n1b), _ptr(wtb), _row(wtb, 9), _ptr(h2), _ptr(part2), frames, 8, 8, hid, 1e-5,
+                                              *skip.frame, _ptr(seed), st), "npvp_mlpdw_mid_fwd_parts_skip")
         DropRecorder.note(d2, "elem", R * hid)
         a2 = torch.empty(R, hid, dtype=f32, device=dev)
         a2_slot = _new_slot(dev)
         check(L.npvp_frameln_act_fwd_parts_skip(_ptr(h2), _ptr(part2), hid // 512, 32768.0, 1e-5, _row(stats, 2), _row(stats, 3),
                                                 _ptr(n2w), _ptr(n2b), None, _ptr(a2), frames, PFh, d2.p, d2.salt, 0.0, 0, 1, _ptr(seed),
-                                                _ptr(a2_slot), sk.p, sk.salt, T, st), "npvp_frameln_act_fwd_parts_skip")
+                                                _ptr(a2_slot), *skip.frame, st), "npvp_frameln_act_fwd_parts_skip")
         tag_amax(a2, a2_slot)
         # fc2 (+ statistics), norm3 + GELU + dropout + residual + drop-path
         h3 = torch.empty(R, Co, dtype=f32, device=dev)
         part3 = torch.empty(frames * (Co // 64) * 2, dtype=f32, device=dev)
-        gemm(1, 1, R, Co, hid, a2, hid, w2, w2.stride(0), h3, bias=b2, b_pre=_planes(w2, "F", R),
-             rowstats=part3, row_skip=rs)
+        gemm(1, 1, R, Co, hid, a2, hid, w2, w2.stride(0), h3, bias=b2, b_pre=_planes(w2, "F", R), rowstats=part3, row_skip=skip.forward)
         DropRecorder.note(d3, "elem", R * Co)
         DropRecorder.note(dp, "group", frames // max(1, T))
         out = torch.empty(R, Co, dtype=f32, device=dev)
         check(L.npvp_frameln_act_fwd_parts_skip(_ptr(h3), _ptr(part3), Co // 64, 4096.0, 1e-5, _row(stats, 4), _row(stats, 5),
                                                 _ptr(n3w), _ptr(n3b), _ptr(res), _ptr(out), frames, PFo, d3.p, d3.salt, dp.p, dp.salt, T,
-                                                _ptr(seed), None, sk.p, sk.salt, T, st), "npvp_frameln_act_fwd_parts_skip")
+                                                _ptr(seed), None, *skip.frame, st), "npvp_frameln_act_fwd_parts_skip")
         ctx.save_for_backward(x, h1, h2, a2, h3, stats, wtb, w1, w2, n1w, n1b, n2w, n2b, n3w, n3b)
         ctx.cfg = (frames, T, d2, d3, dp, res is not None, b1 is not None, b2 is not None)
-        ctx.skip = (sk, T, rs) if sk.on else None          # (taken in forward: backward leaves out what forward left out)
         ctx.sinks = (_wb_sink(w1, b1), _wb_sink(w2, b2), _ln_sink(n1w, n1b), _ln_sink(n2w, n2b), _ln_sink(n3w, n3b))
         sd = _wb_sink(dww, dwb) if (dww.is_contiguous() and dwb is not None) else None
         ctx.sink_dw = sd if (sd and sd[1] is not None) else None
@@ -1590,11 +1595,9 @@ class _MlpDwbn(torch.autograd.Function):
         R, hid = h1.shape
         Co = h3.shape[1]
         dev = x.device
-        sk, sT, rs = ctx.skip if ctx.skip else (NO_DROP, 1, NO_DROP)
-        skip = (sk, sT) if sk.on else None
         dout = _c(dout)
         dh3, gn3w, gn3b = _fln_bwd(dout, h3, stats[4], stats[5], n3w, n3b, frames, 64 * Co, d3, dp, T, s_n3)
-        da2, gw2, gb2 = linear_bwd(dh3, a2, w2, True if has_b2 else None, s_fc2, row_skip=rs)     # (`b` only says whether there is a bias gradient to take)
+        da2, gw2, gb2 = linear_bwd(dh3, a2, w2, True if has_b2 else None, s_fc2, skip=ctx.skip)     # (`b` only says whether there is a bias gradient to take)
         fuse_n2 = MID_BWD_N2 and hid // 16 <= 256
         if fuse_n2:
             # norm2's backward WITHOUT its input gradient: frame sums (partials) + parameter gradients in one pass over da2 / h2;
@@ -1613,7 +1616,7 @@ class _MlpDwbn(torch.autograd.Function):
         sk_dw = ctx.sink_dw if ctx.needs_input_grad[6] and ctx.needs_input_grad[7] else None
         wmode = 2 if sk_dw else 0          # 2: the depthwise gradient partials stay in `ws` for the gradient stream (below)
         if fuse_n2:
-            seed = _S._cur.rng.seed_tensor(dev) if d2.on else None
+            seed = _S._cur.rng.seed_for(dev, d2)
             pe = HbmProbe.begin()
             check(L.npvp_mlpdw_mid_bwd_n2(_ptr(da2), _ptr(h2), _row(stats, 2), _row(stats, 3), _ptr(n2w), _ptr(n2b), _ptr(psum2),
                                           hid // 16, d2.p, d2.salt, _ptr(seed), _ptr(h1), _row(stats, 0), _row(stats, 1), _ptr(n1w),
@@ -1637,9 +1640,9 @@ class _MlpDwbn(torch.autograd.Function):
             check(L.npvp_transpose(_ptr(dwtb), _ptr(gdww), 1, 9, hid, _stream()), "npvp_transpose")
             gdwb = dwtb[9]
         dh1, gn1w, gn1b = _fln_bwd(da1, h1, stats[0], stats[1], n1w, n1b, frames, 64 * hid, NO_DROP, NO_DROP, 1, s_n1,
-                                      psum=psum, nparts=nparts, skip=skip)
+                                      psum=psum, nparts=nparts, skip=ctx.skip)
         del da1
-        dx, gw1, gb1 = linear_bwd(dh1, x, w1, True if has_b1 else None, s_fc1, row_skip=rs)
+        dx, gw1, gb1 = linear_bwd(dh1, x, w1, True if has_b1 else None, s_fc1, skip=ctx.skip)
         return (dx, dout if has_res else None, gw1, gb1, gn1w, gn1b, gdww, gdwb, gn2w, gn2b, gw2, gb2, gn3w, gn3b,
                 None, None, None, None)
 
@@ -1915,11 +1918,11 @@ class _SelfAttnSublayer(torch.autograd.Function):
         C = x2.shape[1]
         dy2 = _c(dy).reshape(-1, C)
         dz, ad = masked_grad(dy2, drop, wo)
-        # a per-sample DropPath (the spatial site) leaves dz - masked here or inside the GEMMs -, hence do, dqk and dv (attention
-        # stays inside a sample) zero in the rows of dropped samples: the three weight gradients leave them out (WGRAD_ROW_SKIP).
-        # The tiling route only: the centre-pad route's projections run on padded rows, where the samples are no row groups
-        rs = drop if (drop.on and drop.mode == 1 and cfg.tiles and drop.g1 * drop.g2 == dy2.shape[0]) else NO_DROP
-        do, gwo, gbo = linear_bwd(dz, o, wo, bo, s_o, a_drop=ad, wgrad_skip=rs)
+        # a per-sample DropPath (the spatial site) leaves dz - masked here or inside the GEMMs -, hence do, dqk and dv (attention stays inside a
+        # sample) zero in the rows of dropped samples: the three weight gradients leave them out (WGRAD_ROW_SKIP).  The tiling route only: the
+        # centre-pad route's projections run on padded rows, where the samples are no row groups
+        skip = SampleSkip.of(skip_roles("self_attn", DROP_PATH_SKIP, WGRAD_ROW_SKIP), drop, drop.g1, drop.g2, dy2.shape[0]) if cfg.tiles else NO_SKIP
+        do, gwo, gbo = linear_bwd(dz, o, wo, bo, s_o, a_drop=ad, skip=skip)
         if not cfg.tiles:
             do = _raw_grid_pad(do, cfg, want_amax=False)            # the pad queries' outputs were cut away: their gradient is 0
         dqk, dv = torch.empty_like(qk), torch.empty_like(v)
@@ -1928,13 +1931,13 @@ class _SelfAttnSublayer(torch.autograd.Function):
             _zero_tail(cfg, dqk, dv)
         # (centre-pad route: `fused` holds the padded rows, see forward - the bias gradients sum the pad rows too, they are keys of
         # their windows, and the weight gradients see their zero rows)
-        dfused, gwqk, gbqk = linear_bwd(dqk, fused, wqk, bqk, s_qk, wgrad_skip=rs)
+        dfused, gwqk, gbqk = linear_bwd(dqk, fused, wqk, bqk, s_qk, skip=skip)
         if not cfg.tiles:
             dfused = _raw_grid_cut(dfused, cfg)
         du, dadd, dbeta, dgamma = _raw_posfuse_bwd(dfused, x1, add, beta_shape, gamma, pst, N, T, ctx.needs_input_grad[6], ctx.act_sinks)
         if cfg.tiles:
             # dx1 = dv Wv + du: the second consumer's gradient rides in as the dgrad GEMM's residual input (no separate add)
-            dx1, gwv, gbv = linear_bwd(dv, x1, wv, bv, s_v, residual=du, wgrad_skip=rs)
+            dx1, gwv, gbv = linear_bwd(dv, x1, wv, bv, s_v, residual=du, skip=skip)
         else:
             dx1, gwv, gbv = linear_bwd(dv, _raw_grid_pad(x1, cfg), wv, bv, s_v)
             dx1 = _raw_grid_cut(dx1, cfg, addend=du)                # ... here the shapes differ: du rides in as the cut's addend

@@ -259,6 +259,10 @@ class RngState:
             self.seed = torch.full((1,), 0x9E3779B97F4A7C15 & 0x7FFFFFFFFFFFFFFF, dtype=torch.int64, device=dev)
         return self.seed
 
+    def seed_for(self, dev, a, b=None, c=None):
+        """the device seed for a launch in which one of these sites (ops.Drop, ops.FrameSkip) is on, else None"""
+        return self.seed_tensor(dev) if (a.p > 0.0 or (b is not None and b.p > 0.0) or (c is not None and c.p > 0.0)) else None
+
     def manual_seed(self, s, dev):
         self.seed_tensor(dev).fill_(int(s) & 0x7FFFFFFFFFFFFFFF)
         self.salt = 0
@@ -595,11 +599,8 @@ class WgradChainState:
     a weight gradient accumulated in place on the gradient stream leaves its `splits` partial slabs in a workspace and a 64-byte
     job; the NEXT weight-gradient launch on that stream does the sum with extra workgroups (no launch of its own: 110 of the 170
     reduction launches of an 8-clip step; HBM-bound work beside MFMA-bound work), WgradStream.join() runs the last one.  Same
-    summation order as the stand-alone reduction, so results are bit-identical.  `enabled = False`: one reduction launch each.
-    `row_skip`: set by ops.linear_wgrad around launch() - the row groups of a DropPath site in which dy is zero; the launch then goes
-    through npvp_wgrad_f16_chained_skip, which leaves their K-steps out (the arguments of launch() stay what they are)."""
+    summation order as the stand-alone reduction, so results are bit-identical.  `enabled = False`: one reduction launch each."""
     enabled = True
-    row_skip = None
 
     def __init__(self, ctx):
         self.ctx = ctx
@@ -631,23 +632,18 @@ class WgradChainState:
         if not self.ctx.wgrad.in_flush:
             self.ctx.reduce.arm()
 
-    def launch(self, dy, x, dw, db, dy_amax, x_amax, a_drop, flag):
-        """dw (+)= dy^T x, db (+)= colsum(dy), both ACCUMULATED (GradSink slices), reduction deferred"""
+    def launch(self, dy, x, dw, db, dy_amax, x_amax, a_drop, flag, row_skip):
+        """dw (+)= dy^T x, db (+)= colsum(dy), both ACCUMULATED (GradSink slices), reduction deferred; row_skip: see ops.linear_wgrad"""
         R, N = dy.shape
         K = x.shape[1]
         st = _stream()
         ws, wsn = _ws(self.workspace_bytes(N, K, R), dy.device)
         job_addr, prev_addr = self.job_slot(st)
-        rs = self.row_skip if (self.row_skip is not None and self.row_skip.on) else None
-        seed = self.ctx.rng.seed_tensor(dy.device) if (a_drop.on or rs is not None) else None
         pe = GemmProbe.begin(6)
-        head = (N, K, R, _ptr(dy), dy.stride(0), _ptr(x), x.stride(0), _ptr(dw), dw.stride(0), _ptr(db), 1, _ptr(dy_amax), _ptr(x_amax),
-                _ptr(flag), a_drop.p, a_drop.g1, a_drop.g2, a_drop.salt)
-        tail = (_ptr(seed), prev_addr, job_addr, _ptr(ws), wsn, st)
-        if rs is not None:
-            check(lib().npvp_wgrad_f16_chained_skip(*head, rs.p, rs.g1, rs.g2, rs.salt, *tail), "npvp_wgrad_f16_chained_skip")
-        else:
-            check(lib().npvp_wgrad_f16_chained(*head, *tail), "npvp_wgrad_f16_chained")
+        check(lib().npvp_wgrad_f16_chained_skip(
+            N, K, R, _ptr(dy), dy.stride(0), _ptr(x), x.stride(0), _ptr(dw), dw.stride(0), _ptr(db), 1, _ptr(dy_amax), _ptr(x_amax),
+            _ptr(flag), a_drop.p, a_drop.g1, a_drop.g2, a_drop.salt, row_skip.p, row_skip.g1, row_skip.g2, row_skip.salt,
+            _ptr(self.ctx.rng.seed_for(dy.device, a_drop, row_skip)), prev_addr, job_addr, _ptr(ws), wsn, st), "npvp_wgrad_f16_chained_skip")
         GemmProbe.end(pe, 2.0 * N * K * R, 4.0 * (N * R + K * R + N * K), (0, 0), 6)
         self.job_added(st, None, (ws, dw, db), None)
 

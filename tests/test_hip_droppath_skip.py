@@ -201,7 +201,7 @@ def test_captured_step_with_drop_path_equals_eager():
 
 
 # ------------------------------------------------------------------------------------------------ the GEMMs, through npvp_gemm_f32_skip
-# ops.gemm(row_skip=...) launches npvp_gemm_f32_skip; ops.linear_bwd(row_skip=...) npvp_linear_bwd_f16_skip where the fused launch
+# ops.gemm(row_skip=...) launches npvp_gemm_f32_skip; ops.linear_bwd(skip=...) npvp_linear_bwd_f16_skip where the fused launch
 # takes the shape.  M = 4 row groups of g1 rows: 64 (two groups per 128-row tile), 128 (a group is a tile) and 192 (tiles that
 # straddle two groups); tiles are 64 or 128 rows high, so a 128-aligned block of 128 dropped rows lies in skipped tiles whatever the
 # variant.
@@ -353,14 +353,15 @@ def test_fused_linear_backward_with_skip_is_bit_equal(K, R, g1):
         for rs in (K.NO_DROP, site):
             fb.flat_g.zero_()
             calls = []
-            name = "npvp_linear_bwd_f16_skip" if rs.on else "npvp_linear_bwd_f16"
+            name = "npvp_linear_bwd_f16_skip"                      # (the one entry point of the fused launch; its skip words: a[31:35])
             real = getattr(K.lib(), name)
-            setattr(K.lib(), name, lambda *a: (calls.append(1), real(*a))[1])
+            setattr(K.lib(), name, lambda *a: (calls.append(a[31:35]), real(*a))[1])
             try:
-                dx, gw, gb = K.linear_bwd(dy, x, w, b, sk, row_skip=rs)
+                dx, gw, gb = K.linear_bwd(dy, x, w, b, sk, skip=K.SampleSkip.of(K.skip_roles("mlpdwbn", True, True), rs, g1, groups, R))
             finally:
                 setattr(K.lib(), name, real)
             assert len(calls) == 1 and gw is None and gb is None, "the fused entry point was not the one launched"
+            assert calls[0] == (site.p, site.g1, site.g2, site.salt) if rs.on else calls[0][0] == 0, calls
             K.ReduceQueue.finish()
             torch.cuda.synchronize()
             outs.append((dx.clone(), w.grad.clone(), b.grad.clone()))

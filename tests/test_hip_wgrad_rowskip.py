@@ -11,6 +11,7 @@ found fails.
 
 The bound is measured, not fixed: the entry point WITHOUT the skip against fp64 on the same inputs, in the same test; the skip form
 may exceed that error by a factor 2 - the margin of another split-K order, nothing else differs."""
+import collections
 import ctypes
 import functools
 
@@ -222,14 +223,15 @@ def test_fused_linear_backward_hands_the_skip_to_its_weight_gradient(K):
         for rs in (K.NO_DROP, site):
             fb.flat_g.zero_()
             calls = []
-            name = "npvp_linear_bwd_f16_skip" if rs.on else "npvp_linear_bwd_f16"
+            name = "npvp_linear_bwd_f16_skip"                      # (the one entry point of the fused launch; its skip words: a[31:35])
             real = getattr(K.lib(), name)
-            setattr(K.lib(), name, lambda *a: (calls.append(1), real(*a))[1])
+            setattr(K.lib(), name, lambda *a: (calls.append(a[31:35]), real(*a))[1])
             try:
-                dx, gw, gb = K.linear_bwd(dy, x, w, b, sk, row_skip=rs)
+                dx, gw, gb = K.linear_bwd(dy, x, w, b, sk, skip=K.SampleSkip.of(K.skip_roles("mlpdwbn", True, True), rs, g1, g2, R))
             finally:
                 setattr(K.lib(), name, real)
             assert len(calls) == 1 and gw is None and gb is None, "the fused entry point was not the one launched"
+            assert calls[0] == (site.p, site.g1, site.g2, site.salt) if rs.on else calls[0][0] == 0, calls
             K.ReduceQueue.finish()
             torch.cuda.synchronize()
             outs.append((dx.clone(), w.grad.clone(), b.grad.clone()))
@@ -265,14 +267,26 @@ def _plain_error():
     return _err(w, dy.double().T @ x.double())
 
 
-def _block_run(impl, m, fb, x, beta, cot, seed, on):
+# entry point -> (index of its four skip words p, g1, g2, salt; operand orientation (a_kc, b_kc): (1, 1) forward, (1, 0) dgrad - the fused
+# launch counts as one -, (0, 0) weight gradient)
+CHAINED, GEMM, FUSED = "npvp_wgrad_f16_chained_skip", "npvp_gemm_f32_skip", "npvp_linear_bwd_f16_skip"
+RECORDED = {CHAINED: (18, lambda a: (0, 0)), GEMM: (37, lambda a: tuple(a[0:2])), FUSED: (31, lambda a: (1, 0))}
+
+
+def _block_run(impl, m, fb, x, beta, cot, seed, on, single_stream_fused=False):
+    """-> parameter gradients, the two sites' keep flags, [(entry point, orientation, skip words)] of every recorded launch.
+    single_stream_fused: without the gradient stream and with the fused dgrad + weight-gradient launch on, instead of the schedule in force"""
     K = impl.ops
     dev = torch.device(DEV)
     calls = []
-    real = K.lib().npvp_wgrad_f16_chained_skip
-    keep = K.WGRAD_ROW_SKIP
+    real = {name: getattr(K.lib(), name) for name in RECORDED}
+    keep = (K.WGRAD_ROW_SKIP, K.WgradStream.enabled, K.FusedLinearBwd.enabled)
+    K.WgradStream.join()
     K.WGRAD_ROW_SKIP = on
-    setattr(K.lib(), "npvp_wgrad_f16_chained_skip", lambda *a: (calls.append(a[18:22]), real(*a))[1])
+    if single_stream_fused:
+        K.WgradStream.enabled, K.FusedLinearBwd.enabled = False, True
+    for name, (at, orient) in RECORDED.items():
+        setattr(K.lib(), name, lambda *a, name=name, at=at, orient=orient: (calls.append((name, orient(a), a[at:at + 4])), real[name](*a))[1])
     try:
         fb.flat_g.zero_()
         K.rng.manual_seed(seed, dev)
@@ -288,9 +302,39 @@ def _block_run(impl, m, fb, x, beta, cot, seed, on):
         torch.cuda.synchronize()
     finally:
         K.DropRecorder.sites = None
-        K.WGRAD_ROW_SKIP = keep
-        setattr(K.lib(), "npvp_wgrad_f16_chained_skip", real)
+        K.WGRAD_ROW_SKIP, K.WgradStream.enabled, K.FusedLinearBwd.enabled = keep
+        for name in RECORDED:
+            setattr(K.lib(), name, real[name])
     return {n: p.grad.detach().clone() for n, p in m.named_parameters()}, masks, calls
+
+
+def _with_spec(calls):
+    """the recorded launches whose skip words are on (p > 0)"""
+    return [c for c in calls if c[2][0] > 0]
+
+
+def _layers(m):
+    """(node, N out, K in) of the block's five linear layers, in backward order"""
+    hid, C = m.SpatialFFN.fc1.weight.shape[:2]
+    return [("self_attn", C, C), ("self_attn", 2 * C, C), ("self_attn", C, C), ("mlpdwbn", C, hid), ("mlpdwbn", hid, C)]
+
+
+def _expected_launches(K, m, R, on, single_stream_fused):
+    """how many launches carry a spec, per (entry point, orientation): ops.skip_roles for the block's five linear layers - out-proj, q|k, v
+    of the spatial self-attention, fc2, fc1 of the MlpDWBN - under DROP_PATH_SKIP on and WGRAD_ROW_SKIP = `on`.  The fused launch
+    where FusedLinearBwd takes the layer in the single-stream schedule, else a dgrad GEMM and a chained weight gradient"""
+    assert K.DROP_PATH_SKIP
+    want = collections.Counter()
+    for node, N, Kin in _layers(m):
+        assert K.WgradChain.takes(N, Kin, R), (N, Kin, R)
+        roles = K.skip_roles(node, True, on)
+        want[(GEMM, (1, 1))] += int(roles.forward)
+        if single_stream_fused and K.FusedLinearBwd.takes(R, N, Kin):
+            want[(FUSED, (1, 0))] += int(roles.fused)
+        else:
+            want[(GEMM, (1, 0))] += int(roles.dgrad)
+            want[(CHAINED, (0, 0))] += int(roles.wgrad)
+    return +want
 
 
 @pytest.mark.parametrize("T", [2, 4])
@@ -334,13 +378,26 @@ def test_nodes_with_the_switch_off_and_on(K, T):
     seen = set()
     for want, seed in picked.items():
         off, masks, calls0 = _block_run(impl, m, fb, x, beta, cot, seed, False)
-        assert len(masks) == 2 and all(len(k) == N for k in masks) and not calls0
+        assert len(masks) == 2 and all(len(k) == N for k in masks)
+        assert not [c for c in _with_spec(calls0) if c[0] == CHAINED], calls0           # switch off: no chained launch carries a spec
         full = [all(k) for k in masks]
         assert tuple(full) == want
         seen.add(tuple(full))
-        on, masks1, calls = _block_run(impl, m, fb, x, beta, cot, seed, True)
+        on, masks1, calls1 = _block_run(impl, m, fb, x, beta, cot, seed, True)
         assert masks1 == masks
+        calls = [c[2] for c in _with_spec(calls1) if c[0] == CHAINED]
         assert len(calls) == 5 and all(c[1:3] == (T * 64, N) for c in calls), calls      # out-proj, q|k, v, fc2, fc1 carry the spec
+        # every launch that carries a spec, per entry point and orientation, is the one ops.skip_roles names - in the schedule in
+        # force and, at T = 4, single-stream with the fused launch on; every spec is the site's as groups of one sample's rows
+        R = N * T * 64
+        runs = [(False, False, calls0), (True, False, calls1)]
+        if T == 4:
+            runs += [(flag, True, _block_run(impl, m, fb, x, beta, cot, seed, flag, single_stream_fused=True)[2]) for flag in (False, True)]
+        for flag, fused, rec in runs:
+            got = collections.Counter(c[:2] for c in _with_spec(rec))
+            assert got == _expected_launches(K, m, R, flag, fused), (T, flag, fused, got)
+            assert all(c[2][1:3] == (T * 64, N) for c in _with_spec(rec)), rec
+            assert any(c[0] == FUSED for c in rec) == fused, (T, flag, fused)         # (the schedule asked for is the one that ran)
         for name in off:
             e = _err(on[name], off[name].double())
             touched = name in SKIP_PARAMS and not full[0 if name.startswith("SLMHSA") else 1]

@@ -36,7 +36,7 @@ QUERIES = {"npvp_gemm_kernel_id", "npvp_gemm_workspace_bytes", "npvp_linear_bwd_
 # the knobs of the linear backward, beside (gradient stream, ReduceQueue) of MODES: fused beside a gradient stream, chain, range guard
 LINEAR_MODES = {"fused": dict(with_gradient_stream=True), "nochain": dict(chain=False), "strict": dict(strict=True),
                 "fallback": dict(fallback=True)}
-LINEAR_CALLS = ("npvp_linear_bwd_f16", "npvp_wgrad_f16_chained", "npvp_splitk_reduce_job", "npvp_splitk_reduce_multi")
+LINEAR_CALLS = ("npvp_linear_bwd_f16_skip", "npvp_wgrad_f16_chained_skip", "npvp_splitk_reduce_job", "npvp_splitk_reduce_multi")    # (the glue's one call per launch site)
 
 
 def install():
