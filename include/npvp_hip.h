@@ -504,6 +504,20 @@ int npvp_grid_center_pad(const float* src, long long ld_src, float* dst, long lo
                          int left, int C, long long rows_out, float* dst_amax, npvp_stream_t stream);
 int npvp_grid_center_cut(const float* src, long long ld_src, const float* addend, long long ld_add, float* dst, long long ld_dst, int F,
                          int H, int W, int Hp, int Wp, int top, int left, int C, float* dst_amax, npvp_stream_t stream);
+/* The learned event token of the encoder, on token rows [N][T][P][C] with row strides ld_* (floats).  C % 4 == 0, strides % 4 == 0 and
+ * >= C, buffers 16-byte aligned, N*(T+1)*P below 2^31.  Plain copies: bit-reproducible; every output element is written exactly once.
+ *   join (ref/models/VidHRFormer.py:36 the token appended as frame T+1 of every clip, :40-41 the positional tables given a zero frame):
+ *        y [N, T+1, P, C]: y[n, t < T] = x[n, t], y[n, T] = token.  token_clip_stride (floats) = 0: ONE [P, C] block for all clips (the
+ *        parameter EVT); > 0: one block per clip, clip n at token + n * token_clip_stride; token = NULL: zeros (a table's zero frame
+ *        with N = 1).  x = NULL: zeros too (the backward of a split whose first output had no gradient).
+ *   split (ref/models/Predictor.py:344  x[:, 0:-1], x[:, -1]): y [N, T+1, P, C] -> x [N, T, P, C] and / or last [N, P, C]; either output
+ *        may be NULL (not both), and only the rows of a wanted output are read.
+ * Each is the other's adjoint; the gradient of a token shared by the clips is npvp_reduce_mid(A = 1, B = N) of the split's `last`.
+ * *_amax (nullable): the amax slot of that output. */
+int npvp_evt_token_join(const float* x, long long ld_x, const float* token, long long ld_token, long long token_clip_stride, float* y,
+                        long long ld_y, int N, int T, int P, int C, float* y_amax, npvp_stream_t stream);
+int npvp_evt_token_split(const float* y, long long ld_y, float* x, long long ld_x, float* last, long long ld_last, int N, int T, int P,
+                         int C, float* x_amax, float* last_amax, npvp_stream_t stream);
 
 /* out[n] = sum_r x[r][n]: bias gradients of every Linear / Conv2d on the path */
 long long npvp_colsum_workspace_bytes(long long rows, int N);

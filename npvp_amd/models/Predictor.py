@@ -1,7 +1,7 @@
 """HIP-backed NP predictor: drop-in for ref/models/Predictor.py:265-359 (`Predictor`).  Same
 constructor signature, attributes (`stochastic`, `TP`, `observed_coor`, `predict_coor`, `nrmlp`, `fuser`,
-`EVT_Former`, `evt_posterior`, `evt_prior`, `transformer`), methods and the 603 state-dict keys,
-so reference checkpoints load with load_state_dict and LitPredictor-style callers keep working.
+`EVT_Former`, `evt_posterior`, `evt_prior`, `transformer`), methods and the 603 state-dict keys (604 with learn_evt_token=True:
+`EVT_Former.EVT`), so reference checkpoints load with load_state_dict and LitPredictor-style callers keep working.
 """
 import torch
 import torch.nn as nn
@@ -22,8 +22,11 @@ class Predictor(nn.Module):
             # the reference's default argument is ONE nn.LayerNorm(512) instance shared by the encoder and
             # the decoder (ref Predictor.py:270,290-291,299): a single tied weight under two state-dict keys
             norm = nn.LayerNorm(512)
-        if not evt_former or learn_evt_token:
-            raise NotImplementedError("evt_former=False / learn_evt_token=True are outside the hot path")
+        if not evt_former:
+            raise NotImplementedError("evt_former=False is not built: the reference's branch (ref/models/Predictor.py:348) feeds the "
+                                      "fuser an (N,T,W,C,H) permutation of the features, which only runs because H = W = 8 reshapes "
+                                      "without error; it normalises over whole frames and indexes the positional tables scrambled, "
+                                      "so it defines nothing worth restating.  Use evt_former=True (with or without learn_evt_token)")
         self.stochastic, self.evt_former = stochastic, evt_former
         self.h_list, self.w_list = h_list, w_list
         self.max_H, self.max_W = max_H, max_W
@@ -60,11 +63,15 @@ class Predictor(nn.Module):
         return (ops.fan_out(beta), ops.fan_out(gamma) if self.nrmlp.fuse_method == 'SPADE' else None)
 
     # -- helpers on the canonical layout -------------------------------------------------------------
-    def _encode(self, feats, pos):
-        """(N,T,C,H,W) features -> canonical encoder output (N,T,H,W,C) and event coding [N, H*W, C] (mean over T)."""
+    def _encode(self, feats, pos, memory=True):
+        """(N,T,C,H,W) features -> canonical encoder output (N,T,H,W,C) and event coding [N, H*W, C]: the mean over T, or with the
+        learned event token the encoder's last output frame, the first T being the memory (ref :343-346).  memory=False: the caller
+        uses the event coding alone (the target pass); with the token the memory is then not produced (an empty tensor)."""
         N, T, C, H, W = feats.shape
         x = ops.nchw_to_canonical(feats).view(N, T, H, W, C)
         x = self.EVT_Former.forward_canonical(x, pos, self.fuser)
+        if self.EVT_Former.evt_token:
+            return ops.evt_token_split(x, memory)                                       # ref :344
         evt = ops.mean_mid(x.view(N, T, H * W * C)).view(N, H * W, C)                  # ref :346
         return x, evt
 
@@ -93,7 +100,7 @@ class Predictor(nn.Module):
             ops.AuxStream.active = True
             try:
                 with torch.cuda.stream(aux):
-                    _, pred_evt = self._encode(predict_features_gt, pp)
+                    _, pred_evt = self._encode(predict_features_gt, pp, memory=False)
                     zp, mu_p, logvar_p = self.evt_posterior.forward_canonical(pred_evt, H, W)
                 for t in (predict_features_gt, pp[0]) + ((pp[1],) if pp[1] is not None else ()):
                     t.record_stream(aux)
@@ -110,7 +117,7 @@ class Predictor(nn.Module):
             if not dual:
                 zo, mu_o, logvar_o = self.evt_prior.forward_canonical(obs_evt, H, W)
                 if predict_features_gt is not None:
-                    _, pred_evt = self._encode(predict_features_gt, pp)
+                    _, pred_evt = self._encode(predict_features_gt, pp, memory=False)
                     zp, mu_p, logvar_p = self.evt_posterior.forward_canonical(pred_evt, H, W)
             if self.training:
                 assert predict_features_gt is not None, \

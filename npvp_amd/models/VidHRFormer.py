@@ -304,19 +304,31 @@ class VidHRFormerBlockEnc(nn.Module):
 
 
 class VidHRFormerEncoder(nn.Module):
-    """ref/models/VidHRFormer.py:11-52 (evt_token=False path, ref/models/Predictor.py:46)."""
+    """ref/models/VidHRFormer.py:11-52.  evt_token=True (ref :22-23, :35-42): the learned parameter EVT (1,H,W,C) is appended to every
+    clip as frame T+1, with zero positional rows for that frame; the layers and the shared norm run on T+1 frames.  The temporal mask
+    of the blocks (ref :99-102: no query but the last sees the last key) is this token's mask: the frames never see the token, the
+    token sees every frame."""
 
     def __init__(self, num_layers, enc_H, enc_W, d_model, num_heads, window_size=7, dropout=0., drop_path=0.,
                  Spatial_FFN_hidden_ratio=4, dim_feedforward=1024, norm=None, evt_token=False):
         super().__init__()
-        if evt_token:
-            raise NotImplementedError("learn_evt_token is outside the hot path (the reference always passes False)")
         self.layers = _get_clones(VidHRFormerBlockEnc(enc_H, enc_W, d_model, num_heads, window_size, dropout, drop_path,
                                                       Spatial_FFN_hidden_ratio, dim_feedforward), num_layers)
         self.num_layers, self.norm, self.evt_token = num_layers, norm, evt_token
+        if self.evt_token:
+            self.EVT = nn.Parameter(torch.randn(1, enc_H, enc_W, d_model), requires_grad=True)          # ref :23
 
     def forward_canonical(self, x, memory_pos, pos_fuser):
-        """x: (N,T,H,W,C) canonical -> (N,T,H,W,C) canonical (after the shared final LayerNorm)."""
+        """x: (N,T,H,W,C) canonical -> (N,T,H,W,C) canonical (after the shared final LayerNorm); with the event token (N,T+1,H,W,C),
+        frame T being the token's."""
+        if self.evt_token:
+            N, T, H, W, C = x.shape
+            if N * (T + 1) * H * W % 32:
+                raise ValueError(f"VidHRFormerEncoder(evt_token=True): the residual stream has N*(T+1)*H*W = {N}*{T + 1}*{H}*{W} token "
+                                 "rows, and the weight-gradient GEMMs sum over them in steps of 32: N*(T+1)*H*W % 32 must be 0")
+            x = ops.evt_token_join(x, self.EVT)                                                          # ref :36
+            beta, gamma = memory_pos
+            memory_pos = (ops.evt_pad_table(beta, T), ops.evt_pad_table(gamma, T))                       # ref :39-42
         for layer in self.layers:
             x = layer(x, memory_pos, pos_fuser)
         if self.norm is not None:
@@ -324,11 +336,11 @@ class VidHRFormerEncoder(nn.Module):
         return x
 
     def forward(self, src, memory_pos, pos_fuser):
-        """src: (N,T,C,H,W) -> (N,T,C,H,W)   (reference signature)"""
+        """src: (N,T,C,H,W) -> (N,T,C,H,W), or (N,T+1,C,H,W) with the event token   (reference signature)"""
         N, T, C, H, W = src.shape
         x = ops.nchw_to_canonical(src).view(N, T, H, W, C)
         x = self.forward_canonical(x, memory_pos, pos_fuser)
-        return ops.canonical_to_nchw(x, N, T, H, W)
+        return ops.canonical_to_nchw(x, N, x.shape[1], H, W)
 
 
 class VidHRFormerBlockDecNAR(nn.Module):

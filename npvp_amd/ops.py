@@ -1848,6 +1848,119 @@ def grid_cut(xp, cfg):
     return _GridCut.apply(xp, cfg)
 
 
+# The learned event token of the encoder (ref/models/VidHRFormer.py:35-42, ref/models/Predictor.py:343-344): the token is appended to
+# every clip as frame T+1, the positional tables get a zero frame, and the encoder's output is split into the memory (the first T
+# frames) and the event coding (the last).  _raw_evt_join / _raw_evt_split are THE call sites of npvp_evt_token_join / _split; each
+# is the other's backward.
+def _raw_evt_join(x2, token, N, T, P, C, dev, want_amax=True):
+    """x2 [N*T*P, C] (None: zeros) + token ([P, C] for all clips, [N*P, C] one per clip, None: zeros) -> [N*(T+1)*P, C]"""
+    per_clip = token is not None and token.shape[0] != P
+    if ((x2 is not None and (tuple(x2.shape) != (N * T * P, C) or x2.stride(1) != 1))
+            or (token is not None and (tuple(token.shape) != ((N if per_clip else 1) * P, C) or not token.is_contiguous()))):
+        raise RuntimeError(f"evt token join: {None if x2 is None else tuple(x2.shape)} + token {None if token is None else tuple(token.shape)} "
+                           f"is not {N} clips of {T} frames of {P} unit-stride token rows of {C} and a [P, C] or [N*P, C] token")
+    out = torch.empty(N * (T + 1) * P, C, dtype=torch.float32, device=dev)
+    slot = _new_slot(dev, want_amax)
+    check(lib().npvp_evt_token_join(_ptr(x2), C if x2 is None else x2.stride(0), _ptr(token), C, P * C if per_clip else 0, _ptr(out), C,
+                                    N, T, P, C, _ptr(slot), _stream()), "npvp_evt_token_join")
+    return tag_amax(out, slot)
+
+
+def _raw_evt_split(y2, N, T, P, want_x=True, want_last=True, want_amax=True):
+    """y2 [N*(T+1)*P, C] -> (x [N*T*P, C] or None, last [N*P, C] or None)"""
+    C = y2.shape[1]
+    if y2.shape[0] != N * (T + 1) * P or y2.stride(1) != 1:
+        raise RuntimeError(f"evt token split: {tuple(y2.shape)} is not {N} clips of {T} + 1 frames of {P} unit-stride token rows")
+    x = torch.empty(N * T * P, C, dtype=torch.float32, device=y2.device) if want_x else None
+    last = torch.empty(N * P, C, dtype=torch.float32, device=y2.device) if want_last else None
+    sx, sl = _new_slot(y2.device, want_amax and want_x), _new_slot(y2.device, want_amax and want_last)
+    check(lib().npvp_evt_token_split(_ptr(y2), y2.stride(0), _ptr(x), C, _ptr(last), C, N, T, P, C, _ptr(sx), _ptr(sl), _stream()),
+          "npvp_evt_token_split")
+    return (None if x is None else tag_amax(x, sx)), (None if last is None else tag_amax(last, sl))
+
+
+class _EvtJoin(torch.autograd.Function):
+    """x (N,T,...,C) + token ((1,...,C) shared by the clips, (N,...,C) one per clip, or None: a zero frame) -> (N,T+1,...,C).
+    Backward: the split; a shared token's gradient is the fixed-order sum of `last` over the clips (npvp_reduce_mid) and goes back
+    through autograd, which orders the contributions of the two encoder passes of a stochastic step."""
+
+    @staticmethod
+    def forward(ctx, x, token):
+        remember(ctx)
+        _chk(x, token)
+        N, T, C = x.shape[0], x.shape[1], x.shape[-1]
+        P = x.numel() // (N * T * C)
+        tk = None if token is None else _c(token).reshape(-1, C)
+        ctx.geom = (N, T, P, C, None if token is None else token.shape)
+        y = _raw_evt_join(_c(x).reshape(N * T * P, C), tk, N, T, P, C, x.device)
+        return y.view(N, T + 1, *x.shape[2:])
+
+    @scoped
+    def backward(ctx, g):
+        N, T, P, C, tshape = ctx.geom
+        want_t = tshape is not None and ctx.needs_input_grad[1]
+        if not (want_t or ctx.needs_input_grad[0]):
+            return None, None
+        dx, dlast = _raw_evt_split(_c(g).reshape(-1, C), N, T, P, ctx.needs_input_grad[0], want_t, want_amax=False)
+        if want_t and tshape[0] == 1 and N > 1:
+            dlast = reduce_mid(dlast.view(1, N, P * C))
+        return (None if dx is None else dx.view(N, T, *g.shape[2:])), (dlast.view(tshape) if want_t else None)
+
+
+class _EvtSplit(torch.autograd.Function):
+    """y (N,T+1,...,C) -> x (N,T,...,C), last [N, P, C] (want_x False: last alone; x is then an empty tensor).  Backward: the join of
+    the two gradients, an output without a gradient counting as zeros."""
+
+    @staticmethod
+    def forward(ctx, y, want_x):
+        remember(ctx)
+        _chk(y)
+        N, T, C = y.shape[0], y.shape[1] - 1, y.shape[-1]
+        P = y.numel() // (N * (T + 1) * C)
+        ctx.geom = (N, T, P, C, y.shape)
+        ctx.set_materialize_grads(False)
+        x, last = _raw_evt_split(_c(y).reshape(-1, C), N, T, P, want_x, True)
+        slot_of = lambda t: getattr(t, "_npvp_amax", (None,))[0]
+        last3 = tag_amax(last.view(N, P, C), slot_of(last))
+        if x is None:
+            x = y.new_empty(0)
+            ctx.mark_non_differentiable(x)
+            return x, last3
+        return tag_amax(x.view(N, T, *y.shape[2:]), slot_of(x)), last3
+
+    @scoped
+    def backward(ctx, dx, dlast):
+        N, T, P, C, shape = ctx.geom
+        if dx is None and dlast is None:
+            return None, None
+        dev = (dx if dx is not None else dlast).device
+        dy = _raw_evt_join(None if dx is None else _c(dx).reshape(N * T * P, C), None if dlast is None else _c(dlast).reshape(N * P, C),
+                           N, T, P, C, dev, want_amax=False)
+        return dy.view(shape), None
+
+
+def evt_token_join(x, token):
+    """x (N,T,H,W,C) + the event token (1,H,W,C) (or one per clip (N,H,W,C), or None: zeros) -> (N,T+1,H,W,C)  (autograd: the backward
+    is evt_token_split, and the sum over clips for a shared token)"""
+    return _EvtJoin.apply(x, token)
+
+
+def evt_token_split(y, want_x=True):
+    """(N,T+1,H,W,C) -> the first T frames (N,T,H,W,C) and the last frame [N, H*W, C], each contiguous with its own amax slot
+    (want_x False: the first is not produced - an empty tensor)"""
+    return _EvtSplit.apply(y, want_x)
+
+
+def evt_pad_table(table, T):
+    """a positional table [T*P, C] -> [(T+1)*P, C] with a zero last frame (ref/models/VidHRFormer.py:40-41), a NEW tensor with its own
+    ActSink: the encoder's sub-layers sum their table gradients in place into it, and its backward cuts the first T*P rows back into
+    the original table's gradient.  None (fuse_method 'Add' has no gamma) stays None."""
+    if table is None:
+        return None
+    C = table.shape[-1]
+    return fan_out(_EvtJoin.apply(table.reshape(1, T, -1, C), None).view(-1, C))
+
+
 class _RowTail:
     """The degenerate geometry of the two entry points: one frame, an R x 1 grid with nothing around it, followed by zero rows up to
     the next multiple of 32 - what a linear layer over R token rows needs where R is no multiple of 32 (the weight-gradient GEMM

@@ -210,14 +210,16 @@ def cosine_warm_restarts_lr(base_lr, eta_min, T_0, epoch_float):
 
 def build_predictor_from_cfg(cls, P, num_past, num_future, **overrides):
     """Construct a Predictor the way LitPredictor.__init__ does (ref/models/Predictor.py:28-47) from the
-    `Predictor:` section of a reference YAML config."""
+    `Predictor:` section of a reference YAML config.  learn_evt_token (ref :46 passes False; the reference's YAMLs do not carry the
+    key) comes from the overrides, else from the section, else it is False."""
     h = torch.linspace(0, P['max_H'] - 1, P['max_H'])
     w = torch.linspace(0, P['max_W'] - 1, P['max_W'])
     to, tp = context_lists(P, num_past, num_future)
     assert P['max_T'] == num_past + num_future, "Incompatible max_T and clip length"
+    learn_evt_token = bool(overrides.pop('learn_evt_token', P.get('learn_evt_token', False)))
     return cls(P['max_H'], P['max_W'], P['max_T'], h, w, to, tp, P['embed_dim'], P['fuse_method'],
                P['param_free_norm_type'], P['evt_hidden_channels'], 1, P['stochastic'], P['transformer_layers'],
-               evt_former=P['evt_former'], learn_evt_token=False, evt_former_num_layers=P['evt_former_num_layers'],
+               evt_former=P['evt_former'], learn_evt_token=learn_evt_token, evt_former_num_layers=P['evt_former_num_layers'],
                rand_context=P['rand_context'], **overrides)
 
 
