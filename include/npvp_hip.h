@@ -80,6 +80,12 @@ long long npvp_graph_node_counts(void* graph, long long* counts, long long* mems
  * of two that puts the bound into [2^14, 2^15) - exact, undone in the epilogue.  It is taken by (a) a_kc = 1 launches with
  * fp16 planes in `b_pre` (npvp_split_weight_f16) and both a_amax / b_amax, (b) weight gradients (a_kc = b_kc = 0, plain
  * epilogue, K >= 1024) with both slots; every other launch with precision 6 runs as precision 4 without planes.
+ * precision 7 ("f16x1", inference): precision 6 in every respect - planes, slots, routes, fallbacks, weight gradients - except that
+ * the launches of (a), kernel ids 5 / 7, multiply the HIGH fp16 terms only: C = epilogue(alpha hi(A sa) hi(B sb) / (sa sb)), hi(x s) =
+ * rne_f16(x s), ONE matrix instruction per product, 11 significant bits per operand (2.9e-4 rel-L2 of a product sum against the exact
+ * one; accumulation stays fp32).  It reads plane 0 of the same fp16 planes (half the weight bytes) in K-steps of 32; tiles, epilogue,
+ * c_amax and the per-row rescue of rows far below the tensor's bound are precision 6's.  Forward-only: adrop_p > 0 or skip_p > 0 with
+ * precision 7 is an argument error.  npvp_amd.ops.eval_arithmetic("f16x1") is what passes it, for launches autograd does not record.
  * c_amax (nullable, any precision, unsplit launches): the kernel adds the bound of the values it stores to C to that slot -
  * the next GEMM's a_amax, at no extra pass.
  * Kernels: gemm_wide_kernel (128 x 256 tiles, 4 waves, A split on the fly, B = pre-split planes `b_pre` copied by LDS-DMA:
@@ -96,18 +102,19 @@ long long npvp_gemm_workspace_bytes(int M, int N, int K);
 /* which kernel npvp_gemm_f32 picks for a shape: 0 gemm_f32_kernel, 1 gemm_split_db_kernel (128 x 128 tiles), 2
  * gemm_wide_kernel<2,4,2,2> (128 x 256 tiles, weight planes by LDS-DMA), 3 gemm_wgrad_wide_kernel, 4 gemm_wide_kernel<2,2,2,2>
  * (the same kernel on 128 x 128 tiles: outputs too small to fill the chip with wide tiles), 5 gemm_f16_kernel<2,4,2,2> (precision 6,
- * 128 x 256 tiles), 6 gemm_wgrad_f16_kernel, 7 gemm_f16_kernel on smaller tiles.  The first word of npvp_gemm_route with a plain
+ * 128 x 256 tiles; precision 7: its one-term instantiation), 6 gemm_wgrad_f16_kernel, 7 gemm_f16_kernel on smaller tiles.  The first word of npvp_gemm_route with a plain
  * epilogue.  Pure function (measurement aid; ops.gemm also decides from it which amax slots to fill). */
 int npvp_gemm_kernel_id(int a_kc, int b_kc, int M, int N, int K, int precision, int has_planes);
 /* The whole route of a launch, for tests that must prove which leaf of the dispatcher they hit (tests/gemm_route_cases.py).  It is the
  * dispatcher's own plan: npvp_gemm_f32 launches what the same planner returns for the facts of its arguments, this query reports what it
- * returns for a caller that hands over a workspace of npvp_gemm_workspace_bytes and (precision 6) both amax slots, and asks for no frame
+ * returns for a caller that hands over a workspace of npvp_gemm_workspace_bytes and (precision 6 / 7) both amax slots, and asks for no frame
  * statistics.  A caller that leaves the workspace or a slot out gets the same answer with that kernel's condition failing: precision 6
  * without slots runs as precision 4 without planes, a split plan without its workspace runs unsplit on the 128 x 128 kernel.
  * out4 = {kernel id as above, tile variant (precision 6, ids 5 / 7: 1 = 128 x 256, 2 = 128 x 128, 3 = 128 x 64, 4 = 64 x 128 tiles;
  * precision 4, ids 2 / 4: 1 = 128 x 256, 2 = 128 x 128; 0 elsewhere), split-K count of the launch, K-steps per split of that kernel (steps
  * of 16, of 32 for id 0)}.  plain_epilogue = no bias / activation / aux_out / residual / dropout (only such launches split K or take a
- * weight-gradient kernel).  With plain_epilogue = 1, out4[0] == npvp_gemm_kernel_id.  Pure function. */
+ * weight-gradient kernel).  With plain_epilogue = 1, out4[0] == npvp_gemm_kernel_id.  Precision 7 answers as precision 6 (the same for
+ * npvp_gemm_kernel_id), except that on ids 5 / 7 the steps are the one-term kernel's own, of 32: out4[3] = K / 32.  Pure function. */
 int npvp_gemm_route(int a_kc, int b_kc, int M, int N, int K, int precision, int has_planes, int plain_epilogue, int* out4);
 int npvp_gemm_f32(int a_kc, int b_kc, int M, int N, int K, const float* A, long long lda, const float* B, long long ldb,
                   float* C, long long ldc, const float* bias, int act, const float* aux_in, float* aux_out,

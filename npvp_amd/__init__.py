@@ -39,6 +39,7 @@ from .trainer import (FlatAdamW, predictor_train_step, full_train_step, predicto
                       save_lightning_checkpoint, load_lightning_checkpoint, GraphedTrainStep,
                       AEPair, ae_optimizer, ae_train_step, ae_data_parallel, ae_val_step, save_ae_checkpoint, load_ae_checkpoint)
 from . import ops
+from .ops import eval_arithmetic
 from . import metrics, data
 
 __all__ = ["Predictor", "VidHRFormerEncoder", "VidHRformerDecoderNAR", "VidHRFormerBlockEnc", "VidHRFormerBlockDecNAR",
@@ -47,6 +48,6 @@ __all__ = ["Predictor", "VidHRFormerEncoder", "VidHRformerDecoderNAR", "VidHRFor
            "full_sample_step", "context_lists",
            "rand_context_collate", "rand_context_batch_process", "vfi_batch_process",
            "save_lightning_checkpoint", "load_lightning_checkpoint", "GraphedTrainStep",
-           "cosine_warm_restarts_lr", "build_predictor_from_cfg", "ops", "metrics", "data",
+           "cosine_warm_restarts_lr", "build_predictor_from_cfg", "ops", "eval_arithmetic", "metrics", "data",
            "build_autoencoder", "prepare_trainable_autoencoder", "AEPair", "ae_optimizer", "ae_train_step", "ae_data_parallel", "ae_val_step",
            "save_ae_checkpoint", "load_ae_checkpoint"]

@@ -393,7 +393,7 @@ void launch_gemm_wide(GemmParams& p, int variant, hipStream_t stream);
 void launch_gemm_wgrad_wide(GemmParams& p, hipStream_t stream);
 // gemm_f16.hip: the two-term fp16 forms of the three (precision 6)
 int gemm_f16_variant(int M, int N, int K);       // 0 not taken, 1 = 128 x 256 tiles, 2 = 128 x 128, 3 = 128 x 64, 4 = 64 x 128
-void launch_gemm_f16(GemmParams& p, int variant, hipStream_t stream);
+void launch_gemm_f16(GemmParams& p, int variant, bool x1, hipStream_t stream);      // x1: the one-term arithmetic (precision 7)
 void launch_gemm_wgrad_f16(GemmParams& p, hipStream_t stream);
 
 }  // namespace npvp

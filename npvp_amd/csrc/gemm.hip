@@ -533,7 +533,8 @@ extern "C" int npvp_split_weights_batched(const void* desc, int count, hipStream
 // ---- the dispatcher: ONE planner.  npvp_gemm_f32 launches the plan, npvp_gemm_route / npvp_gemm_kernel_id report it. ---------------
 // What the choice of kernel depends on, as plain facts:
 struct GemmFacts {
-  int a_kc, b_kc, M, N, K, precision;   // precision as the caller gave it: 6 = the fp16 kernels where they apply, else 4 WITHOUT planes
+  int a_kc, b_kc, M, N, K, precision;   // precision as the caller gave it: 6 = the fp16 kernels where they apply, else 4 WITHOUT planes;
+                                        // 7 = 6 with the one-term arithmetic on ids 5 / 7
   bool planes;                          // pre-split planes of B are handed over (b_pre)
   bool plain;                           // no bias, act == 0, no aux_out, no residual, drop_p == 0
   bool amax;                            // both operand amax slots are handed over (the fp16 kernels scale by them)
@@ -542,15 +543,17 @@ struct GemmFacts {
 };
 // Kernel id: 0 gemm_f32_kernel, 1 gemm_split_db_kernel (both 128 x 128 tiles), 2 / 4 gemm_wide_kernel on 128 x 256 / 128 x 128 tiles,
 // 3 gemm_wgrad_wide_kernel, 5 / 7 gemm_f16_kernel on 128 x 256 / smaller tiles, 6 gemm_wgrad_f16_kernel.  variant: the tile variant of
-// ids 2 / 4 (wide_variant) and 5 / 7 (gemm_f16_variant), else 0.  steps: K-steps per split (of 32 for id 0, of 16 otherwise).
+// ids 2 / 4 (wide_variant) and 5 / 7 (gemm_f16_variant), else 0.  steps: K-steps per split (of 32 for id 0 and for the one-term form
+// of ids 5 / 7, of 16 otherwise).
 struct GemmPlan {
   int id, variant, splits, steps;
   bool planes;                          // the kernel reads the planes
+  bool x1;                              // ids 5 / 7 only: the one-term arithmetic (precision 7), a 32-deep K-step
 };
 
 static GemmPlan plan_gemm(const GemmFacts& f) {
   const int M = f.M, N = f.N, K = f.K;
-  const bool want_h = f.precision == 6;
+  const bool want_h = f.precision == 6 || f.precision == 7;
   const int precision = want_h ? 4 : f.precision;
   // the 128 x 128 kernels split K only with a plain epilogue and a workspace that holds whatever kernel the shape may run on
   int s128 = pick_splits(M, N, K);
@@ -559,10 +562,10 @@ static GemmPlan plan_gemm(const GemmFacts& f) {
   const bool wgrad = !f.a_kc && !f.b_kc && f.plain && !f.rowstats;
   // a weight-gradient kernel takes its own split count s (0: shape not taken) if the workspace holds its slabs and column sums
   auto fits = [&](int s) { return s == 1 || (s > 1 && f.ws_bytes >= splitk_workspace_bytes(s, M, N)); };
-  GemmPlan pl = {precision == 0 ? 0 : 1, 0, s128, 0, false};
+  GemmPlan pl = {precision == 0 ? 0 : 1, 0, s128, 0, false, false};
   int v = 0, s = 0;
   if (want_h && planes_ok && f.amax && (v = gemm_f16_variant(M, N, K)) != 0) {
-    pl.id = v == 1 ? 5 : 7; pl.variant = v; pl.splits = 1; pl.planes = true;
+    pl.id = v == 1 ? 5 : 7; pl.variant = v; pl.splits = 1; pl.planes = true; pl.x1 = f.precision == 7;
   } else if (want_h && wgrad && f.amax && fits(s = f16_wgrad_splits(M, N, K))) {
     pl.id = 6; pl.splits = s;
   } else if (!want_h && precision == 4 && planes_ok && s128 == 1 && (v = wide_variant(M, N, K)) != 0) {
@@ -573,7 +576,7 @@ static GemmPlan plan_gemm(const GemmFacts& f) {
     // the 128 x 128 kernels; fp16 planes (want_h) are not what the bf16 kernel reads, and its rowstats instantiation stages none
     pl.planes = !want_h && precision == 4 && planes_ok && s128 == 1 && !f.rowstats;
   }
-  pl.steps = K / pl.splits / (precision == 0 ? BK : 16);
+  pl.steps = K / pl.splits / ((precision == 0 || pl.x1) ? BK : 16);
   return pl;
 }
 
@@ -590,7 +593,7 @@ extern "C" int npvp_gemm_kernel_id(int a_kc, int b_kc, int M, int N, int K, int 
 
 extern "C" int npvp_gemm_route(int a_kc, int b_kc, int M, int N, int K, int precision, int has_planes, int plain_epilogue, int* out4) {
   NPVP_CHECK_ARG(out4 && M > 0 && N > 0 && K > 0, "gemm_route: empty problem or no result array");
-  NPVP_CHECK_ARG(precision == 0 || precision == 4 || precision == 5 || precision == 6, "gemm_route: precision must be 0, 4, 5 or 6");
+  NPVP_CHECK_ARG(precision == 0 || (precision >= 4 && precision <= 7), "gemm_route: precision must be 0, 4, 5, 6 or 7");
   NPVP_CHECK_ARG(K % BK == 0 && M % 4 == 0 && N % 4 == 0 && !(a_kc == 0 && b_kc == 1), "gemm_route: not a problem npvp_gemm_f32 accepts");
   const GemmPlan r = plan_query(a_kc, b_kc, M, N, K, precision, has_planes, plain_epilogue != 0);
   out4[0] = r.id; out4[1] = r.variant; out4[2] = r.splits; out4[3] = r.steps;
@@ -623,13 +626,16 @@ extern "C" int npvp_gemm_f32_skip(int a_kc, int b_kc, int M, int N, int K, const
   NPVP_CHECK_ARG(skip_p >= 0.f && skip_p < 1.f && (skip_p == 0.f || (seed && skip_g1 > 0 && skip_g2 > 0 && (a_kc || !b_kc))),
                  "gemm: the row skip needs a device seed, row groups and a row-major A or a weight gradient's layout");
   NPVP_CHECK_ARG(M > 0 && N > 0 && K > 0, "gemm: empty problem");
-  NPVP_CHECK_ARG(precision == 0 || precision == 4 || precision == 5 || precision == 6,
+  NPVP_CHECK_ARG(precision == 0 || (precision >= 4 && precision <= 7),
                  "gemm: precision must be 0 (exact fp32-input MFMA), 4 (three-term bf16 split, 6 MFMAs per product: "
-                 "fp32-grade), 5 (two-term bf16 split, 3 MFMAs per product, ~2^-16) or 6 (two-term fp16 split with amax-scaled "
-                 "operands, 3 MFMAs per product: fp32-grade; shapes it does not take run as 4)");
+                 "fp32-grade), 5 (two-term bf16 split, 3 MFMAs per product, ~2^-16), 6 (two-term fp16 split with amax-scaled "
+                 "operands, 3 MFMAs per product: fp32-grade; shapes it does not take run as 4) or 7 (6 with one fp16 term per "
+                 "operand on its forward / dgrad kernels: inference)");
   // precision 6 = fp16 two-term kernels where they apply (a row-major A with fp16 planes of B + both amax slots; weight
-  // gradients with both amax slots), the three-term bf16 kernels WITHOUT planes everywhere else
-  const bool want_h = precision == 6;
+  // gradients with both amax slots), the three-term bf16 kernels WITHOUT planes everywhere else.  Precision 7 = 6, except that the
+  // launches the plan sends to ids 5 / 7 multiply the high terms only (forward-only: no row-group mask on A, no row skip)
+  const bool want_h = precision == 6 || precision == 7;
+  NPVP_CHECK_ARG(precision != 7 || (adrop_p == 0.f && skip_p == 0.f), "gemm: precision 7 is forward-only arithmetic: it takes no adrop and no row skip");
   NPVP_CHECK_ARG(K % BK == 0, "gemm: K must be a multiple of 32");
   NPVP_CHECK_ARG(M % 4 == 0 && N % 4 == 0, "gemm: M and N must be multiples of 4");
   NPVP_CHECK_ARG(((uintptr_t)A % 16) == 0 && ((uintptr_t)B % 16) == 0 && ((uintptr_t)C % 16) == 0, "gemm: pointers must be 16-byte aligned");
@@ -679,7 +685,7 @@ extern "C" int npvp_gemm_f32_skip(int a_kc, int b_kc, int M, int N, int K, const
 
   const dim3 grid(p.tiles_m * p.tiles_n, plan.splits), block(GEMM_THREADS);
   switch (plan.id) {
-    case 5: case 7: launch_gemm_f16(p, plan.variant, stream); break;
+    case 5: case 7: launch_gemm_f16(p, plan.variant, plan.x1, stream); break;
     case 6: launch_gemm_wgrad_f16(p, stream); break;      // (takes the row skip as npvp_wgrad_f16_chained_skip does: same kernel, same slabs)
     case 2: case 4: launch_gemm_wide(p, plan.variant, stream); break;
     case 3: launch_gemm_wgrad_wide(p, stream); break;

@@ -18,6 +18,10 @@
 // Kernel organisation = gemm_wide.hip's (128 x 256 or 128 x 128 tile, 4 waves, K-step 16, two LDS stages, two workgroups
 // per CU) with two planes per operand: 24.8 KB per stage instead of 36.4, 24 MFMAs and ~20 VALU of splitting per wave and
 // K-step instead of 48 and ~60.
+//
+// ONE-TERM form ("f16x1", precision 7; gemm_f16_body<..., X1 = true>): hi_a hi_b alone, ONE matrix instruction per product, for
+// forward passes nobody differentiates (npvp_amd.ops.eval_arithmetic) - 11 significant bits per operand, 2.9e-4 rel-L2 of a
+// product sum against fp64.  Same planes (plane 0), same slots and scales, same tiles; K-step 32.
 #include "gemm.h"
 #include <cstdio>
 #include <cstdlib>
@@ -54,6 +58,22 @@ __device__ __forceinline__ void split_f16_scaled(const f32x4 v, const float s, f
   lo = __builtin_bit_cast(f16x4, lp);
 }
 
+// x (8 consecutive k: a, b), s -> hi = rne_f16(x s) alone: the two mixed FMAs per pair that make the high term above (f16x1)
+__device__ __forceinline__ f16x8 hi_f16_scaled(const f32x4 a, const f32x4 b, const float s) {
+  unsigned int h01, h23, h45, h67;
+  asm("v_fma_mixlo_f16 %0, %1, %2, 0" : "=v"(h01) : "v"(a[0]), "v"(s));
+  asm("v_fma_mixlo_f16 %0, %1, %2, 0" : "=v"(h23) : "v"(a[2]), "v"(s));
+  asm("v_fma_mixlo_f16 %0, %1, %2, 0" : "=v"(h45) : "v"(b[0]), "v"(s));
+  asm("v_fma_mixlo_f16 %0, %1, %2, 0" : "=v"(h67) : "v"(b[2]), "v"(s));
+  asm("v_fma_mixhi_f16 %0, %1, %2, 0" : "+v"(h01) : "v"(a[1]), "v"(s));
+  asm("v_fma_mixhi_f16 %0, %1, %2, 0" : "+v"(h23) : "v"(a[3]), "v"(s));
+  asm("v_fma_mixhi_f16 %0, %1, %2, 0" : "+v"(h45) : "v"(b[1]), "v"(s));
+  asm("v_fma_mixhi_f16 %0, %1, %2, 0" : "+v"(h67) : "v"(b[3]), "v"(s));
+  typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+  const u32x4 hp = {h01, h23, h45, h67};
+  return __builtin_bit_cast(f16x8, hp);
+}
+
 // workgroup-wide OR of a per-thread predicate (every thread calls it; NW waves; `flags` = NW ints of LDS nobody else uses)
 template <int NW>
 __device__ __forceinline__ bool block_any(bool pred, int* flags, int wave) {
@@ -82,7 +102,15 @@ constexpr int gemm_f16_lds_bytes() {
 
 // The kernel's body: workgroup `bid` of the `nwg` that cover the problem, on `lds` (gemm_f16_lds_bytes of it).  A function so that a
 // launch can hold more than one problem (gemm_f16_group_kernel below: a dgrad and the weight gradient of the same dy in ONE launch).
-template <int TM, int TN, int WM, int WN, bool ROWSTATS, int NST>
+//
+// X1 = the ONE-TERM arithmetic ("f16x1", precision 7: forward-only inference): only the high terms are multiplied,
+//     C = epilogue(alpha hi(A sa) hi(B sb) / (sa sb)),   ONE matrix instruction per product.
+// The stage keeps its geometry and the K-step becomes 32 deep: the slots of the low planes hold k-groups 2 - 3 of the high plane, so
+// B is four contiguous k-group slabs of plane 0 of the SAME weight planes (the same number of LDS-DMA pieces per step, half the weight
+// bytes per K), A is two float4 per staged row (one k-group = one 16-byte slot per thread and row, only the two mixed FMAs per pair
+// that make `hi`), the fragment reads are the ones below (term s_ reads k-groups 2 s_ + h) and a step is 2 instead of 6 MFMAs per
+// accumulator and 16 of K.  Tile order, row skip, row guard, scales, epilogue and amax commit are the code of the two-term form.
+template <int TM, int TN, int WM, int WN, bool ROWSTATS, int NST, bool X1 = false>
 __device__ __forceinline__ void gemm_f16_body(const GemmParams& p, char* lds, const int bid, const int nwg) {
   constexpr int NW = WM * WN, THREADS = 64 * NW;
   constexpr int BM = WM * TM * 32, BN = WN * TN * 32;
@@ -101,7 +129,7 @@ __device__ __forceinline__ void gemm_f16_body(const GemmParams& p, char* lds, co
   const int m0 = tile_m * BM, n0 = tile_n * BN;
   const int t = threadIdx.x, lane = t & 63, wave = __builtin_amdgcn_readfirstlane(t >> 6);
   const int wm = wave / WN, wn = wave % WN, r = lane & 31, h = lane >> 5;
-  const int nk = p.K >> 4;
+  const int nk = X1 ? p.K >> 5 : p.K >> 4;
   const float sa = amax_scale(amax_slot_read(p.a_amax));
   const unsigned int cpeek = amax_peek_block(p.c_amax);
 
@@ -130,9 +158,11 @@ __device__ __forceinline__ void gemm_f16_body(const GemmParams& p, char* lds, co
   // global addresses = wave-uniform 64-bit base (SGPRs, advanced per K-step by scalar adds) + a per-lane 32-bit byte offset that
   // never changes: no 64-bit vector adds inside the K loop (they were 6 of its 38 VALU per step)
   const char* a_base = reinterpret_cast<const char*>(p.A + (long long)m0 * p.lda);
-  const unsigned int a_off0 = (unsigned int)(((long long)(min(m0 + rl, p.M - 1) - m0) * p.lda + 4 * quad) * 4);
-  const unsigned int a_off1 = (unsigned int)(((long long)(min(m0 + rl + BM / 2, p.M - 1) - m0) * p.lda + 4 * quad) * 4);
-  const int a_dst = (quad >> 1) * KGS_A + (quad & 1) * 8 + rl * 16;
+  // (X1: a thread stages the 8 k of k-group `quad` of the 32-deep step - two float4, one 16-byte slot)
+  constexpr int AQ = X1 ? 8 : 4;
+  const unsigned int a_off0 = (unsigned int)(((long long)(min(m0 + rl, p.M - 1) - m0) * p.lda + AQ * quad) * 4);
+  const unsigned int a_off1 = (unsigned int)(((long long)(min(m0 + rl + BM / 2, p.M - 1) - m0) * p.lda + AQ * quad) * 4);
+  const int a_dst = X1 ? quad * KGS_A + rl * 16 : (quad >> 1) * KGS_A + (quad & 1) * 8 + rl * 16;
   // a row-group mask on A (the backward of a DropPath site): this thread stages the same two rows in every K-step, so the
   // mask is folded into their scales once
   float sa0 = sa, sa1 = sa;
@@ -149,10 +179,11 @@ __device__ __forceinline__ void gemm_f16_body(const GemmParams& p, char* lds, co
     const int c = wave + NW * i;
     const int slab = c / CPS, part = c - slab * CPS, s = slab >> 1, kg = slab & 1;
     const int col = min(n0 + part * 64 + lane, p.N - 1);
-    b_off[i] = (unsigned int)(((long long)s * (p.b_pre_plane >> 3) + (long long)kg * p.N + col) * 16);
+    if constexpr (X1) b_off[i] = (unsigned int)(((long long)slab * p.N + col) * 16);        // k-group `slab` of plane 0
+    else b_off[i] = (unsigned int)(((long long)s * (p.b_pre_plane >> 3) + (long long)kg * p.N + col) * 16);
     b_dst[i] = A_BYTES + s * B_PLANE + kg * KGS_B + part * 1024;
   }
-  const long long b_step = 32ll * p.N;                // bytes per K-step
+  const long long b_step = (X1 ? 64ll : 32ll) * p.N;  // bytes per K-step
   const unsigned int lds_u32 = (unsigned int)(size_t)((lptr_t)lds);
 
   const int fa_off = h * KGS_A + (wm * TM * 32 + r) * 16;
@@ -164,21 +195,33 @@ __device__ __forceinline__ void gemm_f16_body(const GemmParams& p, char* lds, co
   // in front of every barrier.  VMEM issue order per step: 4 (CPW) LDS-DMA pieces of B tile kt+1, then 2 loads of A tile
   // kt+3; "vmcnt(2)" at the step's end therefore waits for everything but those 2 loads - B kt+1 (one step of latency
   // budget) and A kt+2 (a step and a half) have landed, and the registers consumed in the next step are valid.
+  // (X1: a set is two float4 per row - ea0 / ea0x = floats 0 - 3 / 4 - 7 of the thread's k-group -, 2 APASS loads per step)
   f32x4 ea0, ea1 = {0.f, 0.f, 0.f, 0.f}, eb0, eb1 = {0.f, 0.f, 0.f, 0.f};
+  f32x4 ea0x = {0.f, 0.f, 0.f, 0.f}, ea1x = {0.f, 0.f, 0.f, 0.f}, eb0x = {0.f, 0.f, 0.f, 0.f}, eb1x = {0.f, 0.f, 0.f, 0.f};
 #define NPVP_H_ALOAD(R0, R1, KT)                                                                           \
-  { const char* ab_ = a_base + ((long long)min((KT), nk - 1) << 6);                                        \
+  { const char* ab_ = a_base + ((long long)min((KT), nk - 1) << (X1 ? 7 : 6));                             \
     asm volatile("global_load_dwordx4 %0, %1, %2" : "=v"(R0) : "v"(a_off0), "s"(ab_) : "memory");          \
-    if constexpr (APASS == 2) asm volatile("global_load_dwordx4 %0, %1, %2" : "=v"(R1) : "v"(a_off1), "s"(ab_) : "memory"); }
-  // everything but the APASS loads just issued has landed
-#define NPVP_H_WAIT_BUT_NEWEST(...)                                                                        \
-  { if constexpr (APASS == 2) asm volatile("s_waitcnt vmcnt(2) lgkmcnt(0)" : __VA_ARGS__ :: "memory");     \
-    else asm volatile("s_waitcnt vmcnt(1) lgkmcnt(0)" : __VA_ARGS__ :: "memory"); }
+    if constexpr (X1) asm volatile("global_load_dwordx4 %0, %1, %2 offset:16" : "=v"(R0##x) : "v"(a_off0), "s"(ab_) : "memory"); \
+    if constexpr (APASS == 2) asm volatile("global_load_dwordx4 %0, %1, %2" : "=v"(R1) : "v"(a_off1), "s"(ab_) : "memory"); \
+    if constexpr (APASS == 2 && X1) asm volatile("global_load_dwordx4 %0, %1, %2 offset:16" : "=v"(R1##x) : "v"(a_off1), "s"(ab_) : "memory"); }
+  // everything but the APASS (X1: 2 APASS) loads just issued has landed; RN0 / RN1 = the register set tied to the wait
+#define NPVP_H_WAIT_BUT_NEWEST(RN0, RN1)                                                                   \
+  { if constexpr (X1) asm volatile("s_waitcnt vmcnt(%4) lgkmcnt(0)" : "+v"(RN0), "+v"(RN1), "+v"(RN0##x), "+v"(RN1##x) : "n"(2 * APASS) : "memory"); \
+    else if constexpr (APASS == 2) asm volatile("s_waitcnt vmcnt(2) lgkmcnt(0)" : "+v"(RN0), "+v"(RN1) :: "memory"); \
+    else asm volatile("s_waitcnt vmcnt(1) lgkmcnt(0)" : "+v"(RN0), "+v"(RN1) :: "memory"); }
   // three stages: everything but what THIS step issued has landed - its CPW LDS-DMA pieces (B tile kt+2) and its APASS loads
   // (A tile kt+3); vector-memory operations complete in issue order, so B tile kt+1 and A tile kt+2 (issued a step ago) are in
-  // (two tied register operands: the count is %2)
-#define NPVP_H_WAIT_BUT_THIS_STEP(...)                                                                     \
-  asm volatile("s_waitcnt vmcnt(%2) lgkmcnt(0)" : __VA_ARGS__ : "n"(CPW + APASS) : "memory");
+  // (two tied register operands: the count is %2; X1: four, %4)
+#define NPVP_H_WAIT_BUT_THIS_STEP(RN0, RN1)                                                                \
+  { if constexpr (X1) asm volatile("s_waitcnt vmcnt(%4) lgkmcnt(0)" : "+v"(RN0), "+v"(RN1), "+v"(RN0##x), "+v"(RN1##x) : "n"(CPW + 2 * APASS) : "memory"); \
+    else asm volatile("s_waitcnt vmcnt(%2) lgkmcnt(0)" : "+v"(RN0), "+v"(RN1) : "n"(CPW + APASS) : "memory"); }
 #define NPVP_H_ASTORE(ST, V, ROWOFF)                                                     \
+  if constexpr (X1) {                                                                    \
+    const f32x4 m_ = __builtin_elementwise_max(__builtin_elementwise_abs(V), __builtin_elementwise_abs(V##x));     \
+    if (ROWOFF) rm1 = fmaxf(fmaxf(rm1, fmaxf(m_[0], m_[1])), fmaxf(m_[2], m_[3]));       \
+    else rm0 = fmaxf(fmaxf(rm0, fmaxf(m_[0], m_[1])), fmaxf(m_[2], m_[3]));              \
+    *reinterpret_cast<f16x8*>((ST) + a_dst + (ROWOFF)) = hi_f16_scaled((V), (V##x), (ROWOFF) ? sa1 : sa0); \
+  } else                                                                                 \
   { if (ROWOFF) rm1 = fmaxf(fmaxf(rm1, fmaxf(fabsf((V)[0]), fabsf((V)[1]))), fmaxf(fabsf((V)[2]), fabsf((V)[3])));  \
     else rm0 = fmaxf(fmaxf(rm0, fmaxf(fabsf((V)[0]), fabsf((V)[1]))), fmaxf(fabsf((V)[2]), fabsf((V)[3])));         \
     f16x4 hi_, lo_; split_f16_scaled((V), (ROWOFF) ? sa1 : sa0, hi_, lo_);               \
@@ -214,12 +257,13 @@ __device__ __forceinline__ void gemm_f16_body(const GemmParams& p, char* lds, co
   NPVP_H_BLOAD(lds, 0)
   NPVP_H_ALOAD(ea0, ea1, 0)
   asm volatile("s_waitcnt vmcnt(0)" : "+v"(ea0), "+v"(ea1) :: "memory");
+  if constexpr (X1) asm volatile("" : "+v"(ea0x), "+v"(ea1x) :: "memory");
   NPVP_H_ASTORE(lds, ea0, 0)
   if constexpr (APASS == 2) NPVP_H_ASTORE(lds, ea1, (BM / 2) * 16)
   if constexpr (NST == 3) NPVP_H_BLOAD(lds + STAGE, 1)      // (three stages: B tile 1 leaves here, step kt DMAs tile kt + 2)
   NPVP_H_ALOAD(ea0, ea1, 1)
   NPVP_H_ALOAD(eb0, eb1, 2)
-  NPVP_H_WAIT_BUT_NEWEST("+v"(ea0), "+v"(ea1))
+  NPVP_H_WAIT_BUT_NEWEST(ea0, ea1)
   __builtin_amdgcn_s_barrier();
 
   // one K-step: MFMAs of tile KT on stage CUR; B tile KT+1 is DMA'd into NXT; A tile KT+1 (register set R, loaded two
@@ -245,14 +289,19 @@ __device__ __forceinline__ void gemm_f16_body(const GemmParams& p, char* lds, co
         fa_[s_] = *reinterpret_cast<const f16x8*>(st_ + fa_off + s_ * A_PLANE + i_ * 512);                 \
       if (i_ == 0) { NPVP_H_ASTORE(nx_, R0, 0) if constexpr (APASS == 2) NPVP_H_ASTORE(nx_, R1, (BM / 2) * 16) } \
       if (i_ == TM - 1) { NPVP_H_ALOAD(R0, R1, (KT) + 3) }                                                 \
+      if constexpr (X1) {                                                                                  \
+      _Pragma("unroll") for (int j_ = 0; j_ < TN; ++j_) acc[i_][j_] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa_[0], fb_[0][j_], (FIRST) ? zero16 : acc[i_][j_], 0, 0, 0); \
+      _Pragma("unroll") for (int j_ = 0; j_ < TN; ++j_) acc[i_][j_] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa_[1], fb_[1][j_], acc[i_][j_], 0, 0, 0); \
+      } else {                                                                                             \
       /* smallest terms first */                                                                           \
       _Pragma("unroll") for (int j_ = 0; j_ < TN; ++j_) acc[i_][j_] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa_[1], fb_[0][j_], (FIRST) ? zero16 : acc[i_][j_], 0, 0, 0); \
       _Pragma("unroll") for (int j_ = 0; j_ < TN; ++j_) acc[i_][j_] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa_[0], fb_[1][j_], acc[i_][j_], 0, 0, 0); \
       _Pragma("unroll") for (int j_ = 0; j_ < TN; ++j_) acc[i_][j_] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa_[0], fb_[0][j_], acc[i_][j_], 0, 0, 0); \
+      }                                                                                                    \
     }                                                                                                      \
     __builtin_amdgcn_sched_barrier(0);       /* every MFMA of the step is issued before the wave parks at the wait */ \
-    if constexpr (NST == 3) { NPVP_H_WAIT_BUT_THIS_STEP("+v"(RN0), "+v"(RN1)) }                            \
-    else { NPVP_H_WAIT_BUT_NEWEST("+v"(RN0), "+v"(RN1)) }                                                  \
+    if constexpr (NST == 3) { NPVP_H_WAIT_BUT_THIS_STEP(RN0, RN1) }                                        \
+    else { NPVP_H_WAIT_BUT_NEWEST(RN0, RN1) }                                                              \
     __builtin_amdgcn_s_barrier();                                                                          \
   }
 
@@ -287,6 +336,7 @@ __device__ __forceinline__ void gemm_f16_body(const GemmParams& p, char* lds, co
   //  and a dead asm output may be given a register that the code between the load and this wait uses for something else -
   //  the load then lands in it.  Seen as intermittent wrong tiles once the row guard changed the register allocation.)
   asm volatile("s_waitcnt vmcnt(0)" : "+v"(ea0), "+v"(ea1), "+v"(eb0), "+v"(eb1) :: "memory");
+  if constexpr (X1) asm volatile("" : "+v"(ea0x), "+v"(ea1x), "+v"(eb0x), "+v"(eb1x) :: "memory");
   // (three stages: the last step's clamped B pieces were still in flight at its closing barrier - every wave's must be in before
   //  any wave turns the stages into the epilogue's scratch or a second pass rewrites stage 0)
   if constexpr (NST == 3) __builtin_amdgcn_s_barrier();
@@ -383,10 +433,10 @@ __device__ __forceinline__ void gemm_f16_body(const GemmParams& p, char* lds, co
 }
 
 // NST = LDS stages (see gemm_f16_body).
-template <int TM, int TN, int WM, int WN, bool ROWSTATS, int MINB = 2, int NST = 2>
+template <int TM, int TN, int WM, int WN, bool ROWSTATS, int MINB = 2, int NST = 2, bool X1 = false>
 __global__ __launch_bounds__(64 * WM * WN, MINB) void gemm_f16_kernel(GemmParams p) {
   __shared__ __attribute__((aligned(16))) char lds[gemm_f16_lds_bytes<TM, TN, WM, WN, NST>()];
-  gemm_f16_body<TM, TN, WM, WN, ROWSTATS, NST>(p, lds, blockIdx.x, gridDim.x);
+  gemm_f16_body<TM, TN, WM, WN, ROWSTATS, NST, X1>(p, lds, blockIdx.x, gridDim.x);
 }
 
 // =====================================================================================================
@@ -748,11 +798,24 @@ static void prep_gemm_f16(GemmParams& p, int v) {
   p.colgroups = pick_colgroups((long long)p.N * p.K * 4, p.tiles_m, p.tiles_n);
 }
 
-void launch_gemm_f16(GemmParams& p, int v, hipStream_t stream) {
+// x1: the one-term arithmetic (precision 7) on the same tiles, 32 of K per step (p.K % 32 == 0)
+void launch_gemm_f16(GemmParams& p, int v, bool x1, hipStream_t stream) {
   if (p.rowstats && v != 1) v = 2;                     // frame statistics exist for 128 x 256 and 128 x 128 tiles only
   prep_gemm_f16(p, v);
   dim3 grid(p.tiles_m * p.tiles_n), block(256);
-  if (v == 1) {
+  if (x1) {
+    if (v == 1) {
+      if (p.rowstats) NPVP_LAUNCH((gemm_f16_kernel<2, 4, 2, 2, true, 2, 2, true>), grid, block, 0, stream, p);
+      else NPVP_LAUNCH((gemm_f16_kernel<2, 4, 2, 2, false, 2, 2, true>), grid, block, 0, stream, p);
+    } else if (v == 3) {
+      NPVP_LAUNCH((gemm_f16_kernel<2, 1, 2, 2, false, 2, 3, true>), grid, block, 0, stream, p);
+    } else if (v == 4) {
+      NPVP_LAUNCH((gemm_f16_kernel<1, 2, 2, 2, false, 2, 3, true>), grid, block, 0, stream, p);
+    } else {
+      if (p.rowstats) NPVP_LAUNCH((gemm_f16_kernel<2, 2, 2, 2, true, 2, 3, true>), grid, block, 0, stream, p);
+      else NPVP_LAUNCH((gemm_f16_kernel<2, 2, 2, 2, false, 2, 3, true>), grid, block, 0, stream, p);
+    }
+  } else if (v == 1) {
     if (p.rowstats) NPVP_LAUNCH((gemm_f16_kernel<2, 4, 2, 2, true>), grid, block, 0, stream, p);
     else NPVP_LAUNCH((gemm_f16_kernel<2, 4, 2, 2, false>), grid, block, 0, stream, p);
   } else if (v == 3) {

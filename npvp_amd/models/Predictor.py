@@ -175,19 +175,20 @@ class Predictor(nn.Module):
         out = out.view(S, N, self.TP, C, H, W).permute(1, 0, 2, 3, 4, 5)
         return (out, eps, z) if return_eps else out
 
-    def sample(self, observed_features, n_samples, seed=None, sample_base=0, return_eps=False):
+    def sample(self, observed_features, n_samples, seed=None, sample_base=0, return_eps=False, arithmetic=None):
         """observed_features (N, To, C, H, W) -> n_samples futures per clip, (N, S, Tp, C, H, W) [, eps [S, N, H*W, C]].
         The eval forward (ref Predictor.py:312-322) with S draws of zo instead of one: positional tables, encoder and prior
         head run once, the latent comes from the device sampler (ops.reparam_samples; `evt_prior.eps_fn` is not consulted), the
         decoder runs on S*N clips against the N-clip memory.  seed None: the scheduling context's device seed; an int: that value.
         Sample sample_base + s of a seed is the same latent however S is cut into calls.  Runs under no_grad with eval
-        behaviour; the module's train / eval state is restored."""
+        behaviour; the module's train / eval state is restored.  arithmetic (None = the GEMM mode as it is, or a name
+        ops.eval_arithmetic takes): "f16x1" runs the context encoding and the decode in the one-term fp16 arithmetic."""
         if not self.stochastic:
             raise ValueError("Predictor.sample needs a stochastic predictor (stochastic=True): a deterministic one has one future")
         was_training = self.training
         self.eval()
         try:
-            with torch.no_grad():
+            with torch.no_grad(), ops.arithmetic_scope(arithmetic):
                 ctx = self.sample_context(observed_features)
                 seed_t = self.sample_seed_tensor(seed, observed_features.device)
                 res = self.sample_decode(ctx, n_samples, seed_t, sample_base, return_eps)

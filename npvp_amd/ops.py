@@ -3,6 +3,7 @@ the current HIP stream and the autograd graph; every piece of arithmetic on the 
 a hand-written gfx950 kernel reached through ctypes.  There is no CPU / eager fallback:
 tensors must be fp32 CUDA(ROCm) tensors and the library must be built.
 """
+import contextlib
 import functools
 import os
 from collections import namedtuple
@@ -156,6 +157,73 @@ WGRAD_PRECISION = {"": None, "bf16x6": None, "same": None, "bf16x3": 5}[os.envir
 def set_gemm_precision(name):
     global GEMM_PRECISION
     GEMM_PRECISION = GEMM_MODES[name]
+
+
+# Arithmetic of the forward GEMMs of INFERENCE (opt-in, `eval_arithmetic`): f16x3 is the training arithmetic above; f16x1 multiplies
+# the high fp16 terms only - ONE matrix instruction per product, 11 significant bits per operand (2.9e-4 rel-L2 per GEMM against the
+# exact product), on the same weight planes and amax slots (precision 7 of npvp_gemm_f32: csrc/gemm_f16.hip).  It exists for the
+# sampler, whose S * N clips per call are forward-only work; nothing autograd differentiates ever runs in it.
+EVAL_ARITHMETICS = ("f16x3", "f16x1")
+
+
+def eval_launch_precision(arithmetic, gemm_precision, kernel_id, autograd_off, masked=False):
+    """The precision one GEMM launch is made with under eval_arithmetic(arithmetic): 7 (one fp16 term) iff the arithmetic is f16x1,
+    the GEMM mode is f16x3 (6), the launch runs on the fp16 forward / dgrad kernels (ids 5 / 7), autograd is off and the launch
+    carries no row-group mask or row skip (training features the one-term kernels do not take); else `gemm_precision` unchanged.
+    A pure function of its arguments."""
+    if arithmetic == "f16x1" and gemm_precision == 6 and kernel_id in (5, 7) and autograd_off and not masked:
+        return 7
+    return gemm_precision
+
+
+class eval_arithmetic:
+    """with eval_arithmetic("f16x1"): the forward GEMMs launched inside, under no_grad, on the fp16 kernels run in the one-term
+    arithmetic (see eval_launch_precision); `switched` counts them.  "f16x3" names what runs anyway: nothing changes.  A launch
+    autograd will differentiate (or a backward launch) inside the block is made exactly as outside it.  Blocks nest; the innermost
+    one decides.  f16x1 exists beside the f16x3 GEMM mode only: entering it in another mode raises."""
+    current = None          # the innermost active block (process-wide, like sched._cur: backward nodes run in a thread of their own)
+
+    def __init__(self, name):
+        if name not in EVAL_ARITHMETICS:
+            raise ValueError(f"eval_arithmetic: unknown arithmetic {name!r} (one of {', '.join(EVAL_ARITHMETICS)})")
+        self.name, self.switched, self._outer = name, 0, None
+
+    def __enter__(self):
+        if self.name == "f16x1" and GEMM_PRECISION != 6:
+            raise RuntimeError("eval_arithmetic('f16x1') needs the f16x3 GEMM mode (NPVP_GEMM=f16x3): the bf16 and f32 kernels "
+                               "have no one-term form")
+        self._outer, eval_arithmetic.current = eval_arithmetic.current, self
+        return self
+
+    def __exit__(self, *exc):
+        eval_arithmetic.current, self._outer = self._outer, None
+        return False
+
+
+def arithmetic_scope(name):
+    """the block an entry point's `arithmetic=` argument asks for: None -> nothing at all, a name -> eval_arithmetic(name)"""
+    return contextlib.nullcontext() if name is None else eval_arithmetic(name)
+
+
+class _Function(torch.autograd.Function):
+    """autograd.Function whose `apply` notes, while an eval_arithmetic block is active, whether autograd was recording at the call:
+    inside `forward` grad mode is always off, for a node that will be differentiated too."""
+    _recording = 0          # depth of applies made with grad mode on (nested applies inherit it)
+
+    @classmethod
+    def apply(cls, *args):
+        if eval_arithmetic.current is None or not (torch.is_grad_enabled() or _Function._recording):
+            return super().apply(*args)
+        _Function._recording += 1
+        try:
+            return super().apply(*args)
+        finally:
+            _Function._recording -= 1
+
+
+def _autograd_off():
+    """no graph is being recorded (grad mode off here AND at the enclosing Function.apply) and no backward pass is running"""
+    return not (torch.is_grad_enabled() or _Function._recording or torch._C._current_graph_task_id() != -1)
 
 
 class WeightPlanes:
@@ -363,6 +431,10 @@ def gemm(a_kc, b_kc, M, N, K, A, lda, B, ldb, out, bias=None, act=0, aux_in=None
         if kid == 5 or kid == 7:                # fp16 forward / dgrad kernel
             if a_amax is None:
                 a_amax = amax_of(A)
+            ar = eval_arithmetic.current
+            if ar is not None and precision is None:
+                prec = eval_launch_precision(ar.name, prec, kid, _autograd_off(), a_drop.on or row_skip.on)
+                ar.switched += prec == 7
         elif kid == 6:                          # fp16 weight-gradient kernel
             if a_amax is None:
                 a_amax = amax_of(A)
@@ -696,7 +768,7 @@ class ActSink:
         return None if t is None else getattr(t, "_npvp_sink", None)
 
 
-class _FanOut(torch.autograd.Function):
+class _FanOut(_Function):
     @staticmethod
     def forward(ctx, t, sink):
         ctx.sink = sink
@@ -734,7 +806,7 @@ def broadcast_mid(x, B, scale=1.0):
 
 
 # --------------------------------------------------------------------------- autograd Functions
-class _Transpose(torch.autograd.Function):
+class _Transpose(_Function):
     @staticmethod
     def forward(ctx, x):
         remember(ctx)
@@ -745,7 +817,7 @@ class _Transpose(torch.autograd.Function):
         return transpose(g)
 
 
-class _MeanMid(torch.autograd.Function):
+class _MeanMid(_Function):
     """[A,B,C] -> [A,C] mean over B (event coding = mean over T, ref/models/Predictor.py:346)"""
 
     @staticmethod
@@ -759,7 +831,7 @@ class _MeanMid(torch.autograd.Function):
         return broadcast_mid(g, ctx.B, 1.0 / ctx.B)
 
 
-class _L1Mean(torch.autograd.Function):
+class _L1Mean(_Function):
     """lam * mean|a - b| (ref/models/criterion.py:99-121 with norm_dim None); the gradient goes to `a` only - the second operand of
     the Stage-2 losses is the ground truth.  One fused pass forward, one backward, and no torch reduction: a captured step must not
     contain memset nodes (npvp_hip.h npvp_l1_mean)."""
@@ -793,7 +865,7 @@ def l1_mean(a, b, lam=1.0):
     return _L1Mean.apply(a, b, lam)
 
 
-class _SumAll(torch.autograd.Function):
+class _SumAll(_Function):
     """sum of every element -> device scalar, in a fixed order (npvp_hip.h npvp_sum_all)"""
 
     @staticmethod
@@ -815,7 +887,7 @@ def sum_all(x):
     return _SumAll.apply(x)
 
 
-class _LayerNorm(torch.autograd.Function):
+class _LayerNorm(_Function):
     @staticmethod
     def forward(ctx, x, w, b, eps, relu):
         remember(ctx)
@@ -868,7 +940,7 @@ def layernorm(x, w, b, eps=1e-5, relu=False):
     return _LayerNorm.apply(x, w, b, eps, relu)
 
 
-class _LayerNormNchw(torch.autograd.Function):
+class _LayerNormNchw(_Function):
     """LayerNorm(C) (+ReLU) over the token rows of canonical x [F, 64, C], result in the reference's (N,T,C,H,W) layout
     (ref VidHRFormer.py:150-159): one forward kernel instead of LayerNorm + transpose."""
 
@@ -909,7 +981,7 @@ def layernorm_nchw(x, w, b, eps, relu, N, T, H, W):
     return _LayerNormNchw.apply(x, w, b, eps, relu, N, T, H, W)
 
 
-class _LayerNormRes(torch.autograd.Function):
+class _LayerNormRes(_Function):
     """(x, LN(x)) for the pre-norm residual pattern  x + f(LN(x))  of every sub-layer (ref VidHRFormer.py:87-112).
     Returning x through the Function lets backward fold the residual branch's gradient into the LayerNorm backward
     kernel (dx = d_residual + LN'(dy)) instead of leaving a separate [R, C] add to autograd."""
@@ -940,7 +1012,7 @@ def layernorm_res(x, w, b, eps=1e-5):
     return _LayerNormRes.apply(x, w, b, eps)
 
 
-class _PosFuse(torch.autograd.Function):
+class _PosFuse(_Function):
     """y = GroupNorm1(x + add) * (1 + gamma) + beta on [N*T, PF] frames (ref submodules.py:432-454)."""
 
     @staticmethod
@@ -1001,7 +1073,7 @@ def posfuse(x, add, beta, gamma, N, T):
     return _PosFuse.apply(x, add, beta, gamma, N, T)
 
 
-class _PosFuseInstance(torch.autograd.Function):
+class _PosFuseInstance(_Function):
     """PosFeatFuser with param_free_norm_type='instance' (ref submodules.py:427-431): statistics per (frame, channel) over the
     H*W pixels.  x (N,T,H,W,C) channels-last; beta / gamma [T*H*W, C]; add (N,H,W,C) or None."""
 
@@ -1045,7 +1117,7 @@ def posfuse_instance(x, add, beta, gamma, N, T):
     return _PosFuseInstance.apply(x, add, beta, gamma, N, T)
 
 
-class _Linear(torch.autograd.Function):
+class _Linear(_Function):
     """y = residual + drop(x w^T + b): nn.Linear / 1x1 conv / MHA projections with the residual add
     and the dropout / drop-path that follows them in the reference fused into the GEMM epilogue."""
 
@@ -1137,7 +1209,7 @@ def linear(x, w, b=None, residual=None, drop=NO_DROP, frame_stats=False):
     return _Linear.apply(x, w, b, residual, drop, bool(frame_stats))
 
 
-class _FFN(torch.autograd.Function):
+class _FFN(_Function):
     """out = x + drop3(linear2(drop2(GELU(linear1(xn)))))  (ref/models/VidHRFormer.py:110-112,224-226):
     two GEMMs; bias+GELU+dropout and bias+dropout+residual live in their epilogues, and in backward the
     GELU'/dropout product is the epilogue of the dgrad GEMM."""
@@ -1319,7 +1391,7 @@ def _attn_bwd(q, k, v, go, dq, dk, dv, cfg, packed=None):
     tag_amax(dv, sv)
 
 
-class _AttnPacked(torch.autograd.Function):
+class _AttnPacked(_Function):
     """Self-attention core on a packed [R, 2C] q|k projection and a [R, C] v projection."""
 
     @staticmethod
@@ -1345,7 +1417,7 @@ class _AttnPacked(torch.autograd.Function):
         return dqk, dv, None
 
 
-class _Attn(torch.autograd.Function):
+class _Attn(_Function):
     """Attention core with separate q [Rq,C], k [Rk,C], v [Rk,C] (the enc-dec site)."""
 
     @staticmethod
@@ -1424,7 +1496,7 @@ def _fln_pgrad(dout, h, mean, rstd, w, b, frames, PF, d, sk):
     return psum, dw, db
 
 
-class _FrameLnAct(torch.autograd.Function):
+class _FrameLnAct(_Function):
     """out = res + droppath_n(drop(GELU(LayerNorm((Ch,H,W))(h))))   (ref VidHRFormer.py:381-382,384-386,388-390)"""
 
     @staticmethod
@@ -1470,7 +1542,7 @@ def frameln_act(h, w_cl, b_cl, res, frames, p_drop=0.0, p_dp=0.0, frames_per_sam
     return _FrameLnAct.apply(h, w_cl, b_cl, res, frames, p_drop, p_dp, frames_per_sample, mean, rstd)
 
 
-class _DwConv(torch.autograd.Function):
+class _DwConv(_Function):
     """Depthwise 3x3 on [F, H*W, Ch]; wtb = [10, Ch]: 9 tap-major weight rows + the bias row."""
 
     @staticmethod
@@ -1515,7 +1587,7 @@ def dwconv3x3(a, wtb, frames, H, W, want_stats=False):
     return _DwConv.apply(a, wtb, frames, H, W, bool(want_stats))
 
 
-class _MlpDwbn(torch.autograd.Function):
+class _MlpDwbn(_Function):
     """The whole conv feed-forward sub-layer body of the reference's MlpDWBN (ref/models/VidHRFormer.py:374-392) as ONE
     autograd node:  out = res + droppath(drop(GELU(norm3(fc2(drop(GELU(norm2(dw3x3(GELU(norm1(fc1(x))))))))))))
     Forward = 6 launches + 3 tiny statistics merges: fc1 GEMM (frame statistics in its epilogue) -> fused middle (norm1 +
@@ -1812,7 +1884,7 @@ def _zero_tail(cfg, *ts):
             _raw_grid_pad(None, _ZeroRows(t.shape[0] - body), want_amax=False, out=t[body:])
 
 
-class _GridPad(torch.autograd.Function):
+class _GridPad(_Function):
     @staticmethod
     def forward(ctx, x2, cfg):
         remember(ctx)
@@ -1825,7 +1897,7 @@ class _GridPad(torch.autograd.Function):
         return _raw_grid_cut(_c(g), ctx.cfg), None
 
 
-class _GridCut(torch.autograd.Function):
+class _GridCut(_Function):
     @staticmethod
     def forward(ctx, xp, cfg):
         remember(ctx)
@@ -1879,7 +1951,7 @@ def _raw_evt_split(y2, N, T, P, want_x=True, want_last=True, want_amax=True):
     return (None if x is None else tag_amax(x, sx)), (None if last is None else tag_amax(last, sl))
 
 
-class _EvtJoin(torch.autograd.Function):
+class _EvtJoin(_Function):
     """x (N,T,...,C) + token ((1,...,C) shared by the clips, (N,...,C) one per clip, or None: a zero frame) -> (N,T+1,...,C).
     Backward: the split; a shared token's gradient is the fixed-order sum of `last` over the clips (npvp_reduce_mid) and goes back
     through autograd, which orders the contributions of the two encoder passes of a stochastic step."""
@@ -1907,7 +1979,7 @@ class _EvtJoin(torch.autograd.Function):
         return (None if dx is None else dx.view(N, T, *g.shape[2:])), (dlast.view(tshape) if want_t else None)
 
 
-class _EvtSplit(torch.autograd.Function):
+class _EvtSplit(_Function):
     """y (N,T+1,...,C) -> x (N,T,...,C), last [N, P, C] (want_x False: last alone; x is then an empty tensor).  Backward: the join of
     the two gradients, an output without a gradient counting as zeros."""
 
@@ -1984,7 +2056,7 @@ def linear_any_rows(x, w, b=None):
     return grid_cut(linear(grid_pad(x, tail), w, b), tail)
 
 
-class _SelfAttnSublayer(torch.autograd.Function):
+class _SelfAttnSublayer(_Function):
     """y = x + drop(out_proj(attn(q = k = fuse(LN(x) [+ add]), v = LN(x))))   - spatial-window or temporal self-attention
     (ref/models/VidHRFormer.py:87-88,94-107,210-212,217-221): LN, positional fuse (2 kernels), q|k GEMM, v GEMM, attention
     core, out-projection GEMM with the dropout / drop-path + residual epilogue."""
@@ -2058,7 +2130,7 @@ class _SelfAttnSublayer(torch.autograd.Function):
         return (dx.view(xshape), glw, glb, None, dbeta, dgamma, dadd, gwqk, gbqk, gwv, gbv, gwo, gbo, None, None, None, None)
 
 
-class _CrossAttnSublayer(torch.autograd.Function):
+class _CrossAttnSublayer(_Function):
     """y = x + droppath_t(out_proj(attn(q = fuse(LN(x) + add), k = key, v = memory)))   - the decoder's encoder-decoder
     attention (ref/models/VidHRFormer.py:229-239); key = fuse(memory) is layer invariant and supplied by the caller."""
 
@@ -2118,7 +2190,7 @@ class _CrossAttnSublayer(torch.autograd.Function):
                 None, None, None, None)
 
 
-class _FfnSublayer(torch.autograd.Function):
+class _FfnSublayer(_Function):
     """y = x + drop3(linear2(drop2(GELU(linear1(LN(x))))))   (ref/models/VidHRFormer.py:110-112,224-226)"""
 
     @staticmethod
@@ -2217,7 +2289,7 @@ def ffn_sublayer(x, norm, lin1, lin2, p):
     return _FfnSublayer.apply(x, norm.weight, norm.bias, norm.eps, lin1.weight, lin1.bias, lin2.weight, lin2.bias, p)
 
 
-class _Im2Col(torch.autograd.Function):
+class _Im2Col(_Function):
     """[F, H*W, C] -> [F*H*W, 9*C] patches of a 3x3 / pad-1 conv (tap-major columns); backward = col2im."""
 
     @staticmethod
@@ -2270,7 +2342,7 @@ def mean_mid(x):
 
 
 # --------------------------------------------------------------------------- frozen autoencoder epilogues (csrc/ae.hip)
-class _BiasAct(torch.autograd.Function):
+class _BiasAct(_Function):
     """out = act(x + bias[c]) (+ residual) on an (N,C,H,W) tensor in contiguous or channels_last memory; bias is frozen.
     Gradient w.r.t. x only (the decoder's input-gradient path), through the saved OUTPUT."""
 
@@ -2325,7 +2397,7 @@ def _memory_format(layout):
     return torch.channels_last if layout == 0 else torch.contiguous_format
 
 
-class _BnActTrain(torch.autograd.Function):
+class _BnActTrain(_Function):
     """BatchNorm2d (batch statistics in training, running statistics in eval) -> act (0 none, 1 ReLU) [-> + residual] as one
     statistics pass and one apply pass forward, one sum pass and one dx pass backward (npvp_bn_*).
     group (training mode only; synchronised BatchNorm, Lightning's sync_batchnorm=True, ref/train_AutoEncoder_lightning.py:40-42):
@@ -2417,7 +2489,7 @@ def bn_act_train(x, w, b, running_mean=None, running_var=None, momentum=0.1, eps
 _NL_GRID = {8: 64, 16: 32, 32: 16, 64: 8}        # attention dim A -> side of the AE configs' square grid at C = 8 A; value dim = 4 A
 
 
-class _NonLocalAttn(torch.autograd.Function):
+class _NonLocalAttn(_Function):
     """softmax(q k^T) v of NonLocalAttenion2D (unscaled scores, 2x2 max-pooled keys / values) from ONE projection tensor
     qkv [F*H*W, ld] = [q | k | v | zero padding]; the gradient comes back in the same layout.  export: "npvp_nonlocal_attn" (the AE
     configs' grids) or "npvp_nonlocal_attn_grid" (any H x W: floor pooling, the never-pooled last line / column of an odd grid gets
@@ -2509,7 +2581,7 @@ def nonlocal_attn_grid(q, k, v, H, W):
     return _nl_unpacked(nonlocal_attn_grid_packed, "nonlocal_attn_grid", q, k, v, H, W)
 
 
-class _ReflectPad(torch.autograd.Function):
+class _ReflectPad(_Function):
     """ReflectionPad2d(P) forward, gather-form backward (npvp_reflect_pad)"""
 
     @staticmethod

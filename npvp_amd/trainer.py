@@ -347,12 +347,14 @@ def full_val_step(predictor, enc, dec, past_frames, future_frames, lam_PF_L1=0.0
                               future_frames=future_frames, sync=sync)
 
 
-def predictor_sample_step(predictor, past_feats, n_samples, seed=None, frozen_dec=None, chunk=None, sample_base=0, return_eps=False):
+def predictor_sample_step(predictor, past_feats, n_samples, seed=None, frozen_dec=None, chunk=None, sample_base=0, return_eps=False,
+                          arithmetic=None):
     """n_samples futures per clip from a stochastic predictor (Predictor.sample): -> predicted features (N, S, Tp, C, H, W), or the
     frames (N, S, Tp, c, h, w) of `frozen_dec` when one is given.  chunk (None = all at once): the samples are decoded `chunk` at a
     time, one piece after the other - the encoder / prior part still runs ONCE for all pieces, and a sample's latent does not depend
     on the cut (the pieces only see other GEMM row counts: rounding).  return_eps: also eps and z, each [S, N, H*W, C].  Eval
-    behaviour under no_grad; the module's train / eval state is restored (as predictor_val_step does)."""
+    behaviour under no_grad; the module's train / eval state is restored (as predictor_val_step does).  arithmetic: as in
+    Predictor.sample ("f16x1": the predictor's forward GEMMs in the one-term fp16 arithmetic; None: the call as it always was)."""
     if not predictor.stochastic:
         raise ValueError("predictor_sample_step needs a stochastic predictor (stochastic=True)")
     S = int(n_samples)
@@ -362,7 +364,7 @@ def predictor_sample_step(predictor, past_feats, n_samples, seed=None, frozen_de
     was_training = predictor.training
     predictor.eval()
     try:
-        with torch.no_grad():
+        with torch.no_grad(), ops.arithmetic_scope(arithmetic):
             ctx = predictor.sample_context(past_feats)
             seed_t = predictor.sample_seed_tensor(seed, past_feats.device)
             preds, epss, zs = [], [], []
@@ -385,14 +387,14 @@ def predictor_sample_step(predictor, past_feats, n_samples, seed=None, frozen_de
     return pred
 
 
-def full_sample_step(predictor, enc, dec, past_frames, n_samples, seed=None, chunk=None, sample_base=0, return_eps=False):
+def full_sample_step(predictor, enc, dec, past_frames, n_samples, seed=None, chunk=None, sample_base=0, return_eps=False, arithmetic=None):
     """predictor_sample_step from pixels: frozen encoder on the past frames, n_samples sampled futures, frozen decoder ->
     frames (N, S, Tp, c, h, w)."""
     enc.eval(); dec.eval()
     with torch.no_grad():
         past_feats = enc(past_frames)
     return predictor_sample_step(predictor, past_feats, n_samples, seed, frozen_dec=dec, chunk=chunk, sample_base=sample_base,
-                                 return_eps=return_eps)
+                                 return_eps=return_eps, arithmetic=arithmetic)
 
 
 # ---- batch shaping of the reference's other Stage-2 modes (ref/models/Predictor.py:30-40,62-70,241-262 and the
