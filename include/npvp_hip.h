@@ -656,6 +656,23 @@ int npvp_nonlocal_attn_grid_bwd(const float* q, long long ldq, const float* k, l
                                 const float* go, long long ldgo, const float* lse, float* D, float* dq, long long lddq,
                                 float* dk, long long lddk, float* dv, long long lddv, int F, int H, int W, int A, int V,
                                 npvp_stream_t stream);
+/* Temporal non-local attention: the core of NonLocalAttenion1D.forward (ref/models/submodules.py:221-243) as Factorized3DConvAttn
+ * (learn_3d=True, :62-66, :86-91) applies it to the T frames of every pixel: o = softmax(q k^T) v over a pixel's T rows, scores NOT
+ * scaled, one head.  Operands are read in place from channels-last token rows: row(n, t, p) = (n*T + t)*HW + p for clip n < N, frame
+ * t < T, pixel p < HW; q [rows][ldq] and k [rows][ldk] (first A columns), v [rows][ldv] and o [rows][ldo] (first V columns),
+ * lse [rows] saved for the backward.  (A, V) in {(8,32), (16,64), (32,128), (64,256)}; 1 <= T <= 32 (a pixel's T x T scores are
+ * not tiled over the keys; every shipped clip length is <= 30); N, HW >= 1; N*T*HW < 2^31; leading dimensions multiples of 4
+ * floats and pointers 16-byte aligned (float4 accesses).  Anything else returns -1 with the entry point's name and the offending
+ * value in npvp_last_error.
+ * bwd: P is recomputed from q, k and lse and its row normalised (Phat = P / sum P); D = rowsum(Phat * dP).  A pixel's dq, dk and dv
+ * depend on that pixel's rows only, so one kernel writes all three: no workspace, no atomics, no memset, every element of
+ * dq / dk / dv (first A / A / V columns of their rows) written exactly once, bit-identical on repeated runs.  dq / dk / dv may be
+ * column slices of one buffer.  At T = 1: o = v, dq = dk = 0, dv = go exactly. */
+int npvp_temporal_attn_fwd(const float* q, long long ldq, const float* k, long long ldk, const float* v, long long ldv, float* o,
+                           long long ldo, float* lse, int N, int T, int HW, int A, int V, npvp_stream_t stream);
+int npvp_temporal_attn_bwd(const float* q, long long ldq, const float* k, long long ldk, const float* v, long long ldv, const float* go,
+                           long long ldgo, const float* lse, float* dq, long long lddq, float* dk, long long lddk, float* dv,
+                           long long lddv, int N, int T, int HW, int A, int V, npvp_stream_t stream);
 
 /* ---- the data-parallel exchange: all-reduce(mean) of the parameter gradients, RCCL over xGMI, one process per GPU.
  * Replaces what the reference gets from Lightning's DDP strategy (ref/train_Predictor_lightning.py:40-42: strategy = 'ddp' over

@@ -412,17 +412,42 @@ class SyncBatchNorm2d(nn.BatchNorm2d):
                                True, syncbn_group())
 
 
+class SyncBatchNorm1d(nn.BatchNorm1d):
+    """The BatchNorm1d counterpart, for the two BatchNorm1d layers of a learn_3d Factorized3DConvAttn block (temporal_conv[1] and
+    attn1d.norm_func, ref/models/submodules.py:34-38), which Lightning's sync_batchnorm=True converts as well.  Same parameters /
+    buffers / state-dict keys as nn.BatchNorm1d."""
+
+    def forward(self, x):
+        if not (active() and self.training):
+            return super().forward(x)
+        if self.num_batches_tracked is not None:
+            self.num_batches_tracked.add_(1)
+        return _SyncBNFn.apply(x, self.weight, self.bias, self.running_mean, self.running_var, self.eps, self.momentum,
+                               True, syncbn_group())
+
+
+def _sync_twin(child, cls):
+    new = cls(child.num_features, child.eps, child.momentum, child.affine, child.track_running_stats)
+    new.weight, new.bias = child.weight, child.bias
+    new.running_mean, new.running_var, new.num_batches_tracked = child.running_mean, child.running_var, child.num_batches_tracked
+    new.train(child.training)
+    return new
+
+
 def convert_sync_batchnorm(module):
-    """Swap every nn.BatchNorm2d under `module` for SyncBatchNorm2d in place (parameters and buffers are shared).
+    """Swap every nn.BatchNorm2d under `module` for SyncBatchNorm2d in place (parameters and buffers are shared), and the two
+    BatchNorm1d layers of every learn_3d Factorized3DConvAttn block for SyncBatchNorm1d; any other BatchNorm1d is left alone.
     Collective on first use: every rank must call it (it creates the SyncBatchNorm process group)."""
+    from .models.ResNetAutoEncoder import Factorized3DConvAttn
     syncbn_group()
+    if isinstance(module, Factorized3DConvAttn) and module.learn_3d:
+        if isinstance(module.temporal_conv, nn.Sequential) and type(module.temporal_conv[1]) is nn.BatchNorm1d:
+            module.temporal_conv[1] = _sync_twin(module.temporal_conv[1], SyncBatchNorm1d)
+        if type(module.attn1d.norm_func) is nn.BatchNorm1d:
+            module.attn1d.norm_func = _sync_twin(module.attn1d.norm_func, SyncBatchNorm1d)
     for name, child in list(module.named_children()):
         if type(child) is nn.BatchNorm2d:
-            new = SyncBatchNorm2d(child.num_features, child.eps, child.momentum, child.affine, child.track_running_stats)
-            new.weight, new.bias = child.weight, child.bias
-            new.running_mean, new.running_var, new.num_batches_tracked = child.running_mean, child.running_var, child.num_batches_tracked
-            new.train(child.training)
-            setattr(module, name, new)
+            setattr(module, name, _sync_twin(child, SyncBatchNorm2d))
         else:
             convert_sync_batchnorm(child)
     return module

@@ -4,7 +4,8 @@ FULL training step of Stage 2: frozen encoder on past+future frames (no grad), f
 predicted features with the gradient flowing through it to the predictor (ref/models/Predictor.py:172-194).
 
 SURVEY 8f "next" row #1.  Same class names, constructor signatures and state-dict keys as the reference, so Stage-1
-checkpoints load.  Only the `learn_3d=False` configuration (every shipped config) is supported.
+checkpoints load.  `learn_3d=True` adds the temporal half of every Factorized3DConvAttn block (Conv1d over the T frames of a pixel
++ NonLocalAttenion1D, ref/models/submodules.py:30-38, 62-66, 86-91, 182-255).
   stage 1: the modules as built run on stock PyTorch-ROCm (MIOpen convolutions, rocBLAS matmuls);
   stage 2: `to_device_layout` -> `fuse_frozen_autoencoder`: the pair is frozen and in eval mode in Stage 2, so every
            conv -> BatchNorm -> ReLU (-> + skip) group becomes a `FoldedConvAct`: the convolution with the BatchNorm folded
@@ -99,6 +100,18 @@ def fuse_frozen_autoencoder(enc, dec):
                     a.out_proj.weight.mul_(s.view(-1, 1))
                     a.out_proj.bias.copy_(a.out_proj.bias * s + t)
                     a.norm_func = nn.Identity()
+                if mod.learn_3d:
+                    mod.temporal_conv = FoldedTemporalConvAct(mod.temporal_conv[0], mod.temporal_conv[1] if isinstance(
+                        mod.temporal_conv[1], nn.BatchNorm1d) else None, mod.temporal_conv[2])
+                    a = mod.attn1d
+                    if isinstance(a.norm_func, nn.BatchNorm1d):      # ... and the BatchNorm1d behind attn1d's out_proj
+                        s, t = _bn_scale_shift(a.norm_func)
+                        a.out_proj.weight.mul_(s.view(-1, 1))
+                        a.out_proj.bias.copy_(a.out_proj.bias * s + t)
+                        a.norm_func = nn.Identity()
+                    zero = lambda lin: lin.bias if lin.bias is not None else torch.zeros(lin.out_features, device=lin.weight.device)
+                    a.register_buffer("_npvp_wqkv", torch.cat([a.Wq.weight, a.Wk.weight, a.Wv.weight], 0).detach().clone(), persistent=False)
+                    a.register_buffer("_npvp_bqkv", torch.cat([zero(a.Wq), zero(a.Wk), zero(a.Wv)], 0).detach().clone(), persistent=False)
             elif isinstance(mod, ResnetBlock):
                 mod.conv_block = _fold_sequential(mod.conv_block)
         dec.model = _fold_sequential(dec.model)
@@ -141,15 +154,81 @@ class NonLocalAttenion2D(nn.Module):
         return x + self.gamma * self.activ_func(self.norm_func(out))
 
 
+class NonLocalAttenion1D(nn.Module):
+    """Self-attention over the T frames of one pixel, x (N*H*W, C, T) (ref/models/submodules.py:182-255; un-scaled scores, one head,
+    no pooling).  (sic: the reference spells it 'Attenion'.)"""
+
+    def __init__(self, in_channels, atten_channels_downsample_ratio=8, value_channels_downsample_ratio=2, bias=True,
+                 learn_gamma=True, norm_func=None, activ_func=None):
+        super().__init__()
+        self.bias, self.in_channels = bias, in_channels
+        self.attn_dim = in_channels // atten_channels_downsample_ratio
+        self.value_dim = in_channels // value_channels_downsample_ratio
+        self.Wq = nn.Linear(in_channels, self.attn_dim, bias=bias)
+        self.Wk = nn.Linear(in_channels, self.attn_dim, bias=bias)
+        self.Wv = nn.Linear(in_channels, self.value_dim, bias=bias)
+        self.out_proj = nn.Linear(self.value_dim, in_channels, bias=bias)
+        self.learn_gamma = learn_gamma
+        self.gamma = nn.Parameter(torch.tensor(0., dtype=torch.float32)) if learn_gamma else 1.0
+        self.norm_func = norm_func if norm_func is not None else nn.Identity()
+        self.activ_func = activ_func if activ_func is not None else nn.Identity()
+        for lin in (self.Wq, self.Wk, self.Wv, self.out_proj):
+            nn.init.xavier_uniform_(lin.weight)
+            if bias:
+                nn.init.constant_(lin.bias, 0.)
+
+    def forward(self, x):
+        tok = x.transpose(1, 2)                                                   # (M, T, C)
+        att = F.softmax(self.Wq(tok) @ self.Wk(tok).transpose(1, 2), dim=-1)      # (M, T, T), un-scaled scores, as the reference
+        out = self.out_proj(att @ self.Wv(tok)).transpose(1, 2)                   # (M, C, T)
+        return x + self.gamma * self.activ_func(self.norm_func(out))
+
+
+class FoldedTemporalConvAct(nn.Module):
+    """Conv1d(C, C, 3, 'same') over T -> BatchNorm1d (eval) -> ReLU (+ skip) of a FROZEN Factorized3DConvAttn on the (N*T, C, H, W)
+    frames themselves: that tensor, channels-last, IS a channels-last (N, C, T, H*W) tensor, the Conv1d a conv2d with a [C, C, 3, 1]
+    filter and padding (1, 0) (zero padding per clip by construction).  BatchNorm folded into the weights, one npvp_bias_act pass."""
+
+    def __init__(self, conv, bn, act):
+        super().__init__()
+        assert isinstance(conv, nn.Conv1d) and conv.groups == 1 and conv.kernel_size == (3,) and conv.stride == (1,) and conv.dilation == (1,)
+        w = conv.weight.detach()
+        b = conv.bias.detach() if conv.bias is not None else torch.zeros(conv.out_channels, dtype=w.dtype, device=w.device)
+        if bn is not None:
+            assert isinstance(bn, nn.BatchNorm1d) and not bn.training and bn.track_running_stats, "fold needs an eval-mode BatchNorm1d"
+            s, t = _bn_scale_shift(bn)
+            w = w * s.view(-1, 1, 1)
+            b = b * s + t
+        self.register_buffer("weight", w.unsqueeze(-1).contiguous(memory_format=torch.channels_last))        # [C, C, 3, 1]
+        self.register_buffer("bias", b.detach().float().contiguous())
+        self.act = 0 if act is None else _ACT_CODE[type(act)]
+
+    def forward(self, x, T, residual=None):
+        y = _temporal_view_back(F.conv2d(_temporal_view(x, T), self.weight, None, 1, (1, 0)), x.shape)
+        return ops.bias_act(y, self.bias, self.act, residual)
+
+
+def _temporal_view(x, T):
+    """(N*T, C, H, W) -> (N, C, T, H*W): element (n, c, t, p) is x[n*T + t, c, p / W, p % W].  No copy when x is channels_last (the
+    result is then a channels_last 4-D tensor) - what the reference reaches by reshape + permute + flatten (submodules.py:63)."""
+    NT, C, H, W = x.shape
+    return x.permute(0, 2, 3, 1).reshape(NT // T, T, H * W, C).permute(0, 3, 1, 2)       # (an NCHW x is copied to channels_last here)
+
+
+def _temporal_view_back(y, shape):
+    """inverse of _temporal_view: (N, C, T, H*W) -> (N*T, C, H, W), a view of a channels_last y"""
+    NT, C, H, W = shape
+    return y.permute(0, 2, 3, 1).reshape(NT, H, W, C).permute(0, 3, 1, 2)
+
+
 class Factorized3DConvAttn(nn.Module):
-    """ref/models/submodules.py:9-95 with learn_3d=False: conv3x3+BN+ReLU (+skip) -> NonLocalAttenion2D -> +skip."""
+    """ref/models/submodules.py:9-95: conv3x3+BN+ReLU (+skip) -> NonLocalAttenion2D [-> per pixel over its T frames: Conv1d+BN+ReLU
+    (+skip) -> NonLocalAttenion1D, with learn_3d] -> +skip; conv_first=False runs each attention before its convolution."""
 
     def __init__(self, in_channels, atten_channels_downsample_ratio=8, value_channels_downsample_ratio=2, use_bias=True,
                  learn_gamma=True, norm_layer_2d=nn.BatchNorm2d, norm_layer_1d=nn.BatchNorm1d, activ_func=nn.ReLU(),
                  conv_first=True, learn_3d=True):
         super().__init__()
-        if learn_3d:
-            raise NotImplementedError("learn_3d=True (temporal conv + 1-D attention) is not used by any shipped config")
         self.in_channels, self.learn_3d, self.conv_first = in_channels, learn_3d, conv_first
         self.spatial_conv = nn.Sequential(nn.Conv2d(in_channels, in_channels, kernel_size=3, stride=1, padding=1, bias=use_bias),
                                           norm_layer_2d(in_channels), activ_func)
@@ -157,17 +236,57 @@ class Factorized3DConvAttn(nn.Module):
                                          learn_gamma, norm_layer_2d(in_channels), activ_func=activ_func)
         self.temporal_conv = None
         self.attn1d = None
+        if learn_3d:
+            self.temporal_conv = nn.Sequential(nn.Conv1d(in_channels, in_channels, kernel_size=3, stride=1, padding='same', bias=use_bias),
+                                               norm_layer_1d(in_channels), activ_func)
+            self.attn1d = NonLocalAttenion1D(in_channels, atten_channels_downsample_ratio, value_channels_downsample_ratio, True,
+                                             learn_gamma, norm_layer_1d(in_channels), activ_func=activ_func)
 
-    def forward(self, x, T):
+    def _spatial(self, x):
         if isinstance(self.spatial_conv, FoldedConvAct):       # fused: relu(conv + b) + x in the epilogue pass
             if self.conv_first:
-                return self.attn2d(self.spatial_conv(x, residual=x)) + x
+                return self.attn2d(self.spatial_conv(x, residual=x))
             y = self.attn2d(x)
-            return self.spatial_conv(y, residual=y) + x
+            return self.spatial_conv(y, residual=y)
         if self.conv_first:
-            return self.attn2d(self.spatial_conv(x) + x) + x
+            return self.attn2d(self.spatial_conv(x) + x)
         y = self.attn2d(x)
-        return self.spatial_conv(y) + y + x
+        return self.spatial_conv(y) + y
+
+    def _temporal(self, x, T):
+        """the learn_3d half (ref submodules.py:62-66, 86-91) on x (N*T, C, H, W)"""
+        if isinstance(self.temporal_conv, FoldedTemporalConvAct):      # fused, on the frames in place (no permute copy)
+            if self.conv_first:
+                return _fused_attn1d(self.attn1d, self.temporal_conv(x, T, residual=x), T)
+            y = _fused_attn1d(self.attn1d, x, T)
+            return self.temporal_conv(y, T, residual=y)
+        NT, C, H, W = x.shape
+        N = NT // T
+        y = x.reshape(N, T, C, H, W).permute(0, 3, 4, 2, 1).flatten(0, 2)          # (N*H*W, C, T)
+        if self.conv_first:
+            y = self.attn1d(self.temporal_conv(y) + y)
+        else:
+            y = self.attn1d(y)
+            y = self.temporal_conv(y) + y
+        return y.reshape(N, H, W, C, T).permute(0, 4, 3, 1, 2).flatten(0, 1)
+
+    def forward(self, x, T):
+        y = self._spatial(x)
+        if self.learn_3d:
+            y = self._temporal(y, T)
+        return y + x
+
+
+def _fused_attn1d(a, x, T):
+    """NonLocalAttenion1D of a fused (frozen, eval) pair on the frames x (N*T, C, H, W): on the device the channels-last rows go
+    through the temporal attention kernel (ops.temporal_attn_packed); BatchNorm1d is already folded into out_proj"""
+    NT, C, H, W = x.shape
+    A, V = a.attn_dim, a.value_dim
+    tok = x.permute(0, 2, 3, 1).reshape(NT * H * W, C)                  # a view when x is channels_last
+    qkv = F.linear(tok, a._npvp_wqkv, a._npvp_bqkv)
+    o = ops.temporal_attn_packed(qkv, NT // T, T, H * W, A, V)
+    out = a.out_proj(o).view(NT, H, W, C).permute(0, 3, 1, 2)
+    return x + a.gamma * a.activ_func(a.norm_func(out))
 
 
 class ResnetBlock(nn.Module):

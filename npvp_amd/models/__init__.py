@@ -4,5 +4,6 @@ from .VidHRFormer import (VidHRformerDecoderNAR, VidHRFormerEncoder, VidHRFormer
                           SpatialLocalMultiheadAttention, MlpDWBN, MultiheadAttention, DropPath)
 from .submodules import CoorGenerator, NRMLP, PosFeatFuser, EventEncoder
 from .Predictor import Predictor
-from .ResNetAutoEncoder import ResnetEncoder, ResnetDecoder, ResnetBlock, Factorized3DConvAttn, NonLocalAttenion2D, build_frozen_autoencoder, to_device_layout
+from .ResNetAutoEncoder import (ResnetEncoder, ResnetDecoder, ResnetBlock, Factorized3DConvAttn, NonLocalAttenion2D, NonLocalAttenion1D,
+                                build_frozen_autoencoder, to_device_layout)
 from .ae_train import build_autoencoder, prepare_trainable_autoencoder

@@ -5,6 +5,10 @@ the same state-dict keys, run through the HIP ops of csrc/ae_train.hip instead o
   NonLocalAttenion2D                        ->  one GEMM for [Wq | Wk | Wv] (ops.linear), ops.nonlocal_attn_packed at the configs' own grids,
                                                ops.nonlocal_attn_grid_packed at any other (pooling fused, no score matrix in
                                                HBM), out_proj (ops.linear), ops.bn_act_train + ReLU, x + gamma * h
+  learn_3d: temporal_conv                   ->  the Conv1d over T as a conv2d with a [C, C, 3, 1] filter on the channels-last frames viewed as
+                                               (N, C, T, H*W) (MIOpen, no permute copy), BatchNorm1d through the same ops.bn_act_train
+            NonLocalAttenion1D              ->  one GEMM for [Wq | Wk | Wv], ops.temporal_attn_packed on the same token rows (csrc/ae_temporal.hip),
+                                               out_proj, ops.bn_act_train + ReLU, x + gamma * h
 `prepare_trainable_autoencoder` binds these forwards to the two module INSTANCES; the classes, their forward methods and the frozen
 Stage-2 path (build_frozen_autoencoder / fuse_frozen_autoencoder) are untouched.
 """
@@ -14,7 +18,8 @@ import torch
 import torch.nn as nn
 
 from .. import dp, ops
-from .ResNetAutoEncoder import ResnetEncoder, ResnetDecoder, Factorized3DConvAttn, NonLocalAttenion2D, ResnetBlock
+from .ResNetAutoEncoder import (ResnetEncoder, ResnetDecoder, Factorized3DConvAttn, NonLocalAttenion2D, ResnetBlock, _temporal_view,
+                                _temporal_view_back)
 
 
 def build_autoencoder(AE, img_channels):
@@ -30,13 +35,16 @@ def build_autoencoder(AE, img_channels):
 def _bn(bn, x, act, residual=None):
     """BatchNorm2d (+ ReLU) (+ residual) with nn.BatchNorm2d's own mode logic (ref: torch.nn.modules.batchnorm._BatchNorm.forward).
     A dp.SyncBatchNorm2d in training mode under data parallelism takes its statistics over every rank (Lightning's
-    sync_batchnorm=True, ref/train_AutoEncoder_lightning.py:40-42); a plain BatchNorm2d keeps this rank's own, as torch does."""
+    sync_batchnorm=True, ref/train_AutoEncoder_lightning.py:40-42); a plain BatchNorm2d keeps this rank's own, as torch does.
+    A BatchNorm1d of a learn_3d block (and its dp.SyncBatchNorm1d twin) takes the same call on the (N*T, C, H, W) frames with its own
+    parameters and buffers: over (N*H*W, C, T) it has the per-channel statistics, and the count of the unbiased running variance,
+    that BatchNorm2d has over those frames."""
     if bn.training and bn.track_running_stats and bn.num_batches_tracked is not None:
         bn.num_batches_tracked.add_(1)
     train = bn.training or bn.running_mean is None
     w = bn.weight if bn.weight is not None else torch.ones(bn.num_features, device=x.device)
     b = bn.bias if bn.bias is not None else torch.zeros(bn.num_features, device=x.device)
-    group = dp.syncbn_group() if isinstance(bn, dp.SyncBatchNorm2d) and bn.training and dp.active() else None
+    group = dp.syncbn_group() if isinstance(bn, (dp.SyncBatchNorm2d, dp.SyncBatchNorm1d)) and bn.training and dp.active() else None
     return ops.bn_act_train(x, w, b, bn.running_mean, bn.running_var, bn.momentum, bn.eps, act, train, residual, group=group)
 
 
@@ -73,8 +81,9 @@ def _run_seq(seq, x, residual=None):
     return x if residual is None else x + residual
 
 
-def _attn(a, x):
-    """NonLocalAttenion2D.forward (ref/models/submodules.py:150-176) on the HIP path"""
+def _attn_core(a, x, core):
+    """the shared frame of both attentions on the (N', C, H, W) frames x: [Wq | Wk | Wv] GEMM -> core(qkv) -> out_proj -> norm -> ReLU ->
+    x + gamma * h"""
     N, C, H, W = x.shape
     A, V = a.attn_dim, a.value_dim
     tok = x.permute(0, 2, 3, 1).reshape(N * H * W, C)               # a view when x is channels_last
@@ -96,11 +105,7 @@ def _attn(a, x):
     qkv = ops.linear(tok, torch.cat(ws, 0), torch.cat(bs, 0) if bs is not None else None)
     if rpad:
         qkv = qkv[:R]
-    # the configs' own (C, grid) pairs keep their exact-tile kernels; any other grid takes the general ones (an (A, V) that no
-    # kernel has is refused by either op: it stays with the first, as before)
-    other_grid = ops.nonlocal_attn_dims(A, V) and not ops.nonlocal_attn_config_shape(A, V, H, W)
-    nl = ops.nonlocal_attn_grid_packed if other_grid else ops.nonlocal_attn_packed
-    o = nl(qkv, N, H, W, A, V)
+    o = core(qkv, A, V)
     if rpad:
         o = nn.functional.pad(o, (0, 0, 0, rpad))
     out = ops.linear(o, a.out_proj.weight, a.out_proj.bias)
@@ -108,7 +113,7 @@ def _attn(a, x):
         out = out[:R]
     out = out.view(N, H, W, C).permute(0, 3, 1, 2)
     relu = isinstance(a.activ_func, nn.ReLU)
-    if isinstance(a.norm_func, nn.BatchNorm2d):
+    if isinstance(a.norm_func, (nn.BatchNorm2d, nn.BatchNorm1d)):
         h = _bn(a.norm_func, out, 1 if relu else 0)
         if not relu:
             h = a.activ_func(h)
@@ -117,12 +122,49 @@ def _attn(a, x):
     return x + a.gamma * h
 
 
-def _fact(m, x):
-    """Factorized3DConvAttn.forward with learn_3d=False (ref/models/submodules.py:80-95)"""
+def _attn(a, x):
+    """NonLocalAttenion2D.forward (ref/models/submodules.py:150-176) on the HIP path"""
+    N, C, H, W = x.shape
+
+    def core(qkv, A, V):
+        # the configs' own (C, grid) pairs keep their exact-tile kernels; any other grid takes the general ones (an (A, V) that no
+        # kernel has is refused by either op: it stays with the first, as before)
+        other_grid = ops.nonlocal_attn_dims(A, V) and not ops.nonlocal_attn_config_shape(A, V, H, W)
+        nl = ops.nonlocal_attn_grid_packed if other_grid else ops.nonlocal_attn_packed
+        return nl(qkv, N, H, W, A, V)
+    return _attn_core(a, x, core)
+
+
+def _attn1d(a, x, T):
+    """NonLocalAttenion1D.forward (ref/models/submodules.py:221-243) on the HIP path, on the frames x (N*T, C, H, W) themselves: the
+    token rows are those of the 2-D attention, a pixel's T frames lie H*W rows apart"""
+    NT, C, H, W = x.shape
+    return _attn_core(a, x, lambda qkv, A, V: ops.temporal_attn_packed(qkv, NT // T, T, H * W, A, V))
+
+
+def _temporal_conv(m, x, T):
+    """temporal_conv(y) + y of ref/models/submodules.py:64, :89 on the frames x (N*T, C, H, W): Conv1d(k=3, 'same') over the T frames of a
+    pixel is conv2d with the weight viewed as [C, C, 3, 1] and padding (1, 0) on the (N, C, T, H*W) view (zero padding per clip by
+    construction; the gradients reach the Conv1d's parameters through the view); BatchNorm1d + ReLU + skip in one pass"""
+    conv, bn = m.temporal_conv[0], m.temporal_conv[1]
+    if not (isinstance(bn, nn.BatchNorm1d) and isinstance(m.temporal_conv[2], nn.ReLU)):
+        raise NotImplementedError("trainable autoencoder: temporal_conv must be Conv1d, BatchNorm1d, ReLU")
+    y = nn.functional.conv2d(_temporal_view(x, T), conv.weight.unsqueeze(-1), conv.bias, 1, (1, 0))
+    return _bn(bn, _temporal_view_back(y, x.shape), 1, residual=x)
+
+
+def _fact(m, x, T):
+    """Factorized3DConvAttn.forward (ref/models/submodules.py:48-95), both orders, with and without the temporal half"""
     if m.conv_first:
-        return _attn(m.attn2d, _run_seq(m.spatial_conv, x, residual=x)) + x
+        y = _attn(m.attn2d, _run_seq(m.spatial_conv, x, residual=x))
+        if m.learn_3d:
+            y = _attn1d(m.attn1d, _temporal_conv(m, y, T), T)
+        return y + x
     y = _attn(m.attn2d, x)
-    return _run_seq(m.spatial_conv, y, residual=y) + x
+    y = _run_seq(m.spatial_conv, y, residual=y)
+    if m.learn_3d:
+        y = _temporal_conv(m, _attn1d(m.attn1d, y, T), T)
+    return y + x
 
 
 def _encoder_forward(enc, x):
@@ -132,10 +174,10 @@ def _encoder_forward(enc, x):
         x = x.contiguous(memory_format=torch.channels_last)
     x = _run_seq(enc.block1, _run_seq(enc.block0, x))
     for i in range(1, enc.n_downsampling):
-        x = _run_seq(getattr(enc, f'block{i + 1}_conv'), _fact(getattr(enc, f'block{i + 1}_3dConvAttn'), x))
+        x = _run_seq(getattr(enc, f'block{i + 1}_conv'), _fact(getattr(enc, f'block{i + 1}_3dConvAttn'), x, T))
     for i in range(enc.num_res_blocks):
         rb = getattr(enc, f'res_conv_{i}')
-        x = _fact(getattr(enc, f'res_3dConvAttn_{i}'), x)
+        x = _fact(getattr(enc, f'res_3dConvAttn_{i}'), x, T)
         x = _run_seq(rb.conv_block, x, residual=x)
     x = torch.relu(x)
     return x.reshape(N, T, *x.shape[1:])
@@ -163,6 +205,11 @@ def prepare_trainable_autoencoder(enc, dec, channels_last=True):
             raise RuntimeError("prepare_trainable_autoencoder: this pair has been fused for the frozen Stage-2 path")
         if isinstance(m, nn.BatchNorm2d) and m.momentum is None:
             raise NotImplementedError("prepare_trainable_autoencoder: BatchNorm2d(momentum=None) is not supported")
+        if isinstance(m, nn.BatchNorm1d) and m.momentum is None:
+            raise NotImplementedError("prepare_trainable_autoencoder: BatchNorm1d(momentum=None) is not supported")
+        if isinstance(m, Factorized3DConvAttn) and m.learn_3d and not ops.nonlocal_attn_dims(m.attn1d.attn_dim, m.attn1d.value_dim):
+            raise NotImplementedError(f"prepare_trainable_autoencoder: attn1d's (attn dim, value dim) = ({m.attn1d.attn_dim}, "
+                                      f"{m.attn1d.value_dim}) is not one of {ops.temporal_attn_dims()}")
     enc.forward = types.MethodType(_encoder_forward, enc)
     dec.forward = types.MethodType(_decoder_forward, dec)
     enc._npvp_trainable = dec._npvp_trainable = True

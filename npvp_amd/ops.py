@@ -2581,6 +2581,75 @@ def nonlocal_attn_grid(q, k, v, H, W):
     return _nl_unpacked(nonlocal_attn_grid_packed, "nonlocal_attn_grid", q, k, v, H, W)
 
 
+TEMPORAL_ATTN_MAX_T = 32        # npvp_temporal_attn_*: a pixel's T x T scores are not tiled over the keys
+
+
+class _TemporalAttn(_Function):
+    """softmax(q k^T) v of NonLocalAttenion1D (ref/models/submodules.py:229-237; unscaled scores) over the T frames of every pixel, from
+    ONE projection tensor qkv [N*T*HW, ld] = [q | k | v | zero padding] of channels-last token rows (row = (n T + t) HW + p); the
+    gradient comes back in the same layout, its pad columns zero.  One backward launch writes dq, dk and dv."""
+
+    @staticmethod
+    def forward(ctx, qkv, N, T, HW, A, V):
+        remember(ctx)
+        _chk(qkv)
+        qkv = _c(qkv)
+        ld = qkv.shape[1]
+        o = torch.empty(N * T * HW, V, dtype=torch.float32, device=qkv.device)
+        lse = torch.empty(N * T * HW, dtype=torch.float32, device=qkv.device)
+        p = qkv.data_ptr()
+        check(lib().npvp_temporal_attn_fwd(p, ld, p + 4 * A, ld, p + 8 * A, ld, _ptr(o), V, _ptr(lse), N, T, HW, A, V, _stream()),
+              "npvp_temporal_attn_fwd")
+        ctx.save_for_backward(qkv, lse)
+        ctx.dims = (N, T, HW, A, V)
+        return o
+
+    @scoped
+    def backward(ctx, go):
+        qkv, lse = ctx.saved_tensors
+        N, T, HW, A, V = ctx.dims
+        _chk(go)
+        go = _c(go)
+        ld = qkv.shape[1]
+        dqkv = torch.empty_like(qkv)
+        if ld > 2 * A + V:
+            dqkv[:, 2 * A + V:].zero_()
+        p, d = qkv.data_ptr(), dqkv.data_ptr()
+        check(lib().npvp_temporal_attn_bwd(p, ld, p + 4 * A, ld, p + 8 * A, ld, _ptr(go), V, _ptr(lse), d, ld, d + 4 * A, ld, d + 8 * A, ld,
+                                           N, T, HW, A, V, _stream()), "npvp_temporal_attn_bwd")
+        return dqkv, None, None, None, None, None
+
+
+def temporal_attn_dims():
+    """the (attn dim, value dim) pairs the temporal attention kernels have: the table of the 2-D kernels"""
+    return [(a, 4 * a) for a in _NL_GRID]
+
+
+def temporal_attn_packed(qkv, N, T, HW, A, V):
+    """qkv [N*T*HW, ld >= 2A+V] (columns q | k | v; row = (n T + t) HW + p, the channels-last encoder's token rows) ->
+    softmax(q k^T) v over the T frames of each of the N*HW pixels  [N*T*HW, V]"""
+    if not nonlocal_attn_dims(A, V):
+        raise RuntimeError(f"temporal_attn: (attn dim, value dim) = ({A}, {V}) is not one of {temporal_attn_dims()}")
+    if not 1 <= T <= TEMPORAL_ATTN_MAX_T:
+        raise RuntimeError(f"temporal_attn: T = {T} frames per clip, 1 <= T <= {TEMPORAL_ATTN_MAX_T} (longer clips need key tiling)")
+    if N < 1 or HW < 1 or qkv.dim() != 2 or qkv.shape[0] != N * T * HW or qkv.shape[1] < 2 * A + V:
+        raise RuntimeError(f"temporal_attn: qkv must be [N*T*HW, >= {2 * A + V}] with N, HW >= 1")
+    if qkv.shape[1] % 4:
+        raise RuntimeError(f"temporal_attn: the row length of qkv ({qkv.shape[1]}) must be a multiple of 4")
+    return _TemporalAttn.apply(qkv, N, T, HW, A, V)
+
+
+def temporal_attn(q, k, v, T):
+    """q, k (M, T, a), v (M, T, v) - M sequences of T frames, as NonLocalAttenion1D sees them - -> (M, T, v).  (Packs the rows as
+    one clip of M pixels; the model path hands its token rows to temporal_attn_packed without a copy.)"""
+    M, Tq, A = q.shape
+    V = v.shape[-1]
+    if k.shape != q.shape or v.shape[:2] != q.shape[:2] or Tq != T:
+        raise RuntimeError("temporal_attn: q / k (M, T, a), v (M, T, v)")
+    qkv = torch.cat([q, k, v], 2).transpose(0, 1).reshape(T * M, 2 * A + V)          # row = t M + m
+    return temporal_attn_packed(qkv, 1, T, M, A, V).view(T, M, V).transpose(0, 1)
+
+
 class _ReflectPad(_Function):
     """ReflectionPad2d(P) forward, gather-form backward (npvp_reflect_pad)"""
 

@@ -824,8 +824,8 @@ def ae_optimizer(enc, dec, lr=1e-4):
 def ae_data_parallel(enc, dec, opt, **gradsync_kw):
     """What the reference's Stage-1 trainer gets from `devices=world_size`, the DDP strategy and `sync_batchnorm=True`
     (ref/train_AutoEncoder_lightning.py:40-42), for a prepared pair and its ae_optimizer: the pair (parameters and buffers) broadcast
-    from rank 0, every BatchNorm2d swapped for dp.SyncBatchNorm2d (same state-dict keys; statistics over all ranks in training mode)
-    and a dp.GradSync over the optimiser's flat gradient buffer to pass to ae_train_step.  Collective: every rank calls it, after
+    from rank 0, every BatchNorm2d swapped for dp.SyncBatchNorm2d - and the two BatchNorm1d layers of every learn_3d block for
+    dp.SyncBatchNorm1d - (same state-dict keys; statistics over all ranks in training mode) and a dp.GradSync over the optimiser's flat gradient buffer to pass to ae_train_step.  Collective: every rank calls it, after
     dp.init_distributed().  Without a process group (dp.active() false) nothing is converted and None is returned."""
     from . import dp
     if not dp.active():

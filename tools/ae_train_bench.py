@@ -9,8 +9,11 @@ unchanged - what the data-parallel machinery costs a step beyond its transfers: 
 alternation and every window is reported.
 --size H W trains at H x W frames (each a multiple of 2**n_downsampling) instead of the config's own: off the configs' sizes the
 HIP path's attention runs the any-grid kernels (ops.nonlocal_attn_grid_packed), the stock path materialises its H W x H W / 4 scores.
+--learn-3d flips learn_3d in the chosen config (the shipped dicts stay as they are): every Factorized3DConvAttn block gains its temporal
+Conv1d and NonLocalAttenion1D (csrc/ae_temporal.hip on the HIP path, permute copies + batched matmuls on the stock path); the record
+then also holds the temporal attention kernels' own time per step (forward + backward at every block's shape, timed alone).
 Usage: python tools/ae_train_bench.py --config {BAIR,KTH,KITTI} [--steps 10] [--warmup 3] [--batch B] [--size H W] [--dp] [--repeats R]
-                                      [--paths hip,hip_gs,hip_dp]"""
+                                      [--paths hip,hip_gs,hip_dp] [--learn-3d]"""
 import argparse
 import copy
 import json
@@ -38,19 +41,24 @@ def algorithmic_bytes(enc, dec, frames, H, W):
     dO read + dq, dk, dv written backward (the score matrix stays on chip).  The shapes come from a one-frame probe of COPIES in
     eval mode: the modules passed in are left as they are (running statistics included)."""
     enc, dec = copy.deepcopy(enc).eval(), copy.deepcopy(dec).eval()
-    from npvp_amd.models.ResNetAutoEncoder import NonLocalAttenion2D
+    from npvp_amd.models.ResNetAutoEncoder import NonLocalAttenion2D, NonLocalAttenion1D
     # BatchNorm element counts from the conv outputs of a one-frame probe
     counts = []
 
     def bn_hook(m, inp, out):
         counts.append(inp[0].numel())
-    hs = [m.register_forward_hook(bn_hook) for m in list(enc.modules()) + list(dec.modules()) if isinstance(m, nn.BatchNorm2d)]
+    hs = [m.register_forward_hook(bn_hook) for m in list(enc.modules()) + list(dec.modules()) if isinstance(m, (nn.BatchNorm2d, nn.BatchNorm1d))]
     att = []
 
     def at_hook(m, inp, out):
         N, C, h, w = inp[0].shape
         att.append(h * w * (2 * (C // 8) + C // 2 + C // 2))
     hs += [m.register_forward_hook(at_hook) for m in enc.modules() if isinstance(m, NonLocalAttenion2D)]
+
+    def at1_hook(m, inp, out):
+        M, C, T = inp[0].shape                                  # (pixels of the one-frame probe, C, 1)
+        att.append(M * T * (2 * (C // 8) + C // 2 + C // 2))
+    hs += [m.register_forward_hook(at1_hook) for m in enc.modules() if isinstance(m, NonLocalAttenion1D)]
     with torch.no_grad():
         dec(enc(torch.zeros(1, 1, enc.block0[1].in_channels, H, W)))
     for h in hs:
@@ -58,6 +66,42 @@ def algorithmic_bytes(enc, dec, frames, H, W):
     bn = 4 * frames * sum(n * (1 + 2) + n * 2 + n * 3 for n in counts)           # fwd 3 passes-worth, bwd 5 (residual not counted)
     attn = 4 * frames * sum(e + 2 * e + e for e in att)                            # fwd q,k,v,o ; bwd q,k,v,o,dO + dq,dk,dv
     return bn, attn
+
+
+def temporal_kernel_ms(enc, B, T, H, W, iters=20):
+    """ms per training step spent in the temporal attention kernels alone: forward + backward of ops.temporal_attn_packed at every
+    learn_3d block's (C, grid), timed with device events over `iters` calls each (after 3 warm-up calls), summed over the blocks"""
+    import npvp_amd
+    from npvp_amd.models.ResNetAutoEncoder import Factorized3DConvAttn
+    shapes = []
+
+    def hook(m, inp, out):
+        shapes.append((inp[0].shape[1], inp[0].shape[2] * inp[0].shape[3]))
+    probe = copy.deepcopy(enc).eval()
+    hs = [m.register_forward_hook(hook) for m in probe.modules() if isinstance(m, Factorized3DConvAttn) and m.learn_3d]
+    with torch.no_grad():
+        probe(torch.zeros(1, 1, probe.block0[1].in_channels, H, W))
+    for h in hs:
+        h.remove()
+    total, per = 0.0, []
+    for C, HW in shapes:
+        A, V = C // 8, C // 2
+        ld = 2 * A + V + (-(2 * A + V) % 32)
+        qkv = (0.3 * torch.randn(B * T * HW, ld, device="cuda:0")).requires_grad_()
+        go = torch.randn(B * T * HW, V, device="cuda:0")
+        run = lambda: npvp_amd.ops.temporal_attn_packed(qkv, B, T, HW, A, V).backward(go)
+        for _ in range(3):
+            run()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(iters):
+            run()
+        e1.record()
+        torch.cuda.synchronize()
+        ms = e0.elapsed_time(e1) / iters
+        per.append({"C": C, "HW": HW, "fwd_bwd_ms": round(ms, 4)})
+        total += ms
+    return round(total, 4), per
 
 
 def main():
@@ -73,6 +117,7 @@ def main():
                     help="build every trainer on the process's default scheduling context instead of one context per path")
     ap.add_argument("--dp", action="store_true", help="also time the HIP step on a forced one-rank RCCL group (paths hip_gs, hip_dp)")
     ap.add_argument("--repeats", type=int, default=1, help="timed windows per path, the paths alternating")
+    ap.add_argument("--learn-3d", action="store_true", help="flip learn_3d in the chosen config: the spatio-temporal autoencoder")
     a = ap.parse_args()
     paths = a.paths.split(",") if a.paths else ["stock", "hip"] + (["hip_gs", "hip_dp"] if a.dp else [])
     if not a.dp and any(p in ("hip_gs", "hip_dp") for p in paths):
@@ -86,6 +131,8 @@ def main():
     if not torch.cuda.is_available():
         raise SystemExit("ae_train_bench needs an MI355X")
     cfg = CONFIGS[a.config]
+    if a.learn_3d:
+        cfg = dict(cfg, AE=dict(cfg["AE"], learn_3d=True))
     B, T, ch = a.batch or cfg["B"], cfg["T"], cfg["ch"]
     H, W = a.size or (cfg["S"], cfg["S"])
     down = 2 ** cfg["AE"]["n_downsampling"]
@@ -98,6 +145,9 @@ def main():
     past, fut = x[:, : T // 2].contiguous(), x[:, T // 2:].contiguous()
     out = {"config": a.config, "batch": B, "frames_per_step": B * T, "res": H if H == W else [H, W]}
     out["bn_bytes_per_step"], out["attn_bytes_per_step"] = algorithmic_bytes(enc0, dec0, B * T, H, W)
+    if a.learn_3d:
+        out["learn_3d"] = True
+        out["temporal_attn_kernels_ms_per_step"], out["temporal_attn_kernels"] = temporal_kernel_ms(enc0, B, T, H, W)
     losses, steps = {}, {}
     for path in paths:
         enc, dec = copy.deepcopy(enc0), copy.deepcopy(dec0)
@@ -105,7 +155,7 @@ def main():
             enc, dec = enc.to(dev), dec.to(dev)
             opt = torch.optim.Adam(list(enc.parameters()) + list(dec.parameters()), lr=1e-4, betas=(0.5, 0.999))
 
-            def step():
+            def step(enc=enc, dec=dec, opt=opt):        # (bound now: with --repeats the step outlives this iteration's names)
                 opt.zero_grad()
                 xx = torch.cat([past, fut], 1)
                 loss = (dec(enc(xx)) - xx).abs().mean()
