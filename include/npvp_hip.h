@@ -673,6 +673,20 @@ int npvp_temporal_attn_fwd(const float* q, long long ldq, const float* k, long l
 int npvp_temporal_attn_bwd(const float* q, long long ldq, const float* k, long long ldk, const float* v, long long ldv, const float* go,
                            long long ldgo, const float* lse, float* dq, long long lddq, float* dk, long long lddk, float* dv,
                            long long lddv, int N, int T, int HW, int A, int V, npvp_stream_t stream);
+/* The same core for ANY clip length T >= 1 (N*T*HW < 2^31 is the only bound): same argument rules and refusals, plus the scratch
+ * D [2][N*T*HW] of the backward (row sums of P, then D = rowsum(Phat * dP); non-null, 16-byte aligned, contents undefined on entry).
+ * T <= 32 launches what npvp_temporal_attn_fwd/bwd launch (bit-identical results, D untouched).  Above that the keys are tiled: a
+ * workgroup owns a tile of pixels x a tile of <= 32 frames (16 at (64,256); the clip cut into the fewest equal tiles) and walks the
+ * other side of the T x T scores in tiles of the same size, so LDS per workgroup stays under 64 KB whatever T is.  fwd: one launch, two sweeps over the key tiles (running max
+ * and sum, rescaled when the max rises; then exp(s - m) / l * v).  bwd: two launches - dq per (pixel tile, query tile), which also
+ * writes D; dk and dv per (pixel tile, key tile) over the query tiles.  A key past T has P = 0, a query past T stores and contributes
+ * nothing.  No atomics, no memset, no workspace but D; every element of o / lse / dq / dk / dv written exactly once; sums in tile
+ * order, bit-identical on repeated runs; nothing read or written outside the first A / A / V columns of the operands' rows. */
+int npvp_temporal_attn_long_fwd(const float* q, long long ldq, const float* k, long long ldk, const float* v, long long ldv, float* o,
+                                long long ldo, float* lse, int N, int T, int HW, int A, int V, npvp_stream_t stream);
+int npvp_temporal_attn_long_bwd(const float* q, long long ldq, const float* k, long long ldk, const float* v, long long ldv,
+                                const float* go, long long ldgo, const float* lse, float* D, float* dq, long long lddq, float* dk,
+                                long long lddk, float* dv, long long lddv, int N, int T, int HW, int A, int V, npvp_stream_t stream);
 
 /* ---- the data-parallel exchange: all-reduce(mean) of the parameter gradients, RCCL over xGMI, one process per GPU.
  * Replaces what the reference gets from Lightning's DDP strategy (ref/train_Predictor_lightning.py:40-42: strategy = 'ddp' over

@@ -279,12 +279,13 @@ class Factorized3DConvAttn(nn.Module):
 
 def _fused_attn1d(a, x, T):
     """NonLocalAttenion1D of a fused (frozen, eval) pair on the frames x (N*T, C, H, W): on the device the channels-last rows go
-    through the temporal attention kernel (ops.temporal_attn_packed); BatchNorm1d is already folded into out_proj"""
+    through the temporal attention kernel (ops.temporal_attn_packed, above ops.TEMPORAL_ATTN_MAX_T frames its key-tiled form
+    ops.temporal_attn_long_packed); BatchNorm1d is already folded into out_proj"""
     NT, C, H, W = x.shape
     A, V = a.attn_dim, a.value_dim
     tok = x.permute(0, 2, 3, 1).reshape(NT * H * W, C)                  # a view when x is channels_last
     qkv = F.linear(tok, a._npvp_wqkv, a._npvp_bqkv)
-    o = ops.temporal_attn_packed(qkv, NT // T, T, H * W, A, V)
+    o = ops.temporal_attn_any_packed(qkv, NT // T, T, H * W, A, V)
     out = a.out_proj(o).view(NT, H, W, C).permute(0, 3, 1, 2)
     return x + a.gamma * a.activ_func(a.norm_func(out))
 

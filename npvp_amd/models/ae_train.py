@@ -137,9 +137,10 @@ def _attn(a, x):
 
 def _attn1d(a, x, T):
     """NonLocalAttenion1D.forward (ref/models/submodules.py:221-243) on the HIP path, on the frames x (N*T, C, H, W) themselves: the
-    token rows are those of the 2-D attention, a pixel's T frames lie H*W rows apart"""
+    token rows are those of the 2-D attention, a pixel's T frames lie H*W rows apart.  Clips of more than ops.TEMPORAL_ATTN_MAX_T
+    frames take the key-tiled kernels (ops.temporal_attn_long_packed), every other clip ops.temporal_attn_packed as before"""
     NT, C, H, W = x.shape
-    return _attn_core(a, x, lambda qkv, A, V: ops.temporal_attn_packed(qkv, NT // T, T, H * W, A, V))
+    return _attn_core(a, x, lambda qkv, A, V: ops.temporal_attn_any_packed(qkv, NT // T, T, H * W, A, V))
 
 
 def _temporal_conv(m, x, T):

@@ -2650,6 +2650,74 @@ def temporal_attn(q, k, v, T):
     return temporal_attn_packed(qkv, 1, T, M, A, V).view(T, M, V).transpose(0, 1)
 
 
+class _TemporalAttnLong(_Function):
+    """_TemporalAttn for any clip length (npvp_temporal_attn_long_fwd/bwd): the keys are tiled above TEMPORAL_ATTN_MAX_T frames, at
+    or below it the launches and the bits are _TemporalAttn's.  The backward hands the kernels their scratch D [2][N*T*HW]."""
+
+    @staticmethod
+    def forward(ctx, qkv, N, T, HW, A, V):
+        remember(ctx)
+        _chk(qkv)
+        qkv = _c(qkv)
+        ld = qkv.shape[1]
+        o = torch.empty(N * T * HW, V, dtype=torch.float32, device=qkv.device)
+        lse = torch.empty(N * T * HW, dtype=torch.float32, device=qkv.device)
+        p = qkv.data_ptr()
+        check(lib().npvp_temporal_attn_long_fwd(p, ld, p + 4 * A, ld, p + 8 * A, ld, _ptr(o), V, _ptr(lse), N, T, HW, A, V, _stream()),
+              "npvp_temporal_attn_long_fwd")
+        ctx.save_for_backward(qkv, lse)
+        ctx.dims = (N, T, HW, A, V)
+        return o
+
+    @scoped
+    def backward(ctx, go):
+        qkv, lse = ctx.saved_tensors
+        N, T, HW, A, V = ctx.dims
+        _chk(go)
+        go = _c(go)
+        ld = qkv.shape[1]
+        dqkv = torch.empty_like(qkv)
+        if ld > 2 * A + V:
+            dqkv[:, 2 * A + V:].zero_()
+        D = torch.empty(2 * N * T * HW, dtype=torch.float32, device=qkv.device)
+        p, d = qkv.data_ptr(), dqkv.data_ptr()
+        check(lib().npvp_temporal_attn_long_bwd(p, ld, p + 4 * A, ld, p + 8 * A, ld, _ptr(go), V, _ptr(lse), _ptr(D),
+                                                d, ld, d + 4 * A, ld, d + 8 * A, ld, N, T, HW, A, V, _stream()),
+              "npvp_temporal_attn_long_bwd")
+        return dqkv, None, None, None, None, None
+
+
+def temporal_attn_long_packed(qkv, N, T, HW, A, V):
+    """temporal_attn_packed for any clip length T >= 1: above TEMPORAL_ATTN_MAX_T frames the kernels walk the keys in tiles; a clip
+    that temporal_attn_packed accepts runs temporal_attn_packed's own kernels"""
+    if not nonlocal_attn_dims(A, V):
+        raise RuntimeError(f"temporal_attn_long: (attn dim, value dim) = ({A}, {V}) is not one of {temporal_attn_dims()}")
+    if T < 1:
+        raise RuntimeError(f"temporal_attn_long: T = {T} frames per clip, T >= 1")
+    if N < 1 or HW < 1 or qkv.dim() != 2 or qkv.shape[0] != N * T * HW or qkv.shape[1] < 2 * A + V:
+        raise RuntimeError(f"temporal_attn_long: qkv must be [N*T*HW, >= {2 * A + V}] with N, HW >= 1")
+    if qkv.shape[1] % 4:
+        raise RuntimeError(f"temporal_attn_long: the row length of qkv ({qkv.shape[1]}) must be a multiple of 4")
+    return _TemporalAttnLong.apply(qkv, N, T, HW, A, V)
+
+
+def temporal_attn_long(q, k, v, T):
+    """temporal_attn for any T >= 1: q, k (M, T, a), v (M, T, v) -> (M, T, v)"""
+    M, Tq, A = q.shape
+    V = v.shape[-1]
+    if k.shape != q.shape or v.shape[:2] != q.shape[:2] or Tq != T:
+        raise RuntimeError("temporal_attn_long: q / k (M, T, a), v (M, T, v)")
+    qkv = torch.cat([q, k, v], 2).transpose(0, 1).reshape(T * M, 2 * A + V)          # row = t M + m
+    return temporal_attn_long_packed(qkv, 1, T, M, A, V).view(T, M, V).transpose(0, 1)
+
+
+def temporal_attn_any_packed(qkv, N, T, HW, A, V):
+    """the model's call: temporal_attn_packed up to TEMPORAL_ATTN_MAX_T frames, temporal_attn_long_packed above; both are looked up
+    here, at call time"""
+    op = temporal_attn_packed if T <= TEMPORAL_ATTN_MAX_T else temporal_attn_long_packed
+    return op(qkv, N, T, HW, A, V)
+
+
 class _ReflectPad(_Function):
     """ReflectionPad2d(P) forward, gather-form backward (npvp_reflect_pad)"""
 

@@ -11,9 +11,12 @@ alternation and every window is reported.
 HIP path's attention runs the any-grid kernels (ops.nonlocal_attn_grid_packed), the stock path materialises its H W x H W / 4 scores.
 --learn-3d flips learn_3d in the chosen config (the shipped dicts stay as they are): every Factorized3DConvAttn block gains its temporal
 Conv1d and NonLocalAttenion1D (csrc/ae_temporal.hip on the HIP path, permute copies + batched matmuls on the stock path); the record
-then also holds the temporal attention kernels' own time per step (forward + backward at every block's shape, timed alone).
+then also holds the temporal attention kernels' own time per step (forward + backward at every block's shape, timed alone) next to
+the reference's route for the same core (permute copies to (N H W, T, d) sequences, batched matmuls and softmax, permute back).
+--frames T overrides the config's clip length (like --size its frame size): above ops.TEMPORAL_ATTN_MAX_T = 32 frames the HIP path's
+temporal attention runs the key-tiled kernels (ops.temporal_attn_long_packed), e.g. KTH's evaluation clips of 40 and 50 frames.
 Usage: python tools/ae_train_bench.py --config {BAIR,KTH,KITTI} [--steps 10] [--warmup 3] [--batch B] [--size H W] [--dp] [--repeats R]
-                                      [--paths hip,hip_gs,hip_dp] [--learn-3d]"""
+                                      [--paths hip,hip_gs,hip_dp] [--learn-3d] [--frames T]"""
 import argparse
 import copy
 import json
@@ -69,8 +72,10 @@ def algorithmic_bytes(enc, dec, frames, H, W):
 
 
 def temporal_kernel_ms(enc, B, T, H, W, iters=20):
-    """ms per training step spent in the temporal attention kernels alone: forward + backward of ops.temporal_attn_packed at every
-    learn_3d block's (C, grid), timed with device events over `iters` calls each (after 3 warm-up calls), summed over the blocks"""
+    """ms per training step spent in the temporal attention kernels alone: forward + backward of ops.temporal_attn_packed (above 32
+    frames ops.temporal_attn_long_packed) at every learn_3d block's (C, grid), timed with device events over `iters` calls each (after
+    3 warm-up calls), summed over the blocks; per block also the reference's route for the same core on the same rows (permute copies
+    to (N*HW, T, d), softmax(q k^T) v as batched matmuls, permute back; forward + backward), which the stock path runs"""
     import npvp_amd
     from npvp_amd.models.ResNetAutoEncoder import Factorized3DConvAttn
     shapes = []
@@ -89,17 +94,26 @@ def temporal_kernel_ms(enc, B, T, H, W, iters=20):
         ld = 2 * A + V + (-(2 * A + V) % 32)
         qkv = (0.3 * torch.randn(B * T * HW, ld, device="cuda:0")).requires_grad_()
         go = torch.randn(B * T * HW, V, device="cuda:0")
-        run = lambda: npvp_amd.ops.temporal_attn_packed(qkv, B, T, HW, A, V).backward(go)
-        for _ in range(3):
-            run()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(iters):
-            run()
-        e1.record()
-        torch.cuda.synchronize()
-        ms = e0.elapsed_time(e1) / iters
-        per.append({"C": C, "HW": HW, "fwd_bwd_ms": round(ms, 4)})
+        run = lambda: npvp_amd.ops.temporal_attn_any_packed(qkv, B, T, HW, A, V).backward(go)
+
+        def stock():
+            seq = lambda t: t.reshape(B, T, HW, -1).permute(0, 2, 1, 3).reshape(B * HW, T, -1).contiguous()
+            q, k, v = seq(qkv[:, :A]), seq(qkv[:, A:2 * A]), seq(qkv[:, 2 * A:2 * A + V])
+            o = torch.softmax(q @ k.transpose(1, 2), -1) @ v
+            o.reshape(B, HW, T, V).permute(0, 2, 1, 3).reshape(B * T * HW, V).contiguous().backward(go)
+
+        def timed(fn):
+            for _ in range(3):
+                fn()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(iters):
+                fn()
+            e1.record()
+            torch.cuda.synchronize()
+            return e0.elapsed_time(e1) / iters
+        ms = timed(run)
+        per.append({"C": C, "HW": HW, "T": T, "fwd_bwd_ms": round(ms, 4), "stock_route_fwd_bwd_ms": round(timed(stock), 4)})
         total += ms
     return round(total, 4), per
 
@@ -118,6 +132,7 @@ def main():
     ap.add_argument("--dp", action="store_true", help="also time the HIP step on a forced one-rank RCCL group (paths hip_gs, hip_dp)")
     ap.add_argument("--repeats", type=int, default=1, help="timed windows per path, the paths alternating")
     ap.add_argument("--learn-3d", action="store_true", help="flip learn_3d in the chosen config: the spatio-temporal autoencoder")
+    ap.add_argument("--frames", type=int, default=None, metavar="T", help="frames per clip (default: the config's own clip length)")
     a = ap.parse_args()
     paths = a.paths.split(",") if a.paths else ["stock", "hip"] + (["hip_gs", "hip_dp"] if a.dp else [])
     if not a.dp and any(p in ("hip_gs", "hip_dp") for p in paths):
@@ -133,7 +148,9 @@ def main():
     cfg = CONFIGS[a.config]
     if a.learn_3d:
         cfg = dict(cfg, AE=dict(cfg["AE"], learn_3d=True))
-    B, T, ch = a.batch or cfg["B"], cfg["T"], cfg["ch"]
+    B, T, ch = a.batch or cfg["B"], a.frames or cfg["T"], cfg["ch"]
+    if T < 2:
+        raise SystemExit("--frames: a clip has at least 2 frames (past and future)")
     H, W = a.size or (cfg["S"], cfg["S"])
     down = 2 ** cfg["AE"]["n_downsampling"]
     if H < down or W < down or H % down or W % down:
@@ -143,7 +160,7 @@ def main():
     O.key_hashed_fill(npvp_amd.AEPair(enc0, dec0), 1)
     x = torch.tanh(O.seeded_randn((B, T, ch, H, W), 2)).to(dev)
     past, fut = x[:, : T // 2].contiguous(), x[:, T // 2:].contiguous()
-    out = {"config": a.config, "batch": B, "frames_per_step": B * T, "res": H if H == W else [H, W]}
+    out = {"config": a.config, "batch": B, "frames_per_step": B * T, "frames_per_clip": T, "res": H if H == W else [H, W]}
     out["bn_bytes_per_step"], out["attn_bytes_per_step"] = algorithmic_bytes(enc0, dec0, B * T, H, W)
     if a.learn_3d:
         out["learn_3d"] = True
