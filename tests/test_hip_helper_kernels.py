@@ -18,12 +18,10 @@ import pytest
 import torch
 
 import helper_kernel_cases as H
+from helper_kernel_cases import DEV, PAD, PATTERN, Flat, out_flat  # noqa: F401  (shared with tests/test_hip_hot_kernels.py)
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
-PATTERN = 0x7FC0BEEF          # a quiet NaN with a payload: recognisable, and poison for whoever reads it as a number
-PAD = 8                       # floats in front of and behind every view
 LOG = os.environ.get("NPVP_ERR_LOG")
 
 
@@ -43,37 +41,6 @@ def stream():
 def ok(L, rc, what):
     torch.cuda.synchronize()
     assert rc == 0, f"{what}: rc {rc}: {L.npvp_last_error()}"
-
-
-class Flat:
-    """n floats inside a larger allocation.  kind 'in': NaN around the values; 'out': the bit pattern around (and, without values,
-    in) the view.  shift: floats by which the view starts off 16-byte alignment."""
-
-    def __init__(self, values=None, n=None, kind="in", shift=0):
-        self.n = int(values.numel() if values is not None else n)
-        self.lo = PAD + shift
-        self.base = torch.empty(self.n + 2 * PAD + 4, dtype=torch.float32, device=DEV)
-        if kind == "in":
-            self.base.fill_(float("nan"))
-        else:
-            self.base.view(torch.int32).fill_(PATTERN)
-        self.v = self.base[self.lo:self.lo + self.n]
-        if values is not None:
-            self.v.copy_(values.flatten())
-        self.ptr = self.v.data_ptr()
-        assert self.ptr % 16 == 4 * (shift % 4)
-
-    def intact(self):
-        i = self.base.view(torch.int32)
-        return bool((i[:self.lo] == PATTERN).all()) and bool((i[self.lo + self.n:] == PATTERN).all())
-
-    def cpu(self, *shape):
-        t = self.v.cpu()
-        return t.reshape(shape) if shape else t
-
-
-def out_flat(n, values=None):
-    return Flat(values, n, kind="out")
 
 
 def dev_scalar(values):
