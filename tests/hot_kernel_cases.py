@@ -12,8 +12,8 @@ A frame MEAN is judged in units of the frame's sigma, |mean - ref| * rstd_ref (S
 the relative error of a mean near 0 says nothing (the fp32 oracle itself is 3.8e-6 "relative" on the `flat` mean2).
 
 The families mid_bwd and mid_n2 (the fused middle's backward, without and with norm2 inside) have their references, mutants and
-route checks here and in the host test, but no GPU test yet: the first version of it handed npvp_frameln_act_bwd_apply an amax slot
-shorter than the 2 KB the kernels index and faulted on the GPU.
+route checks here; the C-ABI calls their GPU tests make are data (tests/mid_bwd_calls.py), and the host test holds every operand of
+every call to the extent the kernels index before a GPU runs one (an amax slot is 2 KB, whatever a block raises in it).
 
 Input kinds: `plain` and `flat` as in grid_kernel_cases, `shift` at 10 sigma (see `field`); `chan`: per-channel offsets of 5 sigma
 (on h1, and on the convolution's bias, so that a thread's first output - the shift of the kernels' one-pass sums - is far from the

@@ -4,14 +4,18 @@ norms and the attention cores through the npvp_amd.ops call sites the models use
 tests/hot_kernel_cases.py; tests/test_hot_kernel_cases_host.py shows that those cases reject a wrong kernel.  One recorded run:
 profiles/hot_kernels_errors.txt (NPVP_ERR_LOG=<file> appends `case output error worst-row-error fp32-cpu-error`).
 
-The fused middle's BACKWARD (families mid_bwd and mid_n2 of the cases file) has no test here yet: see DESIGN.md.
+The fused middle's BACKWARD (families mid_bwd and mid_n2 of the cases file) makes its calls from the plans of tests/mid_bwd_calls.py:
+every operand's size is a record there, held on the CPU to the extents the kernels index before anything runs here.
 
 Through the C ABI every operand is a view into a NaN-padded allocation and every output, buffer updated in place and workspace a
 view into one filled with the bit pattern 0x7FC0BEEF, which must be intact around the view afterwards (helper_kernel_cases.Flat)."""
+import ctypes
+
 import pytest
 import torch
 
 import hot_kernel_cases as HK
+import mid_bwd_calls as MC
 from helper_kernel_cases import DEV, PATTERN, Flat, out_flat
 
 pytestmark = pytest.mark.gpu
@@ -168,9 +172,141 @@ def test_dwconv_window_weight_gradient(L, case):
     HK.close_all("dw_wgrad", case, dict(dwt_db=dwt.cpu(10, Ch)))
 
 
+# ------------------------------------------------------------------------------------------------------------------- middle, backward
+class Plan:
+    """runs the steps of a call plan (tests/mid_bwd_calls.py): every buffer is allocated from its record - this file names no operand
+    size - and after every call everything that is not an input must be intact around its view.  bufs: {buf name: Flat}"""
+
+    def __init__(self, L, tensors):
+        self.L, self.tensors, self.bufs, self.keep, self.host = L, dict(tensors), {}, [], {}
+
+    def value(self, name, count):
+        t = self.bufs[name].v if name in self.bufs else self.tensors[name]
+        assert t.numel() == count, f"{name}: {t.numel()} values for a record of {count}"
+        return t
+
+    def operand(self, r, missing):
+        if r.role == "null":
+            return None
+        if r.role == "host":                    # job records in host memory: a new one, or the one an earlier call wrote
+            if r.fill is None:
+                self.host[r.buf] = ctypes.create_string_buffer(4 * r.count)
+            return ctypes.addressof(self.host[r.fill or r.buf])
+        if r.role == "seed":                    # one 64-bit word, as tests/test_hip_helper_kernels.py::run_drop builds it
+            assert r.count == MC.SEED_FLOATS
+            s = torch.tensor([-1, -1, MC.DROP_SEED, -1, -1], dtype=torch.int64, device=DEV)[2:3]
+            self.keep.append(s)
+            return s.data_ptr()
+        if r.role == "slot":
+            assert r.count == AMAX_SLOT_FLOATS
+            f = slot()
+        elif r.role in ("in", "inout"):
+            known = r.fill in self.bufs or r.fill in self.tensors
+            v = self.value(r.fill, r.count) if known or missing is None else missing(r.count)
+            f = Flat(v) if r.role == "in" else out_flat(r.count, v)
+        else:
+            assert r.role in ("out", "workspace"), r
+            f = out_flat(r.count)
+        if r.buf is not None:
+            self.bufs[r.buf] = f
+        self.keep.append(f)
+        return f.ptr
+
+    def launch(self, c, missing=None):
+        """-> (return code, {role: the Flats of this call with it}).  missing: count -> values for an operand no step has made"""
+        mine, args = {}, []
+        for a in c.args:
+            if isinstance(a, MC.Val):
+                args.append(stream() if a.value == MC.STREAM else a.value)
+                continue
+            before = len(self.keep)
+            args.append(self.operand(a, missing))
+            mine.setdefault(a.role, []).extend(self.keep[before:])
+        return getattr(self.L, c.entry)(*args), mine
+
+    def run(self, steps):
+        for s in steps:
+            if isinstance(s, MC.Derive):
+                self.tensors[s.name] = s.fn(self.bufs[s.source].cpu())
+                continue
+            rc, _ = self.launch(s)
+            ok(self.L, rc, s.entry)
+            for name, f in self.bufs.items():
+                assert f.intact(), f"{s.entry}: written outside the extent of {name}"
+            for name in s.untouched:
+                assert bool((self.bufs[name].base.view(torch.int32) == PATTERN).all()), f"{s.entry} wrote {name}"
+        return self
+
+    def cpu(self, name, *shape):
+        return self.bufs[name].cpu(*shape)
+
+    def frame_sums(self, name, frames):
+        """[frames][partials][2] -> [frames, 2]: a frame's partials added in float64"""
+        return self.cpu(name).double().reshape(frames, -1, 2).sum(1)
+
+
+def norm1_backward(p, Fr, Ch):
+    """what every plan ends with: npvp_frameln_act_bwd_apply on the middle's own da1 and psum - and its amax slot is max |dh1| to the bit"""
+    dh1 = p.cpu("dh1", Fr, 64, Ch)
+    assert float(p.cpu("dh1_amax").max()) == float(dh1.abs().max()), "the amax slot of dh1"
+    return dict(dh1=dh1, dw1n=p.cpu("dw1n", 64, Ch), db1n=p.cpu("db1n", 64, Ch))
+
+
+@pytest.mark.parametrize("case", HK.MID_BWD, ids=HK.case_id)
+def test_mid_bwd(L, case):
+    """mlpdw_mid_bwd_kernel<1, false>: npvp_mlpdw_mid_bwd with accumulate 0, 1 (onto prior_dwt) and 2 (dwt_db left alone), the
+    partials of the last through npvp_mlpdw_mid_bwd_reduce (accumulate 0 and 1), _reduce_into and _reduce_job + npvp_sum_rows_multi
+    (onto prior_gw / prior_gb) - each against float64, none against another -, and norm1's backward on the kernel's own da1 and psum.
+    127 | 128 | 129 frames: a chunk per frame, 128 chunks, 65 chunks of 2 with a last of 1."""
+    Fr, Ch, kind = case
+    p = Plan(L, MC.tensors("mid_bwd", case)).run(MC.plan("mid_bwd", case))
+    got = dict(da1=p.cpu("da1", Fr, 64, Ch), dwt_db=p.cpu("dwt_db", 10, Ch), dwt_db_acc=p.cpu("dwt_db_acc", 10, Ch),
+               psum=p.frame_sums("psum", Fr), gw=p.cpu("gw", Ch, 9), gb=p.cpu("gb"), **norm1_backward(p, Fr, Ch))
+    for tag in ("_b", "_c"):                 # (the same launch but for where dwt_db goes)
+        assert torch.equal(p.bufs["da1" + tag].v, p.bufs["da1"].v) and torch.equal(p.bufs["psum" + tag].v, p.bufs["psum"].v)
+    label, ref, f32 = f"mid_bwd[{HK.case_id(case)}", HK.ref64("mid_bwd", case), HK.ref32("mid_bwd", case)
+    failures = []
+    for route, g in (("]", got), ("|reduce]", dict(dwt_db=p.cpu("dwt_db_r0", 10, Ch), dwt_db_acc=p.cpu("dwt_db_r1", 10, Ch))),
+                     ("|reduce_job]", dict(gw=p.cpu("gw_q", Ch, 9), gb=p.cpu("gb_q")))):
+        try:
+            HK.close_dict(label + route, g, ref, f32)
+        except AssertionError as e:           # (every route is measured and logged before the case fails)
+            failures.append(str(e))
+    assert not failures, "; ".join(failures)
+
+
+@pytest.mark.parametrize("case", HK.MID_N2, ids=HK.case_id)
+def test_mid_n2(L, case):
+    """mlpdw_mid_bwd_kernel<1, true>: npvp_frameln_act_bwd_pgrad (norm2's frame sums as per_frame / 1024 partials, and its parameter
+    gradients), npvp_mlpdw_mid_bwd_n2 on those partials - or, nparts2 = 1, on the frame's sums merged on the host - and norm1's backward
+    behind it.  With dropout the reference takes the keep-scale that the kernels drew, recovered by npvp_drop_apply on ones with the
+    same (p, salt, seed)."""
+    Fr, Ch, drop_p, nparts2 = case
+    p = Plan(L, MC.tensors("mid_n2", case)).run(MC.plan("mid_n2", case))
+    got = dict(psum2=p.frame_sums("psum2", Fr), dw2n=p.cpu("dw2n", 64, Ch), db2n=p.cpu("db2n", 64, Ch), da1=p.cpu("da1", Fr, 64, Ch),
+               dwt_db=p.cpu("dwt_db", 10, Ch), psum=p.frame_sums("psum", Fr), **norm1_backward(p, Fr, Ch))
+    if drop_p == 0.0:
+        return HK.close_all("mid_n2", case, got)
+    keep = p.cpu("keep", Fr, 64, Ch)
+    scale = float(keep.max())
+    assert bool(((keep == 0) | (keep == scale)).all()) and abs(scale * (1.0 - drop_p) - 1.0) < 1e-6 and float(p.cpu("keep_amax").max()) == scale
+    share = float((keep != 0).double().mean())
+    assert abs(share - (1.0 - drop_p)) <= 4 * (drop_p * (1.0 - drop_p) / keep.numel()) ** 0.5, share
+    HK.close_dict(f"mid_n2[{HK.case_id(case)}]", got, HK.mid_n2_reference(case, torch.float64, mask=keep.double()),
+                  HK.mid_n2_reference(case, torch.float32, mask=keep.double()))
+
+
 # ------------------------------------------------------------------------------------------------------------------- refusals
 def test_the_middle_refuses_what_it_cannot_run(L):
-    """a grid that is not 8 x 8, Ch % 512 != 0, a short workspace: non-zero, a message, nothing written"""
+    """a grid that is not 8 x 8, Ch % 512 != 0, a short workspace: non-zero, a message, nothing written; and the backward's argument
+    errors (mid_bwd_calls.refusals: nparts2 0 and 257, dropout without a seed or with p = 1, per_frame % 1024, nparts 0, a null psum,
+    a workspace four bytes short for each producer), every other operand at the size of a call that runs"""
+    for what, c, base, family, case in MC.refusals():
+        p = Plan(L, MC.tensors(family, case))
+        rc, mine = p.launch(c, missing=torch.zeros)
+        assert not mine.get("inout")
+        refused(L, rc, what, mine.get("out", []) + mine.get("workspace", []))
+        assert all(s.intact() and not bool(s.v.any()) for s in mine.get("slot", [])), f"{what}: an amax slot was raised"
     Fr, Ch = 1, 512
     i = HK.mid_inputs("mid_fwd", HK.MID_FWD[0])
     d = mid_operands(i)

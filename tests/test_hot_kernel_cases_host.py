@@ -4,11 +4,14 @@
     bound (or as a non-finite value) in at least one case of the family;
   * the fp32 CPU oracle passes every case and every output at bound / 4: a condition on the INPUTS, so that the bound is not inside
     the reference's own arithmetic noise;
-  * the tables take both sides of every predicate the launchers branch on (the library's pure functions, no device)."""
+  * the tables take both sides of every predicate the launchers branch on (the library's pure functions, no device);
+  * the C-ABI calls of the fused middle's backward tests (tests/mid_bwd_calls.py) hand every pointer parameter exactly the floats
+    the kernels index behind it."""
 import pytest
 import torch
 
 import hot_kernel_cases as HK
+import mid_bwd_calls as MC
 from oracle import ops as O
 
 
@@ -65,6 +68,152 @@ def test_the_inputs_the_kernels_are_given_are_those_of_the_reference():
     assert bool(O.encoder_temporal_mask(Tq)[0, Tk - 1])
     scores = (q[:64, :64] @ k[:64, :64].t()) / 8.0                      # (any unplanted block: sigma WIDE_Q)
     assert 0.85 * HK.WIDE_Q < float(scores.std()) < 1.15 * HK.WIDE_Q
+
+
+# ------------------------------------------------------------------------------------------------------------------- call plans
+# The fused middle's backward tests make their C-ABI calls from plans (tests/mid_bwd_calls.py).  Before a GPU sees one: every pointer
+# record has exactly the extent that the kernels index (the table read off csrc/, workspaces from the library's queries), every amax
+# slot its 2 KB, every pointer parameter of the prototype a record, every operand a definition.  (The first version of these tests
+# wrote an operand's size by hand beside the call: a 16-byte amax slot, where frameln_act_bwd_fused_kernel peeks and raises word
+# (blockIdx.x & 31) * 16 of 512 - an illegal memory access.)
+PLANS = [(f, c) for f in ("mid_bwd", "mid_n2") for c in HK.CASES[f]]
+plan_ids = lambda fc: f"{fc[0]}-{HK.case_id(fc[1])}"
+
+
+def calls_of(family, case):
+    return [s for s in MC.plan(family, case) if isinstance(s, MC.Call)]
+
+
+def prototype_params(entry):
+    """[(C type, name)] of an entry point's parameters: the types from npvp_amd._lib.PROTOTYPES (the parser tests/test_abi.py holds to
+    its grammar), the names read beside them from the same header"""
+    import re
+    from npvp_amd import _lib
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", open(_lib.HEADER_PATH).read(), flags=re.S)
+    m = re.search(r"\b%s\s*\(([^)]*)\)" % entry, text)
+    names = [re.search(r"(\w+)\s*$", p).group(1) for p in m.group(1).split(",")]
+    types = _lib.PROTOTYPES[entry][1]
+    assert len(names) == len(types), entry
+    return list(zip(types, names))
+
+
+def values_of(c):
+    return {a.name: a.value for a in c.args if isinstance(a, MC.Val)}
+
+
+def plan_extent_mismatches(L, steps):
+    bad = []
+    for c in (s for s in steps if isinstance(s, MC.Call)):
+        s = values_of(c)
+        for r in MC.ptrs(c):
+            want = MC.EXTENTS[c.entry][r.name][0](s, L)
+            if want == 0:           # not dereferenced with these arguments: a null, or an output that must come back all pattern
+                if not (r.role == "null" or (r.role == "out" and r.buf in c.untouched)):
+                    bad.append((c.entry, r.name, r.role, r.count, "is not touched"))
+            elif r.role == "null" or r.count != want:
+                bad.append((c.entry, r.name, r.role, r.count, want))
+    return bad
+
+
+@pytest.mark.parametrize("fc", PLANS, ids=plan_ids)
+def test_every_record_of_a_plan_has_the_extent_the_kernels_index(L, fc):
+    """`==`, not `>=`: the views are exact, and the padding around them is the canary"""
+    assert plan_extent_mismatches(L, MC.plan(*fc)) == []
+    assert all(r.role in MC.ROLES and r.count >= 0 for c in calls_of(*fc) for r in MC.ptrs(c))
+
+
+def short_slots(steps):
+    """records of role `slot` that are not 512 floats, and amax parameters that got anything but a slot or a null"""
+    return [(c.entry, r.name, r.role, r.count) for c in steps if isinstance(c, MC.Call) for r in MC.ptrs(c)
+            if (r.role == "slot" and r.count != 512) or ("amax" in r.name and r.role not in ("slot", "null"))]
+
+
+def test_every_amax_slot_has_its_2_kb():
+    import ast
+    import os
+    for fc in PLANS:
+        assert short_slots(MC.plan(*fc)) == [], fc
+        assert any(r.role == "slot" for c in calls_of(*fc) for r in MC.ptrs(c)), fc
+    # the slot() helper of the GPU test, which every slot operand there comes from, read from its source: its constant and its allocation
+    src = ast.parse(open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "test_hip_hot_kernels.py")).read())
+    ns = {}
+    exec(compile(ast.Module(body=[n for n in src.body if isinstance(n, ast.Assign) and ast.unparse(n.targets[0]) == "AMAX_SLOT_FLOATS"],
+                            type_ignores=[]), "test_hip_hot_kernels.py", "exec"), ns)
+    assert ns["AMAX_SLOT_FLOATS"] == 512 == MC.AMAX_SLOT_FLOATS
+    fn = next(n for n in src.body if isinstance(n, ast.FunctionDef) and n.name == "slot")
+    assert ast.unparse(fn.body[-1]) == "return out_flat(AMAX_SLOT_FLOATS, torch.zeros(AMAX_SLOT_FLOATS))"
+
+
+def plan_prototype_mismatches(steps):
+    bad = []
+    for c in (s for s in steps if isinstance(s, MC.Call)):
+        params = prototype_params(c.entry)
+        if len(params) != len(c.args):
+            bad.append((c.entry, len(c.args), len(params)))
+            continue
+        for (ctype, name), a in zip(params, c.args):
+            pointer = ctype.endswith("*")
+            if a.name != name or pointer != isinstance(a, MC.Ptr) or (ctype == "npvp_stream_t") != (isinstance(a, MC.Val) and a.value == MC.STREAM):
+                bad.append((c.entry, name, ctype, a))
+        if set(c.untouched) - {r.buf for r in MC.ptrs(c) if r.role == "out"}:
+            bad.append((c.entry, "untouched", c.untouched))
+    return bad
+
+
+@pytest.mark.parametrize("fc", PLANS, ids=plan_ids)
+def test_every_pointer_parameter_of_a_prototype_has_a_record_in_order(fc):
+    assert plan_prototype_mismatches(MC.plan(*fc)) == []
+
+
+def plan_undefined_operands(family, case, steps):
+    """a `fill` names a tensor of the case's inputs or what an earlier step left, with the record's count; no buffer name is given twice"""
+    known = {k: t.numel() for k, t in MC.tensors(family, case).items()}
+    bad = []
+    for s in steps:
+        if isinstance(s, MC.Derive):
+            if known.get(s.source) is None or s.name in known:
+                bad.append(("derive", s.name, s.source))
+            known[s.name] = s.count
+            continue
+        for r in MC.ptrs(s):
+            if r.role in ("in", "inout") or (r.role == "host" and r.fill):
+                if known.get(r.fill) != r.count:
+                    bad.append((s.entry, r.name, r.fill, known.get(r.fill), r.count))
+            elif r.fill is not None:
+                bad.append((s.entry, r.name, "a fill on a", r.role))
+        for r in MC.ptrs(s):
+            if r.buf is not None:
+                if r.buf in known or r.role == "in":
+                    bad.append((s.entry, r.name, "names again", r.buf))
+                known[r.buf] = r.count
+    return bad
+
+
+@pytest.mark.parametrize("fc", PLANS, ids=plan_ids)
+def test_every_operand_of_a_plan_is_defined(fc):
+    assert plan_undefined_operands(*fc, MC.plan(*fc)) == []
+
+
+def test_the_plan_checks_see_a_short_record(L):
+    """each of the four checks above fails on a plan with one slot cut to 4 floats, and on one with a psum a partial short"""
+    for fc in PLANS:
+        steps = MC.plan(*fc)
+        assert steps[-1].entry == "npvp_frameln_act_bwd_apply"
+        record = lambda name: next(r for r in MC.ptrs(steps[-1]) if r.name == name)
+        cut = lambda name, count: steps[:-1] + [MC.replaced(steps[-1], **{name: record(name)._replace(count=count)})]
+        slot4, psum_short = cut("dh_amax", 4), cut("psum", record("psum").count - 2)
+        assert plan_extent_mismatches(L, slot4) and short_slots(slot4) and plan_extent_mismatches(L, psum_short)
+        assert plan_undefined_operands(*fc, psum_short)              # (the producer left more than the record takes)
+        assert plan_prototype_mismatches(steps[:-1] + [steps[-1]._replace(args=tuple(a for a in steps[-1].args if a.name != "dh_amax"))])
+
+
+def test_the_refusals_are_complete_calls_at_full_size(L):
+    """the calls the GPU test expects to be refused: complete, and - but for the argument under test - with the extents of a call that
+    runs, so that one which is not refused stays inside its buffers"""
+    for what, c, base, family, case in MC.refusals():
+        assert plan_prototype_mismatches([c]) == [] and plan_extent_mismatches(L, [base]) == [], what
+        assert all(r == b or r.role == "null" for r, b in zip(MC.ptrs(c), MC.ptrs(base))), what
+        assert sum(a != b for a, b in zip(c.args, base.args)) == 1, what
 
 
 def both(values):
