@@ -578,6 +578,14 @@ int npvp_u8hwc_to_f32chw(const void* src_u8, float* dst, long long frames, int H
 int npvp_bias_act(const float* x, const float* bias, const float* residual, float* out, long long outer, long long inner, int C,
                   int layout, int act, npvp_stream_t stream);
 int npvp_act_bwd(const float* g, const float* y, float* dx, long long n, int act, npvp_stream_t stream);
+/* The tail of NonLocalAttenion2D.forward (ref/models/submodules.py:150-176: bias of out_proj, folded BatchNorm, activation, gamma *,
+ * + x) as ONE pass over out_proj's product, 12 B per element with a residual:
+ *   out = fmaf(s, act(x + bias[c]), residual)      residual NULL: out = s * act(x + bias[c])
+ * s = *scale, ONE float in DEVICE memory read by the kernel (no host synchronisation: the call can be captured in a graph);
+ * scale NULL: s = 1, and the result is npvp_bias_act's bit for bit.  Layouts, acts and the vector rule are npvp_bias_act's; every
+ * output element is written exactly once (no atomics, no workspace). */
+int npvp_bias_act_scaled(const float* x, const float* bias, const float* scale, const float* residual, float* out, long long outer,
+                         long long inner, int C, int layout, int act, npvp_stream_t stream);
 
 /* ---- Stage-1 autoencoder training (csrc/ae_train.hip): LitAE.training_step / shared_step (ref/models/ResNetAutoEncoder.py:13-49)
  * through ResnetEncoder / ResnetDecoder (ref :51-204) and NonLocalAttenion2D (ref/models/submodules.py:98-176); the convolutions

@@ -11,8 +11,11 @@ checkpoints load.  `learn_3d=True` adds the temporal half of every Factorized3DC
            conv -> BatchNorm -> ReLU (-> + skip) group becomes a `FoldedConvAct`: the convolution with the BatchNorm folded
            into its weights (MIOpen) + ONE hand-written epilogue pass `npvp_bias_act` (csrc/ae.hip) instead of separate
            bias / BatchNorm / ReLU / skip-add passes; the decoder's input gradient goes through `npvp_act_bwd`.
+           `attn2d="hip"` (opt-in, inference only) also sends the encoder's NonLocalAttenion2D through the non-local attention
+           kernels and one `npvp_bias_act_scaled` pass (`_fused_attn2d`); the default `"stock"` leaves it on stock PyTorch.
 """
 import functools
+import types
 
 import torch
 import torch.nn as nn
@@ -81,9 +84,41 @@ def _fold_sequential(seq):
     return nn.Sequential(*out)
 
 
-def fuse_frozen_autoencoder(enc, dec):
+ATTN2D_ROUTES = ("stock", "hip")
+
+
+def _check_attn2d(attn2d):
+    if attn2d not in ATTN2D_ROUTES:
+        raise ValueError(f"attn2d={attn2d!r}: the route of the frozen encoder's NonLocalAttenion2D is one of {ATTN2D_ROUTES}")
+
+
+def _zero_or_bias(lin):
+    return lin.bias if lin.bias is not None else torch.zeros(lin.out_features, dtype=lin.weight.dtype, device=lin.weight.device)
+
+
+def _register_wqkv(a):
+    """[Wq | Wk | Wv] of an attention as one projection (non-persistent buffers: the state-dict keys stay the reference's)"""
+    a.register_buffer("_npvp_wqkv", torch.cat([a.Wq.weight, a.Wk.weight, a.Wv.weight], 0).detach().clone(), persistent=False)
+    a.register_buffer("_npvp_bqkv", torch.cat([_zero_or_bias(a.Wq), _zero_or_bias(a.Wk), _zero_or_bias(a.Wv)], 0).detach().clone(),
+                      persistent=False)
+
+
+def _attn2d_takes_hip(a):
+    """a NonLocalAttenion2D of a fused pair (BatchNorm already folded into out_proj) that the HIP route can run: an (A, V) the
+    non-local kernels are instantiated for, an activation the epilogue has, gamma a Parameter or the float 1.0"""
+    gamma_ok = isinstance(a.gamma, torch.Tensor) or a.gamma == 1.0
+    act_ok = isinstance(a.activ_func, nn.Identity) or type(a.activ_func) in _ACT_CODE
+    return (ops.nonlocal_attn_dims(a.attn_dim, a.value_dim) and isinstance(a.norm_func, nn.Identity) and act_ok and gamma_ok
+            and a.out_proj.bias is not None)
+
+
+def fuse_frozen_autoencoder(enc, dec, attn2d="stock"):
     """In-place module surgery on an eval-mode pair that already holds its final weights; freezes its parameters (do it after load_state_dict:
-    the folded modules no longer carry the reference's state-dict keys).  Returns (enc, dec)."""
+    the folded modules no longer carry the reference's state-dict keys).  Returns (enc, dec).
+    attn2d: "stock" (default) leaves every NonLocalAttenion2D of the encoder on its own forward (PyTorch: the (frames, H*W, H*W/4) scores
+    in memory); "hip" sends those whose (attn_dim, value_dim) has non-local kernels (ops.nonlocal_attn_dims) through `_fused_attn2d`
+    (inference only: no scores in memory, one epilogue pass).  Any other value is refused."""
+    _check_attn2d(attn2d)
     for m in (enc, dec):
         assert not m.training, "fuse_frozen_autoencoder: eval mode only (BatchNorm must use its running statistics)"
         for q in m.parameters():
@@ -100,6 +135,9 @@ def fuse_frozen_autoencoder(enc, dec):
                     a.out_proj.weight.mul_(s.view(-1, 1))
                     a.out_proj.bias.copy_(a.out_proj.bias * s + t)
                     a.norm_func = nn.Identity()
+                if attn2d == "hip" and _attn2d_takes_hip(a):
+                    _register_wqkv(a)
+                    a.forward = types.MethodType(_fused_attn2d, a)
                 if mod.learn_3d:
                     mod.temporal_conv = FoldedTemporalConvAct(mod.temporal_conv[0], mod.temporal_conv[1] if isinstance(
                         mod.temporal_conv[1], nn.BatchNorm1d) else None, mod.temporal_conv[2])
@@ -109,9 +147,7 @@ def fuse_frozen_autoencoder(enc, dec):
                         a.out_proj.weight.mul_(s.view(-1, 1))
                         a.out_proj.bias.copy_(a.out_proj.bias * s + t)
                         a.norm_func = nn.Identity()
-                    zero = lambda lin: lin.bias if lin.bias is not None else torch.zeros(lin.out_features, device=lin.weight.device)
-                    a.register_buffer("_npvp_wqkv", torch.cat([a.Wq.weight, a.Wk.weight, a.Wv.weight], 0).detach().clone(), persistent=False)
-                    a.register_buffer("_npvp_bqkv", torch.cat([zero(a.Wq), zero(a.Wk), zero(a.Wv)], 0).detach().clone(), persistent=False)
+                    _register_wqkv(a)
             elif isinstance(mod, ResnetBlock):
                 mod.conv_block = _fold_sequential(mod.conv_block)
         dec.model = _fold_sequential(dec.model)
@@ -290,6 +326,27 @@ def _fused_attn1d(a, x, T):
     return x + a.gamma * a.activ_func(a.norm_func(out))
 
 
+def _fused_attn2d(a, x):
+    """NonLocalAttenion2D.forward of a fused (frozen, eval) pair under attn2d="hip", on channels-last frames x (F, C, H, W): one GEMM
+    for [Wq | Wk | Wv], the non-local attention kernels (online softmax, K / V pooled 2x2 in the tile loads: no (F, HW, HW/4) tensor), one
+    GEMM for out_proj and ONE pass  x + gamma * act(y + out_proj.bias[c])  (npvp_bias_act_scaled; gamma is read on the device).
+    A grid without a 2x2 window or an input that is not channels-last keeps the stock forward (no silent copy)."""
+    Fr, C, H, W = x.shape
+    A, V = a.attn_dim, a.value_dim
+    if H < 2 or W < 2 or x.is_contiguous() or not x.is_contiguous(memory_format=torch.channels_last):
+        return NonLocalAttenion2D.forward(a, x)
+    if torch.is_grad_enabled() and x.requires_grad:
+        raise NotImplementedError('attn2d="hip" (to_device_layout / fuse_frozen_autoencoder) is inference-only: the input of this '
+                                  'NonLocalAttenion2D requires grad; fuse the pair with attn2d="stock" to differentiate through it')
+    tok = x.permute(0, 2, 3, 1).reshape(Fr * H * W, C)                  # a view of channels-last frames
+    qkv = F.linear(tok, a._npvp_wqkv, a._npvp_bqkv)
+    nl = ops.nonlocal_attn_packed if ops.nonlocal_attn_config_shape(A, V, H, W) else ops.nonlocal_attn_grid_packed
+    o = nl(qkv, Fr, H, W, A, V)
+    y = F.linear(o, a.out_proj.weight).view(Fr, H, W, C).permute(0, 3, 1, 2)
+    act = 0 if isinstance(a.activ_func, nn.Identity) else _ACT_CODE[type(a.activ_func)]
+    return ops.bias_act_scaled(y, a.out_proj.bias, a.gamma if isinstance(a.gamma, torch.Tensor) else None, act, residual=x)
+
+
 class ResnetBlock(nn.Module):
     """ref/models/ResNetAutoEncoder.py:206-261: x + [pad, conv3, norm, ReLU, (dropout), pad, conv3, norm](x)."""
 
@@ -402,9 +459,10 @@ def build_frozen_autoencoder(AE, img_channels):
     return enc, dec
 
 
-def to_device_layout(enc, dec, device):
+def to_device_layout(enc, dec, device, attn2d="stock"):
     """Move the frozen pair to an MI355X.  The ENCODER runs in torch.channels_last (MIOpen's NHWC kernels: 27.5 -> 24.8 ms
     for 640 frames of 64x64, and its (N*T,H,W,C) output is the predictor's canonical layout, so the layout transpose at
     the predictor's entry disappears); the decoder stays NCHW (NHWC measured slower: 9.0 -> 11.2 ms fwd + input-grad)."""
+    _check_attn2d(attn2d)
     enc, dec = enc.to(device).to(memory_format=torch.channels_last), dec.to(device)
-    return fuse_frozen_autoencoder(enc.eval(), dec.eval())
+    return fuse_frozen_autoencoder(enc.eval(), dec.eval(), attn2d=attn2d)

@@ -2381,6 +2381,34 @@ def bias_act(x, bias, act=0, residual=None):
     return _BiasAct.apply(x, bias, residual, act)
 
 
+def bias_act_scaled(x, bias, scale, act=0, residual=None):
+    """out = residual + s * act(x + bias[c]) on an (N,C,H,W) tensor in contiguous or channels_last memory, one pass
+    (npvp_bias_act_scaled): the tail of the frozen NonLocalAttenion2D.  scale: a one-element DEVICE tensor the kernel reads (no
+    .item(), no host synchronisation), or None for s = 1.  Forward only: an input that requires grad is refused."""
+    ts = [t for t in (x, bias, scale, residual) if t is not None]
+    if torch.is_grad_enabled() and any(t.requires_grad for t in ts):
+        raise NotImplementedError("bias_act_scaled: forward only (the frozen autoencoder's attention tail); an input requires grad")
+    _chk(*ts)
+    if x.dim() != 4 or bias.shape != (x.shape[1],):
+        raise RuntimeError("bias_act_scaled: x must be (N, C, H, W) and bias (C,)")
+    if scale is not None and scale.numel() != 1:
+        raise RuntimeError("bias_act_scaled: scale must hold one float")
+    if residual is not None and residual.shape != x.shape:
+        raise RuntimeError("bias_act_scaled: residual shape differs from x")
+    N, C, H, W = x.shape
+    cl = (not x.is_contiguous()) and x.is_contiguous(memory_format=torch.channels_last)
+    if not cl and not x.is_contiguous():
+        x = x.contiguous()
+    if residual is not None and residual.stride() != x.stride():
+        residual = residual.contiguous(memory_format=torch.channels_last if cl else torch.contiguous_format)
+    out = torch.empty_like(x)
+    outer, inner, layout = (N * H * W, C, 0) if cl else (N * C, H * W, 1)
+    bias = _c(bias)
+    check(lib().npvp_bias_act_scaled(_ptr(x), _ptr(bias), _ptr(scale), _ptr(residual), _ptr(out), outer, inner, C, layout, act,
+                                     _stream()), "npvp_bias_act_scaled")
+    return out
+
+
 # --------------------------------------------------------------------------- Stage-1 autoencoder training (csrc/ae_train.hip)
 def _nchw_layout(x, what):
     """(x, outer, inner, layout) of an (N,C,H,W) tensor as the layout kernels read it: channels_last memory is layout 0 (rows
