@@ -17,6 +17,7 @@
 // _bwd, any T >= 1: the same launches up to 32 frames, above that the key-tiled kernels in the second half of this file (one forward
 // launch; a dq launch that also fills the caller's scratch D [2][rows], then a dk / dv launch), whose LDS does not depend on T.
 #include "common.h"
+#include "ae_attn_dims.h"
 
 #include <stdio.h>
 
@@ -528,8 +529,7 @@ static int ta_check_shape(const char* name, int N, int T, int HW, int A, int V, 
   if (tiled) TA_REQUIRE(T >= 1, "%s: T = %d, a clip has T >= 1 frames", name, T);
   else TA_REQUIRE(T >= 1 && T <= TA_MAX_T, "%s: T = %d, 1 <= T <= %d frames per clip (longer clips need key tiling)", name, T, TA_MAX_T);
   TA_REQUIRE(N >= 1 && HW >= 1, "%s: N = %d, HW = %d must be >= 1", name, N, HW);
-  TA_REQUIRE((A == 8 && V == 32) || (A == 16 && V == 64) || (A == 32 && V == 128) || (A == 64 && V == 256),
-             "%s: (attn dim, value dim) = (%d, %d) must be (8,32), (16,64), (32,128) or (64,256)", name, A, V);
+  TA_REQUIRE(npvp_ae_attn_dims(A, V), "%s: (attn dim, value dim) = (%d, %d) must be (8,32), (16,64), (32,128) or (64,256)", name, A, V);
   TA_REQUIRE((long long)N * T * HW < (1ll << 31), "%s: too many rows, N*T*HW = %lld (< 2^31)", name, (long long)N * T * HW);
   return NPVP_OK;
 }
@@ -541,8 +541,9 @@ static int ta_check_operand(const char* name, const char* what, const void* p, l
   return NPVP_OK;
 }
 
-#define TA_DISPATCH(MACRO) \
-  if (A == 8) MACRO(8, 32) else if (A == 16) MACRO(16, 64) else if (A == 32) MACRO(32, 128) else MACRO(64, 256)
+// MACRO(A, V) for the pair of ae_attn_dims.h that ta_check_shape has let through
+#define TA_CASE(a, vv, MACRO) if (A == a) MACRO(a, vv) else
+#define TA_DISPATCH(MACRO) NPVP_AE_ATTN_DIMS(TA_CASE, MACRO) {}
 
 static TAGeo ta_geo(int T, int HW, int PT) {
   TAGeo g;
@@ -582,12 +583,18 @@ static int ta_launch_bwd(const float* q, long long ldq, const float* k, long lon
   return NPVP_OK;
 }
 
-static int ta_check_fwd(const char* name, const float* q, long long ldq, const float* k, long long ldk, const float* v, long long ldv,
-                        const float* o, long long ldo, const float* lse, int N, int T, int HW, int A, int V, bool tiled) {
+// what the forward and the backward check first, in this order: the shape, then the operands q, k, v
+static int ta_check_qkv(const char* name, const float* q, long long ldq, const float* k, long long ldk, const float* v, long long ldv,
+                        int N, int T, int HW, int A, int V, bool tiled) {
   if (int rc = ta_check_shape(name, N, T, HW, A, V, tiled)) return rc;
   if (int rc = ta_check_operand(name, "q", q, ldq, A)) return rc;
   if (int rc = ta_check_operand(name, "k", k, ldk, A)) return rc;
-  if (int rc = ta_check_operand(name, "v", v, ldv, V)) return rc;
+  return ta_check_operand(name, "v", v, ldv, V);
+}
+
+static int ta_check_fwd(const char* name, const float* q, long long ldq, const float* k, long long ldk, const float* v, long long ldv,
+                        const float* o, long long ldo, const float* lse, int N, int T, int HW, int A, int V, bool tiled) {
+  if (int rc = ta_check_qkv(name, q, ldq, k, ldk, v, ldv, N, T, HW, A, V, tiled)) return rc;
   if (int rc = ta_check_operand(name, "o", o, ldo, V)) return rc;
   TA_REQUIRE(lse != nullptr, "%s: null buffer lse", name);
   return NPVP_OK;
@@ -596,10 +603,7 @@ static int ta_check_fwd(const char* name, const float* q, long long ldq, const f
 static int ta_check_bwd(const char* name, const float* q, long long ldq, const float* k, long long ldk, const float* v, long long ldv,
                         const float* go, long long ldgo, const float* lse, const float* dq, long long lddq, const float* dk,
                         long long lddk, const float* dv, long long lddv, int N, int T, int HW, int A, int V, bool tiled) {
-  if (int rc = ta_check_shape(name, N, T, HW, A, V, tiled)) return rc;
-  if (int rc = ta_check_operand(name, "q", q, ldq, A)) return rc;
-  if (int rc = ta_check_operand(name, "k", k, ldk, A)) return rc;
-  if (int rc = ta_check_operand(name, "v", v, ldv, V)) return rc;
+  if (int rc = ta_check_qkv(name, q, ldq, k, ldk, v, ldv, N, T, HW, A, V, tiled)) return rc;
   if (int rc = ta_check_operand(name, "go", go, ldgo, V)) return rc;
   if (int rc = ta_check_operand(name, "dq", dq, lddq, A)) return rc;
   if (int rc = ta_check_operand(name, "dk", dk, lddk, A)) return rc;

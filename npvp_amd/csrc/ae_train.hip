@@ -17,6 +17,7 @@
 // The attention runs on the f32 VALU (v_fma_f32): exact fp32 products at the same peak rate as the f32 MFMA (cdna_hip_programming §3),
 // and the head dimensions here (8..64) are too narrow to fill an MFMA tile without padding.
 #include "common.h"
+#include "ae_attn_dims.h"
 
 #include <stdlib.h>
 
@@ -896,7 +897,7 @@ static bool nl_force_general() {
 static int nl_check(bool grid, int F, int H, int W, int A, int V) {
   NL_REQUIRE(F > 0 && H >= 2 && W >= 2, "", grid ? "F >= 1, H >= 2, W >= 2" : "H even, W a power of two");
   NL_REQUIRE(grid || (H % 2 == 0 && (W & (W - 1)) == 0), "", "H even, W a power of two");
-  NL_REQUIRE((A == 8 && V == 32) || (A == 16 && V == 64) || (A == 32 && V == 128) || (A == 64 && V == 256), "",
+  NL_REQUIRE(npvp_ae_attn_dims(A, V), "",
              "(attn dim, value dim) must be (8,32), (16,64), (32,128) or (64,256): C = 64..512 of the AE configs");
   NL_REQUIRE(grid || nl_config_shape(H, W, A), "",
              "grid not supported (the AE configs' grids: 64x64 @ C=64, 32x32 @ 128, 16x16 @ 256, 8x8 @ 512)");
@@ -904,11 +905,13 @@ static int nl_check(bool grid, int F, int H, int W, int A, int V) {
   return NPVP_OK;
 }
 
+// MACRO(A, V, exact) for the pair of ae_attn_dims.h that nl_check has let through
+#define NL_CASE(a, vv, MACRO, ex) if (A == a) MACRO(a, vv, ex) else
 #define NL_DISPATCH(MACRO)                                                                                                         \
   if (exact) {                                                                                                                     \
-    if (A == 8) MACRO(8, 32, true) else if (A == 16) MACRO(16, 64, true) else if (A == 32) MACRO(32, 128, true) else MACRO(64, 256, true)  \
+    NPVP_AE_ATTN_DIMS(NL_CASE, MACRO, true) {}                                                                                     \
   } else {                                                                                                                         \
-    if (A == 8) MACRO(8, 32, false) else if (A == 16) MACRO(16, 64, false) else if (A == 32) MACRO(32, 128, false) else MACRO(64, 256, false) \
+    NPVP_AE_ATTN_DIMS(NL_CASE, MACRO, false) {}                                                                                    \
   }
 
 // grid: the any-grid entry point (its name in the error texts, its shapes); the other one refuses what is no config shape

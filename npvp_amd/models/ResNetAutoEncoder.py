@@ -328,7 +328,7 @@ def _fused_attn1d(a, x, T):
 
 def _fused_attn2d(a, x):
     """NonLocalAttenion2D.forward of a fused (frozen, eval) pair under attn2d="hip", on channels-last frames x (F, C, H, W): one GEMM
-    for [Wq | Wk | Wv], the non-local attention kernels (online softmax, K / V pooled 2x2 in the tile loads: no (F, HW, HW/4) tensor), one
+    for [Wq | Wk | Wv], the non-local attention kernels (ops.nonlocal_attn_any_packed: online softmax, K / V pooled 2x2 in the tile loads: no (F, HW, HW/4) tensor), one
     GEMM for out_proj and ONE pass  x + gamma * act(y + out_proj.bias[c])  (npvp_bias_act_scaled; gamma is read on the device).
     A grid without a 2x2 window or an input that is not channels-last keeps the stock forward (no silent copy)."""
     Fr, C, H, W = x.shape
@@ -340,8 +340,7 @@ def _fused_attn2d(a, x):
                                   'NonLocalAttenion2D requires grad; fuse the pair with attn2d="stock" to differentiate through it')
     tok = x.permute(0, 2, 3, 1).reshape(Fr * H * W, C)                  # a view of channels-last frames
     qkv = F.linear(tok, a._npvp_wqkv, a._npvp_bqkv)
-    nl = ops.nonlocal_attn_packed if ops.nonlocal_attn_config_shape(A, V, H, W) else ops.nonlocal_attn_grid_packed
-    o = nl(qkv, Fr, H, W, A, V)
+    o = ops.nonlocal_attn_any_packed(qkv, Fr, H, W, A, V)
     y = F.linear(o, a.out_proj.weight).view(Fr, H, W, C).permute(0, 3, 1, 2)
     act = 0 if isinstance(a.activ_func, nn.Identity) else _ACT_CODE[type(a.activ_func)]
     return ops.bias_act_scaled(y, a.out_proj.bias, a.gamma if isinstance(a.gamma, torch.Tensor) else None, act, residual=x)

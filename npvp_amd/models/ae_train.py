@@ -2,12 +2,12 @@
 the same state-dict keys, run through the HIP ops of csrc/ae_train.hip instead of stock torch:
   [pad] conv [BatchNorm2d [ReLU]] [+ skip]  ->  ops.reflect_pad, the convolution (MIOpen), ops.bn_act_train (statistics + one apply
                                                pass, skip-add fused)
-  NonLocalAttenion2D                        ->  one GEMM for [Wq | Wk | Wv] (ops.linear), ops.nonlocal_attn_packed at the configs' own grids,
-                                               ops.nonlocal_attn_grid_packed at any other (pooling fused, no score matrix in
-                                               HBM), out_proj (ops.linear), ops.bn_act_train + ReLU, x + gamma * h
+  NonLocalAttenion2D                        ->  one GEMM for [Wq | Wk | Wv] (ops.linear), ops.nonlocal_attn_any_packed (the exact-tile kernels at
+                                               the configs' own grids, the any-grid ones at any other; pooling fused, no score
+                                               matrix in HBM), out_proj (ops.linear), ops.bn_act_train + ReLU, x + gamma * h
   learn_3d: temporal_conv                   ->  the Conv1d over T as a conv2d with a [C, C, 3, 1] filter on the channels-last frames viewed as
                                                (N, C, T, H*W) (MIOpen, no permute copy), BatchNorm1d through the same ops.bn_act_train
-            NonLocalAttenion1D              ->  one GEMM for [Wq | Wk | Wv], ops.temporal_attn_packed on the same token rows (csrc/ae_temporal.hip),
+            NonLocalAttenion1D              ->  one GEMM for [Wq | Wk | Wv], ops.temporal_attn_any_packed on the same token rows (csrc/ae_temporal.hip),
                                                out_proj, ops.bn_act_train + ReLU, x + gamma * h
 `prepare_trainable_autoencoder` binds these forwards to the two module INSTANCES; the classes, their forward methods and the frozen
 Stage-2 path (build_frozen_autoencoder / fuse_frozen_autoencoder) are untouched.
@@ -123,16 +123,10 @@ def _attn_core(a, x, core):
 
 
 def _attn(a, x):
-    """NonLocalAttenion2D.forward (ref/models/submodules.py:150-176) on the HIP path"""
+    """NonLocalAttenion2D.forward (ref/models/submodules.py:150-176) on the HIP path; ops.nonlocal_attn_any_packed chooses between the
+    configs' exact-tile kernels and the any-grid ones"""
     N, C, H, W = x.shape
-
-    def core(qkv, A, V):
-        # the configs' own (C, grid) pairs keep their exact-tile kernels; any other grid takes the general ones (an (A, V) that no
-        # kernel has is refused by either op: it stays with the first, as before)
-        other_grid = ops.nonlocal_attn_dims(A, V) and not ops.nonlocal_attn_config_shape(A, V, H, W)
-        nl = ops.nonlocal_attn_grid_packed if other_grid else ops.nonlocal_attn_packed
-        return nl(qkv, N, H, W, A, V)
-    return _attn_core(a, x, core)
+    return _attn_core(a, x, lambda qkv, A, V: ops.nonlocal_attn_any_packed(qkv, N, H, W, A, V))
 
 
 def _attn1d(a, x, T):

@@ -2342,6 +2342,21 @@ def mean_mid(x):
 
 
 # --------------------------------------------------------------------------- frozen autoencoder epilogues (csrc/ae.hip)
+def _nchw_layout(x, what):
+    """(x, outer, inner, layout) of an (N,C,H,W) tensor as the layout kernels read it: channels_last memory is layout 0 (rows
+    [N*H*W][C]), contiguous memory layout 1 (planes [N*C][H*W]); anything else is made contiguous first"""
+    if x.dim() != 4:
+        raise RuntimeError(f"{what}: x must be (N, C, H, W)")
+    N, C, H, W = x.shape
+    if x.is_contiguous(memory_format=torch.channels_last) and not x.is_contiguous():
+        return x, N * H * W, C, 0
+    return x.contiguous(), N * C, H * W, 1
+
+
+def _memory_format(layout):
+    return torch.channels_last if layout == 0 else torch.contiguous_format
+
+
 class _BiasAct(_Function):
     """out = act(x + bias[c]) (+ residual) on an (N,C,H,W) tensor in contiguous or channels_last memory; bias is frozen.
     Gradient w.r.t. x only (the decoder's input-gradient path), through the saved OUTPUT."""
@@ -2351,17 +2366,13 @@ class _BiasAct(_Function):
         remember(ctx)
         _chk(x, bias, residual)
         need_x, need_res = ctx.needs_input_grad[0], ctx.needs_input_grad[2]     # (read before x may be rebound to a no-grad copy)
-        N, C, H, W = x.shape
-        cl = (not x.is_contiguous()) and x.is_contiguous(memory_format=torch.channels_last)
-        if not cl and not x.is_contiguous():
-            x = x.contiguous()
+        x, outer, inner, layout = _nchw_layout(x, "bias_act")
         if residual is not None and residual.stride() != x.stride():
-            residual = residual.contiguous(memory_format=torch.channels_last if cl else torch.contiguous_format)
+            residual = residual.contiguous(memory_format=_memory_format(layout))
         out = torch.empty_like(x)
-        outer, inner, layout = (N * H * W, C, 0) if cl else (N * C, H * W, 1)
-        check(lib().npvp_bias_act(_ptr(x), _ptr(bias), _ptr(residual), _ptr(out), outer, inner, C, layout, act, _stream()),
+        check(lib().npvp_bias_act(_ptr(x), _ptr(bias), _ptr(residual), _ptr(out), outer, inner, x.shape[1], layout, act, _stream()),
               "npvp_bias_act")
-        ctx.act, ctx.cl, ctx.has_res = act, cl, residual is not None
+        ctx.act, ctx.cl, ctx.has_res = act, layout == 0, residual is not None
         if need_x or need_res:
             if residual is not None:
                 raise NotImplementedError("bias_act: backward with a fused skip-add is not on the Stage-2 path")
@@ -2395,36 +2406,17 @@ def bias_act_scaled(x, bias, scale, act=0, residual=None):
         raise RuntimeError("bias_act_scaled: scale must hold one float")
     if residual is not None and residual.shape != x.shape:
         raise RuntimeError("bias_act_scaled: residual shape differs from x")
-    N, C, H, W = x.shape
-    cl = (not x.is_contiguous()) and x.is_contiguous(memory_format=torch.channels_last)
-    if not cl and not x.is_contiguous():
-        x = x.contiguous()
+    x, outer, inner, layout = _nchw_layout(x, "bias_act_scaled")
     if residual is not None and residual.stride() != x.stride():
-        residual = residual.contiguous(memory_format=torch.channels_last if cl else torch.contiguous_format)
+        residual = residual.contiguous(memory_format=_memory_format(layout))
     out = torch.empty_like(x)
-    outer, inner, layout = (N * H * W, C, 0) if cl else (N * C, H * W, 1)
     bias = _c(bias)
-    check(lib().npvp_bias_act_scaled(_ptr(x), _ptr(bias), _ptr(scale), _ptr(residual), _ptr(out), outer, inner, C, layout, act,
+    check(lib().npvp_bias_act_scaled(_ptr(x), _ptr(bias), _ptr(scale), _ptr(residual), _ptr(out), outer, inner, x.shape[1], layout, act,
                                      _stream()), "npvp_bias_act_scaled")
     return out
 
 
 # --------------------------------------------------------------------------- Stage-1 autoencoder training (csrc/ae_train.hip)
-def _nchw_layout(x, what):
-    """(x, outer, inner, layout) of an (N,C,H,W) tensor as the layout kernels read it: channels_last memory is layout 0 (rows
-    [N*H*W][C]), contiguous memory layout 1 (planes [N*C][H*W]); anything else is made contiguous first"""
-    if x.dim() != 4:
-        raise RuntimeError(f"{what}: x must be (N, C, H, W)")
-    N, C, H, W = x.shape
-    if x.is_contiguous(memory_format=torch.channels_last) and not x.is_contiguous():
-        return x, N * H * W, C, 0
-    return x.contiguous(), N * C, H * W, 1
-
-
-def _memory_format(layout):
-    return torch.channels_last if layout == 0 else torch.contiguous_format
-
-
 class _BnActTrain(_Function):
     """BatchNorm2d (batch statistics in training, running statistics in eval) -> act (0 none, 1 ReLU) [-> + residual] as one
     statistics pass and one apply pass forward, one sum pass and one dx pass backward (npvp_bn_*).
@@ -2514,45 +2506,62 @@ def bn_act_train(x, w, b, running_mean=None, running_var=None, momentum=0.1, eps
     return _BnActTrain.apply(x, w, b, residual, running_mean, running_var, momentum, eps, act, bool(train), group if train else None)
 
 
-_NL_GRID = {8: 64, 16: 32, 32: 16, 64: 8}        # attention dim A -> side of the AE configs' square grid at C = 8 A; value dim = 4 A
+_NL_GRID = {8: 64, 16: 32, 32: 16, 64: 8}        # attention dim A -> side of the AE configs' square grid at C = 8 A; value dim = 4 A (csrc/ae_attn_dims.h)
 
 
-class _NonLocalAttn(_Function):
-    """softmax(q k^T) v of NonLocalAttenion2D (unscaled scores, 2x2 max-pooled keys / values) from ONE projection tensor
-    qkv [F*H*W, ld] = [q | k | v | zero padding]; the gradient comes back in the same layout.  export: "npvp_nonlocal_attn" (the AE
-    configs' grids) or "npvp_nonlocal_attn_grid" (any H x W: floor pooling, the never-pooled last line / column of an odd grid gets
-    dk = dv = 0 from the backward's own kernels); <export>_fwd and <export>_bwd take the same arguments."""
+class _PackedAttn(_Function):
+    """softmax(q k^T) v (unscaled scores) from ONE projection tensor qkv [rows, ld] = [q | k | v | zero padding], rows = n0*n1*n2; the
+    gradient comes back in the same layout, its pad columns zero.  <export>_fwd / <export>_bwd are the C entry points, (n0, n1, n2)
+    their three leading ints:
+      "npvp_nonlocal_attn" (F, H, W)       NonLocalAttenion2D at the AE configs' grids: keys / values 2x2 max-pooled in the kernels
+      "npvp_nonlocal_attn_grid" (F, H, W)  the same on any H x W: floor pooling, the never-pooled last line / column of an odd grid
+                                           gets dk = dv = 0 from the backward's own kernels
+      "npvp_temporal_attn" (N, T, HW)      NonLocalAttenion1D (ref/models/submodules.py:229-237) over the T <= TEMPORAL_ATTN_MAX_T frames
+                                           of every pixel of channels-last token rows (row = (n T + t) HW + p); one backward launch
+      "npvp_temporal_attn_long" (N, T, HW) the same for any T: the keys are tiled above TEMPORAL_ATTN_MAX_T frames, at or below it the
+                                           launches and the bits are npvp_temporal_attn's
+    scratch: the backward hands <export>_bwd a scratch D [2][rows] after lse (every export but "npvp_temporal_attn")."""
 
     @staticmethod
-    def forward(ctx, qkv, F, H, W, A, V, export):
+    def forward(ctx, qkv, n0, n1, n2, A, V, export, scratch):
         remember(ctx)
         _chk(qkv)
         qkv = _c(qkv)
-        ld = qkv.shape[1]
-        o = torch.empty(F * H * W, V, dtype=torch.float32, device=qkv.device)
-        lse = torch.empty(F * H * W, dtype=torch.float32, device=qkv.device)
+        ld, rows = qkv.shape[1], n0 * n1 * n2
+        o = torch.empty(rows, V, dtype=torch.float32, device=qkv.device)
+        lse = torch.empty(rows, dtype=torch.float32, device=qkv.device)
         p = qkv.data_ptr()
-        check(getattr(lib(), export + "_fwd")(p, ld, p + 4 * A, ld, p + 8 * A, ld, _ptr(o), V, _ptr(lse), F, H, W, A, V, _stream()),
+        check(getattr(lib(), export + "_fwd")(p, ld, p + 4 * A, ld, p + 8 * A, ld, _ptr(o), V, _ptr(lse), n0, n1, n2, A, V, _stream()),
               export + "_fwd")
         ctx.save_for_backward(qkv, lse)
-        ctx.dims = (F, H, W, A, V, export)
+        ctx.dims = (n0, n1, n2, A, V, export, scratch)
         return o
 
     @scoped
     def backward(ctx, go):
         qkv, lse = ctx.saved_tensors
-        F, H, W, A, V, export = ctx.dims
+        n0, n1, n2, A, V, export, scratch = ctx.dims
         _chk(go)
         go = _c(go)
         ld = qkv.shape[1]
         dqkv = torch.empty_like(qkv)
         if ld > 2 * A + V:
             dqkv[:, 2 * A + V:].zero_()
-        D = torch.empty(2 * F * H * W, dtype=torch.float32, device=qkv.device)
+        D = [torch.empty(2 * n0 * n1 * n2, dtype=torch.float32, device=qkv.device)] if scratch else []
         p, d = qkv.data_ptr(), dqkv.data_ptr()
-        check(getattr(lib(), export + "_bwd")(p, ld, p + 4 * A, ld, p + 8 * A, ld, _ptr(go), V, _ptr(lse), _ptr(D),
-                                              d, ld, d + 4 * A, ld, d + 8 * A, ld, F, H, W, A, V, _stream()), export + "_bwd")
-        return dqkv, None, None, None, None, None, None
+        check(getattr(lib(), export + "_bwd")(p, ld, p + 4 * A, ld, p + 8 * A, ld, _ptr(go), V, _ptr(lse), *map(_ptr, D),
+                                              d, ld, d + 4 * A, ld, d + 8 * A, ld, n0, n1, n2, A, V, _stream()), export + "_bwd")
+        return dqkv, None, None, None, None, None, None, None
+
+
+def _check_qkv(name, qkv, n0, n1, n2, A, V, temporal=False):
+    """the qkv [n0*n1*n2, >= 2A+V] check of every packed op.  temporal: (n0, n1, n2) = (N, T, HW) with N, HW >= 1 (T has the op's own
+    check), and the kernels read the rows as float4: a row length % 4 == 0"""
+    rows, ok = ("N*T*HW", n0 >= 1 and n2 >= 1) if temporal else ("F*H*W", True)
+    if not ok or qkv.dim() != 2 or qkv.shape[0] != n0 * n1 * n2 or qkv.shape[1] < 2 * A + V:
+        raise RuntimeError(f"{name}: qkv must be [{rows}, >= {2 * A + V}]" + (" with N, HW >= 1" if temporal else ""))
+    if temporal and qkv.shape[1] % 4:
+        raise RuntimeError(f"{name}: the row length of qkv ({qkv.shape[1]}) must be a multiple of 4")
 
 
 def _nl_unpacked(packed, name, q, k, v, H, W):
@@ -2565,23 +2574,6 @@ def _nl_unpacked(packed, name, q, k, v, H, W):
     return packed(qkv, F, H, W, A, V).view(F, P, V)
 
 
-def nonlocal_attn_packed(qkv, F, H, W, A, V):
-    """qkv [F*H*W, ld >= 2A+V] (columns q | k | v, k and v UNPOOLED) -> softmax(q pool(k)^T) pool(v)  [F*H*W, V]"""
-    if A not in _NL_GRID or V != 4 * A:
-        raise RuntimeError(f"nonlocal_attn: (attn dim, value dim) = ({A}, {V}) is not one of the AE configs' {[(a, 4 * a) for a in _NL_GRID]}")
-    if H * W != _NL_GRID[A] ** 2 or H % 2 or W & (W - 1):
-        raise RuntimeError(f"nonlocal_attn: a {H}x{W} grid at C = {8 * A} is not one of the AE configs' "
-                           f"({', '.join(f'{s}x{s} @ {8 * a}' for a, s in _NL_GRID.items())})")
-    if qkv.dim() != 2 or qkv.shape[0] != F * H * W or qkv.shape[1] < 2 * A + V:
-        raise RuntimeError(f"nonlocal_attn: qkv must be [F*H*W, >= {2 * A + V}]")
-    return _NonLocalAttn.apply(qkv, F, H, W, A, V, "npvp_nonlocal_attn")
-
-
-def nonlocal_attn(q, k, v, H, W):
-    """q, k, v (F, H*W, a / a / v) - k and v the projections BEFORE the 2x2 max-pool - -> (F, H*W, v)"""
-    return _nl_unpacked(nonlocal_attn_packed, "nonlocal_attn", q, k, v, H, W)
-
-
 def nonlocal_attn_dims(A, V):
     """True where the non-local attention kernels have an instantiation for (attn dim, value dim)"""
     return A in _NL_GRID and V == 4 * A
@@ -2592,6 +2584,22 @@ def nonlocal_attn_config_shape(A, V, H, W):
     return nonlocal_attn_dims(A, V) and H * W == _NL_GRID[A] ** 2 and H % 2 == 0 and W & (W - 1) == 0
 
 
+def nonlocal_attn_packed(qkv, F, H, W, A, V):
+    """qkv [F*H*W, ld >= 2A+V] (columns q | k | v, k and v UNPOOLED) -> softmax(q pool(k)^T) pool(v)  [F*H*W, V]"""
+    if not nonlocal_attn_dims(A, V):
+        raise RuntimeError(f"nonlocal_attn: (attn dim, value dim) = ({A}, {V}) is not one of the AE configs' {[(a, 4 * a) for a in _NL_GRID]}")
+    if not nonlocal_attn_config_shape(A, V, H, W):
+        raise RuntimeError(f"nonlocal_attn: a {H}x{W} grid at C = {8 * A} is not one of the AE configs' "
+                           f"({', '.join(f'{s}x{s} @ {8 * a}' for a, s in _NL_GRID.items())})")
+    _check_qkv("nonlocal_attn", qkv, F, H, W, A, V)
+    return _PackedAttn.apply(qkv, F, H, W, A, V, "npvp_nonlocal_attn", True)
+
+
+def nonlocal_attn(q, k, v, H, W):
+    """q, k, v (F, H*W, a / a / v) - k and v the projections BEFORE the 2x2 max-pool - -> (F, H*W, v)"""
+    return _nl_unpacked(nonlocal_attn_packed, "nonlocal_attn", q, k, v, H, W)
+
+
 def nonlocal_attn_grid_packed(qkv, F, H, W, A, V):
     """nonlocal_attn_packed on any grid H, W >= 2 (odd, rectangular, not a power of two): the keys / values are the
     floor(H/2) x floor(W/2) windows of nn.MaxPool2d((2, 2), stride=2); a config shape runs nonlocal_attn_packed's own kernels"""
@@ -2599,9 +2607,8 @@ def nonlocal_attn_grid_packed(qkv, F, H, W, A, V):
         raise RuntimeError(f"nonlocal_attn_grid: (attn dim, value dim) = ({A}, {V}) is not one of {[(a, 4 * a) for a in _NL_GRID]}")
     if H < 2 or W < 2:
         raise RuntimeError(f"nonlocal_attn_grid: a {H}x{W} grid has no 2x2 window")
-    if qkv.dim() != 2 or qkv.shape[0] != F * H * W or qkv.shape[1] < 2 * A + V:
-        raise RuntimeError(f"nonlocal_attn_grid: qkv must be [F*H*W, >= {2 * A + V}]")
-    return _NonLocalAttn.apply(qkv, F, H, W, A, V, "npvp_nonlocal_attn_grid")
+    _check_qkv("nonlocal_attn_grid", qkv, F, H, W, A, V)
+    return _PackedAttn.apply(qkv, F, H, W, A, V, "npvp_nonlocal_attn_grid", True)
 
 
 def nonlocal_attn_grid(q, k, v, H, W):
@@ -2609,48 +2616,30 @@ def nonlocal_attn_grid(q, k, v, H, W):
     return _nl_unpacked(nonlocal_attn_grid_packed, "nonlocal_attn_grid", q, k, v, H, W)
 
 
+def nonlocal_attn_any_packed(qkv, F, H, W, A, V):
+    """the model's call: nonlocal_attn_packed at the configs' own (C, grid) pairs (their exact-tile kernels), nonlocal_attn_grid_packed
+    at any other grid; an (A, V) that no kernel has stays with the first, which refuses it.  Both are looked up here, at call time"""
+    other_grid = nonlocal_attn_dims(A, V) and not nonlocal_attn_config_shape(A, V, H, W)
+    op = nonlocal_attn_grid_packed if other_grid else nonlocal_attn_packed
+    return op(qkv, F, H, W, A, V)
+
+
 TEMPORAL_ATTN_MAX_T = 32        # npvp_temporal_attn_*: a pixel's T x T scores are not tiled over the keys
-
-
-class _TemporalAttn(_Function):
-    """softmax(q k^T) v of NonLocalAttenion1D (ref/models/submodules.py:229-237; unscaled scores) over the T frames of every pixel, from
-    ONE projection tensor qkv [N*T*HW, ld] = [q | k | v | zero padding] of channels-last token rows (row = (n T + t) HW + p); the
-    gradient comes back in the same layout, its pad columns zero.  One backward launch writes dq, dk and dv."""
-
-    @staticmethod
-    def forward(ctx, qkv, N, T, HW, A, V):
-        remember(ctx)
-        _chk(qkv)
-        qkv = _c(qkv)
-        ld = qkv.shape[1]
-        o = torch.empty(N * T * HW, V, dtype=torch.float32, device=qkv.device)
-        lse = torch.empty(N * T * HW, dtype=torch.float32, device=qkv.device)
-        p = qkv.data_ptr()
-        check(lib().npvp_temporal_attn_fwd(p, ld, p + 4 * A, ld, p + 8 * A, ld, _ptr(o), V, _ptr(lse), N, T, HW, A, V, _stream()),
-              "npvp_temporal_attn_fwd")
-        ctx.save_for_backward(qkv, lse)
-        ctx.dims = (N, T, HW, A, V)
-        return o
-
-    @scoped
-    def backward(ctx, go):
-        qkv, lse = ctx.saved_tensors
-        N, T, HW, A, V = ctx.dims
-        _chk(go)
-        go = _c(go)
-        ld = qkv.shape[1]
-        dqkv = torch.empty_like(qkv)
-        if ld > 2 * A + V:
-            dqkv[:, 2 * A + V:].zero_()
-        p, d = qkv.data_ptr(), dqkv.data_ptr()
-        check(lib().npvp_temporal_attn_bwd(p, ld, p + 4 * A, ld, p + 8 * A, ld, _ptr(go), V, _ptr(lse), d, ld, d + 4 * A, ld, d + 8 * A, ld,
-                                           N, T, HW, A, V, _stream()), "npvp_temporal_attn_bwd")
-        return dqkv, None, None, None, None, None
 
 
 def temporal_attn_dims():
     """the (attn dim, value dim) pairs the temporal attention kernels have: the table of the 2-D kernels"""
     return [(a, 4 * a) for a in _NL_GRID]
+
+
+def _ta_unpacked(packed, name, q, k, v, T):
+    """q, k (M, T, a), v (M, T, v) -> packed(q | k | v as one clip of M pixels, row = t M + m) as (M, T, v)"""
+    M, Tq, A = q.shape
+    V = v.shape[-1]
+    if k.shape != q.shape or v.shape[:2] != q.shape[:2] or Tq != T:
+        raise RuntimeError(f"{name}: q / k (M, T, a), v (M, T, v)")
+    qkv = torch.cat([q, k, v], 2).transpose(0, 1).reshape(T * M, 2 * A + V)
+    return packed(qkv, 1, T, M, A, V).view(T, M, V).transpose(0, 1)
 
 
 def temporal_attn_packed(qkv, N, T, HW, A, V):
@@ -2660,59 +2649,14 @@ def temporal_attn_packed(qkv, N, T, HW, A, V):
         raise RuntimeError(f"temporal_attn: (attn dim, value dim) = ({A}, {V}) is not one of {temporal_attn_dims()}")
     if not 1 <= T <= TEMPORAL_ATTN_MAX_T:
         raise RuntimeError(f"temporal_attn: T = {T} frames per clip, 1 <= T <= {TEMPORAL_ATTN_MAX_T} (longer clips need key tiling)")
-    if N < 1 or HW < 1 or qkv.dim() != 2 or qkv.shape[0] != N * T * HW or qkv.shape[1] < 2 * A + V:
-        raise RuntimeError(f"temporal_attn: qkv must be [N*T*HW, >= {2 * A + V}] with N, HW >= 1")
-    if qkv.shape[1] % 4:
-        raise RuntimeError(f"temporal_attn: the row length of qkv ({qkv.shape[1]}) must be a multiple of 4")
-    return _TemporalAttn.apply(qkv, N, T, HW, A, V)
+    _check_qkv("temporal_attn", qkv, N, T, HW, A, V, temporal=True)
+    return _PackedAttn.apply(qkv, N, T, HW, A, V, "npvp_temporal_attn", False)
 
 
 def temporal_attn(q, k, v, T):
     """q, k (M, T, a), v (M, T, v) - M sequences of T frames, as NonLocalAttenion1D sees them - -> (M, T, v).  (Packs the rows as
     one clip of M pixels; the model path hands its token rows to temporal_attn_packed without a copy.)"""
-    M, Tq, A = q.shape
-    V = v.shape[-1]
-    if k.shape != q.shape or v.shape[:2] != q.shape[:2] or Tq != T:
-        raise RuntimeError("temporal_attn: q / k (M, T, a), v (M, T, v)")
-    qkv = torch.cat([q, k, v], 2).transpose(0, 1).reshape(T * M, 2 * A + V)          # row = t M + m
-    return temporal_attn_packed(qkv, 1, T, M, A, V).view(T, M, V).transpose(0, 1)
-
-
-class _TemporalAttnLong(_Function):
-    """_TemporalAttn for any clip length (npvp_temporal_attn_long_fwd/bwd): the keys are tiled above TEMPORAL_ATTN_MAX_T frames, at
-    or below it the launches and the bits are _TemporalAttn's.  The backward hands the kernels their scratch D [2][N*T*HW]."""
-
-    @staticmethod
-    def forward(ctx, qkv, N, T, HW, A, V):
-        remember(ctx)
-        _chk(qkv)
-        qkv = _c(qkv)
-        ld = qkv.shape[1]
-        o = torch.empty(N * T * HW, V, dtype=torch.float32, device=qkv.device)
-        lse = torch.empty(N * T * HW, dtype=torch.float32, device=qkv.device)
-        p = qkv.data_ptr()
-        check(lib().npvp_temporal_attn_long_fwd(p, ld, p + 4 * A, ld, p + 8 * A, ld, _ptr(o), V, _ptr(lse), N, T, HW, A, V, _stream()),
-              "npvp_temporal_attn_long_fwd")
-        ctx.save_for_backward(qkv, lse)
-        ctx.dims = (N, T, HW, A, V)
-        return o
-
-    @scoped
-    def backward(ctx, go):
-        qkv, lse = ctx.saved_tensors
-        N, T, HW, A, V = ctx.dims
-        _chk(go)
-        go = _c(go)
-        ld = qkv.shape[1]
-        dqkv = torch.empty_like(qkv)
-        if ld > 2 * A + V:
-            dqkv[:, 2 * A + V:].zero_()
-        D = torch.empty(2 * N * T * HW, dtype=torch.float32, device=qkv.device)
-        p, d = qkv.data_ptr(), dqkv.data_ptr()
-        check(lib().npvp_temporal_attn_long_bwd(p, ld, p + 4 * A, ld, p + 8 * A, ld, _ptr(go), V, _ptr(lse), _ptr(D),
-                                                d, ld, d + 4 * A, ld, d + 8 * A, ld, N, T, HW, A, V, _stream()),
-              "npvp_temporal_attn_long_bwd")
-        return dqkv, None, None, None, None, None
+    return _ta_unpacked(temporal_attn_packed, "temporal_attn", q, k, v, T)
 
 
 def temporal_attn_long_packed(qkv, N, T, HW, A, V):
@@ -2722,21 +2666,13 @@ def temporal_attn_long_packed(qkv, N, T, HW, A, V):
         raise RuntimeError(f"temporal_attn_long: (attn dim, value dim) = ({A}, {V}) is not one of {temporal_attn_dims()}")
     if T < 1:
         raise RuntimeError(f"temporal_attn_long: T = {T} frames per clip, T >= 1")
-    if N < 1 or HW < 1 or qkv.dim() != 2 or qkv.shape[0] != N * T * HW or qkv.shape[1] < 2 * A + V:
-        raise RuntimeError(f"temporal_attn_long: qkv must be [N*T*HW, >= {2 * A + V}] with N, HW >= 1")
-    if qkv.shape[1] % 4:
-        raise RuntimeError(f"temporal_attn_long: the row length of qkv ({qkv.shape[1]}) must be a multiple of 4")
-    return _TemporalAttnLong.apply(qkv, N, T, HW, A, V)
+    _check_qkv("temporal_attn_long", qkv, N, T, HW, A, V, temporal=True)
+    return _PackedAttn.apply(qkv, N, T, HW, A, V, "npvp_temporal_attn_long", True)
 
 
 def temporal_attn_long(q, k, v, T):
     """temporal_attn for any T >= 1: q, k (M, T, a), v (M, T, v) -> (M, T, v)"""
-    M, Tq, A = q.shape
-    V = v.shape[-1]
-    if k.shape != q.shape or v.shape[:2] != q.shape[:2] or Tq != T:
-        raise RuntimeError("temporal_attn_long: q / k (M, T, a), v (M, T, v)")
-    qkv = torch.cat([q, k, v], 2).transpose(0, 1).reshape(T * M, 2 * A + V)          # row = t M + m
-    return temporal_attn_long_packed(qkv, 1, T, M, A, V).view(T, M, V).transpose(0, 1)
+    return _ta_unpacked(temporal_attn_long_packed, "temporal_attn_long", q, k, v, T)
 
 
 def temporal_attn_any_packed(qkv, N, T, HW, A, V):

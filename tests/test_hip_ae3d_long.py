@@ -341,3 +341,35 @@ def test_frozen_fused_pair_on_40_frames(npvp):
     assert npvp._lib.lib().npvp_launch_count() > n0
     assert rel(got, stock) < 1e-4, rel(got, stock)
     assert torch.isfinite(rec).all() and rec.shape == frames.shape
+
+
+# ------------------------------------------------------------------------------------------------------------------ the one node
+def test_each_packed_op_calls_its_own_exports(npvp):
+    """the four packed attention ops share one autograd node: each makes exactly one _fwd and one _bwd call, of its own stem and of no
+    other, and hands the backward a scratch D (the 22 arguments of the header) everywhere but in npvp_temporal_attn_bwd (21: it has
+    no D).  (The numbers are held to float64 by the tests of each op.)"""
+    L, ops = npvp._lib.lib(), npvp.ops
+    stems = ("npvp_nonlocal_attn", "npvp_nonlocal_attn_grid", "npvp_temporal_attn", "npvp_temporal_attn_long")
+    real = {s + p: getattr(L, s + p) for s in stems for p in ("_fwd", "_bwd")}
+    calls = []
+    count = lambda name: lambda *a: calls.append((name, len(a))) or real[name](*a)
+    A, V, ld = 8, 32, 48
+    cases = [(ops.nonlocal_attn_packed, stems[0], (1, 64, 64), 22),               # the smallest config shape at A = 8
+             (ops.nonlocal_attn_grid_packed, stems[1], (2, 3, 5), 22),            # odd in both directions
+             (ops.temporal_attn_packed, stems[2], (2, 3, 5), 21),
+             (ops.temporal_attn_long_packed, stems[3], (1, 33, 3), 22)]           # the shortest clip on the key-tiled kernels
+    assert all(len(npvp._lib.SIGNATURES[stem + "_bwd"][1]) == n for _, stem, _, n in cases)
+    try:
+        for name in real:
+            setattr(L, name, count(name))
+        for op, stem, (n0, n1, n2), nbwd in cases:
+            del calls[:]
+            qkv = O.seeded_randn((n0 * n1 * n2, ld), 610).mul_(0.5).to(DEV).requires_grad_()
+            o = op(qkv, n0, n1, n2, A, V)
+            o.backward(torch.ones_like(o))
+            torch.cuda.synchronize()
+            assert calls == [(stem + "_fwd", 15), (stem + "_bwd", nbwd)], (stem, calls)
+            assert o.shape == (n0 * n1 * n2, V) and torch.isfinite(qkv.grad).all()
+    finally:
+        for name, f in real.items():
+            setattr(L, name, f)

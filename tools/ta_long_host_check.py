@@ -168,7 +168,7 @@ def main():
         with open(src, "w") as f:
             f.write(PRELUDE + body + MAIN)
         subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-pthread",
-                        src, "-o", exe], check=True)
+                        "-I" + os.path.dirname(SRC), src, "-o", exe], check=True)
         return subprocess.run([exe]).returncode
 
 
