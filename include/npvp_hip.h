@@ -587,6 +587,44 @@ int npvp_act_bwd(const float* g, const float* y, float* dx, long long n, int act
 int npvp_bias_act_scaled(const float* x, const float* bias, const float* scale, const float* residual, float* out, long long outer,
                          long long inner, int C, int layout, int act, npvp_stream_t stream);
 
+/* ---- 3 x 3 convolutions of the frozen encoder on the matrix cores (csrc/conv3x3.hip; opt-in, to_device_layout(..., conv3x3="hip")):
+ * the stride-1 "same" convolutions with C_in, C_out multiples of 64 - the spatial_conv of every Factorized3DConvAttn
+ * (ref/models/submodules.py:23-27, zero padding) and the two convolutions of every ResnetBlock (ref/models/ResNetAutoEncoder.py:
+ * 206-261, ReflectionPad2d(1)) - as ONE forward-only implicit-GEMM launch on channels-last frames, BatchNorm folded into w and bias:
+ *   y[f,h,w,co] = act( sum_{kh,kw,ci} x[f, src(h,kh), src(w,kw), ci] * w[co,ci,kh,kw] + bias[co] ) (+ residual[f,h,w,co])
+ * x [F][H][W][C_in], y and residual (nullable) [F][H][W][C_out], fp32; act as npvp_bias_act (0 none, 1 ReLU, 2 tanh, 3 sigmoid).
+ * pad_mode 0: zero padding (an out-of-range tap contributes 0; H, W >= 1).  pad_mode 1: ReflectionPad2d(1) (-1 -> 1, H -> H - 2;
+ * H, W >= 2).  The padding is index math (npvp_conv3x3_src): no padded copy, no im2col tensor, no separate epilogue pass.  Any
+ * H x W; output tiles may straddle frame borders, taps never do.  F * H * W < 2^31.
+ * Arithmetic: precision 6 of npvp_gemm_f32 ("f16x3": both operands scaled by the power of two of their amax slot and split into two
+ * fp16 terms, three v_mfma_f32_32x32x16_f16 per product, fp32 accumulation) on the GEMM M = F H W, N = C_out, K = 9 C_in with K
+ * ordered (kh, kw, ci).  No split-K and no atomics on y: every output element is written exactly once and two runs give the same
+ * bits.  Unlike the GEMM there is no per-row rescue: one scale per tensor (a pixel 2^18 below the tensor's bound keeps subnormal low
+ * terms, i.e. an absolute error of 2^-40 of the bound).  Nothing here synchronises; every call can be captured in a graph. */
+/* bytes of the weight planes: two fp16 terms of [C_out][9 C_in] */
+long long npvp_conv3x3_planes_bytes(int C_in, int C_out);
+/* w [C_out][C_in][3][3] (contiguous) -> planes[2 terms][9 C_in / 8][C_out][8 over k], k = (kh * 3 + kw) * C_in + ci - the F layout of
+ * npvp_split_weight_f16 for the matrix [C_out][9 C_in], so a K-step of the kernel stays inside one tap -, scaled by the power of two
+ * of w's amax, which is (re)computed into the slot w_amax (zeroed here first).  Once per frozen weight. */
+int npvp_conv3x3_planes(const float* w, int C_in, int C_out, void* planes, float* w_amax, npvp_stream_t stream);
+/* The convolution.  planes / w_amax: from npvp_conv3x3_planes; x_amax: the slot that bounds |x| (its producer's, or npvp_amax over
+ * [F H W][C_in]); y_amax (nullable): receives the bound of the values stored to y, as the GEMM epilogues' c_amax does - the x_amax
+ * of a following convolution at no extra pass.  workspace / ws_bytes: reserved, the kernel needs none (pass NULL, 0).  x, y, residual
+ * and planes 16-byte aligned; y must not overlap x or residual. */
+int npvp_conv3x3_f16(const float* x, const void* planes, const float* bias, const float* residual, float* y, int F, int H, int W,
+                     int C_in, int C_out, int pad_mode, int act, const float* x_amax, const float* w_amax, float* y_amax,
+                     void* workspace, long long ws_bytes, npvp_stream_t stream);
+/* The plan npvp_conv3x3_f16 launches for a shape (it launches what the same planner returns): out6 = {tile variant (1: 128 x 128
+ * output tiles, C_out % 128 == 0; 2: 128 x 64), rows per tile, columns per tile, row tiles, column tiles, workgroups (256 threads
+ * each, one per tile)}.  Returns 0, or -1 for a shape the convolution refuses.  Pure function. */
+int npvp_conv3x3_route(int F, int H, int W, int C_in, int C_out, int* out6);
+/* out4 = {m0, m1, n0, n1}: the rows [m0, m1) of [F H W] and columns [n0, n1) of C_out that workgroup `block` of that plan stores -
+ * the function the kernel itself calls.  Pure function. */
+int npvp_conv3x3_tile(int F, int H, int W, int C_in, int C_out, int block, int* out4);
+/* Source coordinate of tap `tap` (0, 1, 2 = offsets -1, 0, +1) at output coordinate `c` of an axis of `extent` pixels, or -1 for a tap
+ * that contributes 0 (zero padding) - the __host__ __device__ function the kernel calls (csrc/conv3x3_index.h).  -2: bad argument. */
+int npvp_conv3x3_src(int c, int tap, int extent, int pad_mode);
+
 /* ---- Stage-1 autoencoder training (csrc/ae_train.hip): LitAE.training_step / shared_step (ref/models/ResNetAutoEncoder.py:13-49)
  * through ResnetEncoder / ResnetDecoder (ref :51-204) and NonLocalAttenion2D (ref/models/submodules.py:98-176); the convolutions
  * stay MIOpen's.  Every entry point is deterministic (fixed-order sums, no atomics) and needs no zero-filled buffer.

@@ -10,13 +10,6 @@
 
 namespace npvp {
 
-__device__ __forceinline__ float ae_act(float v, int act) {
-  if (act == 1) return fmaxf(v, 0.f);
-  if (act == 2) return tanhf(v);
-  if (act == 3) return 1.f / (1.f + __expf(-v));
-  return v;
-}
-
 template <bool VEC4>
 __global__ void bias_act_kernel(const float* __restrict__ x, const float* __restrict__ bias, const float* __restrict__ res,
                                 float* __restrict__ out, long long outer, long long inner, int C, int layout, int act) {

@@ -123,6 +123,14 @@ __device__ __forceinline__ float amax4(float m, const float4& v) {
   return fmaxf(fmaxf(fmaxf(m, fabsf(v.x)), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w)));
 }
 
+// activation of the frozen autoencoder's epilogues (ae.hip, conv3x3.hip): 0 none, 1 ReLU, 2 tanh, 3 sigmoid
+__device__ __forceinline__ float ae_act(float v, int act) {
+  if (act == 1) return fmaxf(v, 0.f);
+  if (act == 2) return tanhf(v);
+  if (act == 3) return 1.f / (1.f + __expf(-v));
+  return v;
+}
+
 // acc += a * b as exactly one v_fmac_f32 (the optimiser can neither pair it into v_pk_fma_f32 nor split it).
 __device__ __forceinline__ void fmac_scalar(float& acc, float a, float b) {
 #if defined(__HIP_DEVICE_COMPILE__)

@@ -13,6 +13,10 @@ checkpoints load.  `learn_3d=True` adds the temporal half of every Factorized3DC
            bias / BatchNorm / ReLU / skip-add passes; the decoder's input gradient goes through `npvp_act_bwd`.
            `attn2d="hip"` (opt-in, inference only) also sends the encoder's NonLocalAttenion2D through the non-local attention
            kernels and one `npvp_bias_act_scaled` pass (`_fused_attn2d`); the default `"stock"` leaves it on stock PyTorch.
+           `conv3x3="hip"` (opt-in, inference only) sends the encoder's 3 x 3 stride-1 convolutions with 64-multiple channels
+           (every spatial_conv, both convolutions of every ResnetBlock) through ONE f16x3 implicit-GEMM launch each
+           (`ops.conv3x3_packed`, csrc/conv3x3.hip: padding as index math, bias + activation + skip in its epilogue); the default
+           `"stock"` leaves them on MIOpen + `npvp_bias_act`.
 """
 import functools
 import types
@@ -55,8 +59,29 @@ class FoldedConvAct(nn.Module):
         self.output_padding = conv.output_padding if self.transposed else None
         self.act = 0 if act is None else _ACT_CODE[type(act)]
         self.pad = pad
+        self.conv3x3_pad = None          # "zero" / "reflect" once routed to the 3 x 3 kernel (fuse_frozen_autoencoder(conv3x3="hip"))
+
+    def route_conv3x3(self, pad):
+        """send this convolution through ops.conv3x3_packed with the padding rule `pad`; the weight planes and the weight's amax slot
+        are non-persistent buffers (the state-dict keys do not change), built here when the weight is on the device and at the first
+        routed forward otherwise"""
+        self.conv3x3_pad = pad
+        planes, w_amax = ops.conv3x3_planes(self.weight) if self.weight.is_cuda else (None, None)
+        self.register_buffer("_npvp_planes", planes, persistent=False)
+        self.register_buffer("_npvp_w_amax", w_amax, persistent=False)
+
+    def _conv3x3(self, x, residual):
+        if torch.is_grad_enabled() and (x.requires_grad or (residual is not None and residual.requires_grad)):
+            raise NotImplementedError('conv3x3="hip" (to_device_layout / fuse_frozen_autoencoder) is inference-only: the input of this '
+                                      'convolution requires grad; fuse the pair with conv3x3="stock" to differentiate through it')
+        if self._npvp_planes is None or self._npvp_planes.device != x.device:
+            self._npvp_planes, self._npvp_w_amax = ops.conv3x3_planes(self.weight.to(x.device))
+        return ops.conv3x3_packed(x, self._npvp_planes, self._npvp_w_amax, self.bias, self.conv3x3_pad, self.act, residual)
 
     def forward(self, x, residual=None):
+        # routed: channels-last frames only (anything else keeps the stock forward below: no silent copy)
+        if self.conv3x3_pad is not None and _channels_last_only(x) and (residual is None or _channels_last_only(residual)):
+            return self._conv3x3(x, residual)
         if self.pad is not None:
             x = self.pad(x)
         if self.transposed:
@@ -64,6 +89,10 @@ class FoldedConvAct(nn.Module):
         else:
             y = F.conv2d(x, self.weight, None, self.stride, self.padding, self.dilation, 1)
         return ops.bias_act(y, self.bias, self.act, residual)
+
+
+def _channels_last_only(x):
+    return x.dim() == 4 and x.is_contiguous(memory_format=torch.channels_last) and not x.is_contiguous()
 
 
 def _fold_sequential(seq):
@@ -92,6 +121,38 @@ def _check_attn2d(attn2d):
         raise ValueError(f"attn2d={attn2d!r}: the route of the frozen encoder's NonLocalAttenion2D is one of {ATTN2D_ROUTES}")
 
 
+CONV3X3_ROUTES = ("stock", "hip")
+
+
+def _check_conv3x3(conv3x3):
+    if conv3x3 not in CONV3X3_ROUTES:
+        raise ValueError(f"conv3x3={conv3x3!r}: the route of the frozen encoder's 3 x 3 convolutions is one of {CONV3X3_ROUTES}")
+
+
+def _conv3x3_takes_hip(m):
+    """the padding rule ("zero" / "reflect") under which the 3 x 3 kernel runs this FoldedConvAct, or None: a 3 x 3, stride-1,
+    undilated, not transposed convolution with 64-multiple channel counts, zero-padded by 1 or behind a ReflectionPad2d(1)"""
+    if m.transposed or tuple(m.weight.shape[2:]) != (3, 3) or tuple(m.stride) != (1, 1) or tuple(m.dilation) != (1, 1):
+        return None
+    # every 64-multiple channel count stays on the kernel: at C = 64, 128, 256 and 512 (the encoders' four (C, grid) pairs, zero and
+    # reflection padding) both hip timings beat both MIOpen + npvp_bias_act timings (profiles/frozen_conv3x3_bench.txt); a channel
+    # count that loses there would be named and excluded here
+    if not ops.conv3x3_takes(m.weight.shape[1], m.weight.shape[0]):
+        return None
+    if m.pad is None:
+        return "zero" if tuple(m.padding) == (1, 1) else None
+    if type(m.pad) is nn.ReflectionPad2d and tuple(m.pad.padding) == (1, 1, 1, 1) and tuple(m.padding) == (0, 0):
+        return "reflect"
+    return None
+
+
+def _route_conv3x3(folded):
+    for m in folded:
+        pad = _conv3x3_takes_hip(m)
+        if pad is not None:
+            m.route_conv3x3(pad)
+
+
 def _zero_or_bias(lin):
     return lin.bias if lin.bias is not None else torch.zeros(lin.out_features, dtype=lin.weight.dtype, device=lin.weight.device)
 
@@ -112,13 +173,18 @@ def _attn2d_takes_hip(a):
             and a.out_proj.bias is not None)
 
 
-def fuse_frozen_autoencoder(enc, dec, attn2d="stock"):
+def fuse_frozen_autoencoder(enc, dec, attn2d="stock", conv3x3="stock"):
     """In-place module surgery on an eval-mode pair that already holds its final weights; freezes its parameters (do it after load_state_dict:
     the folded modules no longer carry the reference's state-dict keys).  Returns (enc, dec).
     attn2d: "stock" (default) leaves every NonLocalAttenion2D of the encoder on its own forward (PyTorch: the (frames, H*W, H*W/4) scores
     in memory); "hip" sends those whose (attn_dim, value_dim) has non-local kernels (ops.nonlocal_attn_dims) through `_fused_attn2d`
-    (inference only: no scores in memory, one epilogue pass).  Any other value is refused."""
+    (inference only: no scores in memory, one epilogue pass).  Any other value is refused.
+    conv3x3: "stock" (default) leaves every convolution on MIOpen + npvp_bias_act; "hip" sends the ENCODER's FoldedConvActs that
+    `_conv3x3_takes_hip` accepts - every spatial_conv and ResnetBlock convolution with 64-multiple channels - through
+    ops.conv3x3_packed (inference only).  The 7 x 7 and stride-2 convolutions, ReplicationPad2d blocks and the decoder stay stock.
+    Any other value is refused."""
     _check_attn2d(attn2d)
+    _check_conv3x3(conv3x3)
     for m in (enc, dec):
         assert not m.training, "fuse_frozen_autoencoder: eval mode only (BatchNorm must use its running statistics)"
         for q in m.parameters():
@@ -150,6 +216,8 @@ def fuse_frozen_autoencoder(enc, dec, attn2d="stock"):
                     _register_wqkv(a)
             elif isinstance(mod, ResnetBlock):
                 mod.conv_block = _fold_sequential(mod.conv_block)
+        if conv3x3 == "hip":
+            _route_conv3x3([m for m in enc.modules() if isinstance(m, FoldedConvAct)])
         dec.model = _fold_sequential(dec.model)
     return enc, dec
 
@@ -458,10 +526,11 @@ def build_frozen_autoencoder(AE, img_channels):
     return enc, dec
 
 
-def to_device_layout(enc, dec, device, attn2d="stock"):
+def to_device_layout(enc, dec, device, attn2d="stock", conv3x3="stock"):
     """Move the frozen pair to an MI355X.  The ENCODER runs in torch.channels_last (MIOpen's NHWC kernels: 27.5 -> 24.8 ms
     for 640 frames of 64x64, and its (N*T,H,W,C) output is the predictor's canonical layout, so the layout transpose at
     the predictor's entry disappears); the decoder stays NCHW (NHWC measured slower: 9.0 -> 11.2 ms fwd + input-grad)."""
     _check_attn2d(attn2d)
+    _check_conv3x3(conv3x3)
     enc, dec = enc.to(device).to(memory_format=torch.channels_last), dec.to(device)
-    return fuse_frozen_autoencoder(enc.eval(), dec.eval(), attn2d=attn2d)
+    return fuse_frozen_autoencoder(enc.eval(), dec.eval(), attn2d=attn2d, conv3x3=conv3x3)
