@@ -625,6 +625,34 @@ int npvp_conv3x3_tile(int F, int H, int W, int C_in, int C_out, int block, int* 
  * that contributes 0 (zero padding) - the __host__ __device__ function the kernel calls (csrc/conv3x3_index.h).  -2: bad argument. */
 int npvp_conv3x3_src(int c, int tap, int extent, int pad_mode);
 
+/* ---- The stride-2 3 x 3 convolutions of the frozen encoder (opt-in, to_device_layout(..., down3x3="hip")): block1 and every
+ * block{i}_conv (ref/models/ResNetAutoEncoder.py:75-106: Conv2d(kernel 3, stride 2, padding 1), BatchNorm folded, ReLU), the same
+ * kernel, arithmetic, tiles and epilogue as npvp_conv3x3_f16 on the GEMM M = F Ho Wo, N = C_out, K = 9 C_in:
+ *   y[f,oh,ow,co] = act( sum_{kh,kw,ci} x[f, 2 oh + kh - 1, 2 ow + kw - 1, ci] * w[co,ci,kh,kw] + bias[co] ) (+ residual[f,oh,ow,co])
+ * x [F][H][W][C_in]; y and residual (nullable) [F][Ho][Wo][C_out] with Ho = (H + 1) / 2, Wo = (W + 1) / 2; a tap outside the H x W
+ * grid contributes 0 (zero padding only: no pad_mode) - on an odd extent that is tap 2 of the last output as well as tap 0 of the
+ * first.  C_in % 32 == 0 (block1 of the ngf = 32 encoders: one K-step per tap) and C_out % 64 == 0; F, H, W >= 1; H * W and
+ * F * Ho * Wo < 2^31.  Every output element is written exactly once (no split-K, no atomics on y); two runs give the same bits. */
+/* bytes of the weight planes, or -1 for channel counts outside the rule above */
+long long npvp_conv3x3s2_planes_bytes(int C_in, int C_out);
+/* npvp_conv3x3_planes under the stride-2 channel rule: the same layout planes[2 terms][9 C_in / 8][C_out][8 over k],
+ * k = (kh * 3 + kw) * C_in + ci, the same kernel, w_amax zeroed and recomputed here.  Once per frozen weight. */
+int npvp_conv3x3s2_planes(const float* w, int C_in, int C_out, void* planes, float* w_amax, npvp_stream_t stream);
+/* The convolution.  H, W: the INPUT grid.  planes / w_amax: from npvp_conv3x3s2_planes; x_amax: the slot that bounds |x|; y_amax
+ * (nullable): receives the bound of the values stored to y.  act as npvp_bias_act.  workspace / ws_bytes: reserved (NULL, 0).
+ * x, y, residual and planes 16-byte aligned; y must not overlap x or residual. */
+int npvp_conv3x3s2_f16(const float* x, const void* planes, const float* bias, const float* residual, float* y, int F, int H, int W,
+                       int C_in, int C_out, int act, const float* x_amax, const float* w_amax, float* y_amax, void* workspace,
+                       long long ws_bytes, npvp_stream_t stream);
+/* The plan npvp_conv3x3s2_f16 launches: out8 = the six fields of npvp_conv3x3_route for M = F Ho Wo, then Ho, Wo.  Returns 0, or -1
+ * for a shape the convolution refuses.  Pure function. */
+int npvp_conv3x3s2_route(int F, int H, int W, int C_in, int C_out, int* out8);
+/* out4 = {m0, m1, n0, n1}: the rows [m0, m1) of [F Ho Wo] and columns [n0, n1) of C_out that workgroup `block` stores.  Pure function. */
+int npvp_conv3x3s2_tile(int F, int H, int W, int C_in, int C_out, int block, int* out4);
+/* Source coordinate 2 o + tap - 1 of tap `tap` (0, 1, 2) at OUTPUT coordinate `o` (0 <= o < (extent + 1) / 2) of an axis of `extent`
+ * input pixels, or -1 for a tap that contributes 0 - the __host__ __device__ function the kernel calls.  -2: bad argument. */
+int npvp_conv3x3s2_src(int o, int tap, int extent);
+
 /* ---- Stage-1 autoencoder training (csrc/ae_train.hip): LitAE.training_step / shared_step (ref/models/ResNetAutoEncoder.py:13-49)
  * through ResnetEncoder / ResnetDecoder (ref :51-204) and NonLocalAttenion2D (ref/models/submodules.py:98-176); the convolutions
  * stay MIOpen's.  Every entry point is deterministic (fixed-order sums, no atomics) and needs no zero-filled buffer.

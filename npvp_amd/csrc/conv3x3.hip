@@ -16,6 +16,10 @@
 // stage afterwards; one barrier per K-step.  The gather is plain C++ (float4 loads, 16-byte LDS stores); the waits are the compiler's.
 // Epilogue in the accumulator layout: back to the operands' scale, + bias, activation, + residual, store (a wave stores 128-byte row
 // segments), the bound of the stored values into y_amax.  Every output element is written exactly once: no split-K, no atomics on y.
+//
+// The stride-2 downsampling convolutions (block1, block{i}_conv: zero padding 1, x [F][H][W][C_in] -> y [F][Ho][Wo][C_out],
+// npvp_conv3x3s2_*) are the same kernel with STRIDE = 2: only which pixel a tile row is and where its taps lie differ.  C_in % 32 == 0
+// there (block1 of the ngf = 32 encoders): a K-step of 32 still lies inside one tap, one K-step per tap at C_in = 32.
 #include "gemm.h"
 #include "f16_split.h"
 #include "conv3x3_index.h"
@@ -24,13 +28,17 @@ namespace npvp {
 
 struct Conv3x3Params {
   const float* x; const _Float16* planes; const float* bias; const float* res; float* y;
-  int H, W, Cin, Cout; long long M; int pad_mode, act;
+  int H, W, Cin, Cout; long long M; int pad_mode, act;      // H, W: the INPUT grid; M: output pixels
   const float* x_amax; const float* w_amax; float* y_amax;
   Conv3x3Plan plan;
 };
 
-template <int TN>
+// STRIDE 1: the "same" convolution, a tile row m is the pixel (f, h, w) of the H x W grid.  STRIDE 2 (zero padding 1, the downsampling
+// convolutions): a tile row m is the OUTPUT pixel (f, oh, ow) of the Ho x Wo grid (conv3x3s2_out) and its taps are resolved by
+// conv3x3s2_src inside frame f of the H x W input; p.M = F Ho Wo and p.pad_mode is not read.  Everything else is shared.
+template <int TN, int STRIDE = 1>
 __global__ __launch_bounds__(256, 2) void conv3x3_f16_kernel(Conv3x3Params p) {
+  static_assert(STRIDE == 1 || STRIDE == 2, "stride 1 or 2");
   constexpr int TM = 2, WN = 2, BM = 128, BN = WN * TN * 32;
   constexpr int KGS_A = BM * 16, A_PLANE = 4 * KGS_A, A_BYTES = 2 * A_PLANE;
   constexpr int KGS_B = BN * 16, B_PLANE = 4 * KGS_B, B_BYTES = 2 * B_PLANE;
@@ -46,6 +54,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_f16_kernel(Conv3x3Params p) {
   const float sa = amax_scale(amax_slot_read(p.x_amax)), sb = amax_scale(amax_slot_read(p.w_amax));
   const unsigned int cpeek = amax_peek_block(p.y_amax);
   const int H = p.H, W = p.W, Cin = p.Cin, Cout = p.Cout, HW = H * W;
+  const int Wo = STRIDE == 1 ? W : conv3x3s2_out(W), HWo = STRIDE == 1 ? HW : conv3x3s2_out(H) * Wo;      // the grid the rows index
   const int nk = (9 * Cin) >> 5, spt = Cin >> 5;       // K-steps; K-steps per tap
 
   // A staging: thread (rl, g) stages k-group g of rows rl and rl + 64 of the tile (rows past M: the last row, computed and not stored)
@@ -55,8 +64,8 @@ __global__ __launch_bounds__(256, 2) void conv3x3_f16_kernel(Conv3x3Params p) {
 #pragma unroll
   for (int q = 0; q < 2; ++q) {
     const long long m = (long long)m0 + rl + 64 * q < p.M ? (long long)m0 + rl + 64 * q : p.M - 1;
-    const int f = (int)(m / HW), rem = (int)(m - (long long)f * HW);
-    ph[q] = rem / W; pw[q] = rem - ph[q] * W;
+    const int f = (int)(m / HWo), rem = (int)(m - (long long)f * HWo);
+    ph[q] = rem / Wo; pw[q] = rem - ph[q] * Wo;
     fbase[q] = (long long)f * HW;
   }
   // B staging: piece i = t + 256 j of the tile's [term][k-group][column] pieces
@@ -80,7 +89,9 @@ __global__ __launch_bounds__(256, 2) void conv3x3_f16_kernel(Conv3x3Params p) {
     if (cs == 0) {
 #pragma unroll
       for (int q = 0; q < 2; ++q) {
-        const int sh = conv3x3_src(ph[q], kh, H, p.pad_mode), sw = conv3x3_src(pw[q], kw, W, p.pad_mode);
+        int sh, sw;
+        if constexpr (STRIDE == 1) { sh = conv3x3_src(ph[q], kh, H, p.pad_mode); sw = conv3x3_src(pw[q], kw, W, p.pad_mode); }
+        else { sh = conv3x3s2_src(ph[q], kh, H); sw = conv3x3s2_src(pw[q], kw, W); }
         aoff[q] = (sh < 0 || sw < 0) ? -1ll : (fbase[q] + (long long)sh * W + sw) * Cin + g * 8;
       }
     }
@@ -219,10 +230,39 @@ extern "C" long long npvp_conv3x3_planes_bytes(int C_in, int C_out) {
   return 2ll * 9 * C_in * C_out * 2;
 }
 
+// the stride-2 entry points' channel rule: a K-step of 32 inside one tap, 64-column tiles
+static bool conv3x3s2_channels_ok(int C_in, int C_out) { return C_in > 0 && C_out > 0 && C_in % 32 == 0 && C_out % 64 == 0; }
+
+static bool conv3x3s2_shape_ok(int F, int H, int W, int C_in, int C_out) {
+  return F > 0 && H > 0 && W > 0 && conv3x3s2_channels_ok(C_in, C_out) && (long long)H * W < (1ll << 31) &&
+         (long long)F * conv3x3s2_out(H) * conv3x3s2_out(W) < (1ll << 31) && 9ll * C_in < (1ll << 31);
+}
+
+#define CONV3X3S2_SHAPE_MSG "conv3x3s2: F, H, W >= 1, C_in a multiple of 32, C_out a multiple of 64, H * W and F * Ho * Wo below 2^31"
+
+extern "C" long long npvp_conv3x3s2_planes_bytes(int C_in, int C_out) {
+  if (!conv3x3s2_channels_ok(C_in, C_out)) return -1;
+  return 2ll * 9 * C_in * C_out * 2;
+}
+
+// zero the slot, the weight's amax into it, the scaled two-term planes (conv3x3_planes_kernel itself needs C_in % 8 == 0 only)
+static int conv3x3_planes_launch(const float* w, int C_in, int C_out, void* planes, float* w_amax, hipStream_t stream);
+
+extern "C" int npvp_conv3x3s2_planes(const float* w, int C_in, int C_out, void* planes, float* w_amax, hipStream_t stream) {
+  NPVP_CHECK_ARG(w && planes && w_amax, "conv3x3s2_planes: w, planes and w_amax must be non-null");
+  NPVP_CHECK_ARG(conv3x3s2_channels_ok(C_in, C_out), "conv3x3s2_planes: C_in must be a multiple of 32 and C_out a multiple of 64");
+  NPVP_CHECK_ARG(((uintptr_t)w % 16) == 0 && ((uintptr_t)planes % 16) == 0, "conv3x3s2_planes: w and planes must be 16-byte aligned");
+  return conv3x3_planes_launch(w, C_in, C_out, planes, w_amax, stream);
+}
+
 extern "C" int npvp_conv3x3_planes(const float* w, int C_in, int C_out, void* planes, float* w_amax, hipStream_t stream) {
   NPVP_CHECK_ARG(w && planes && w_amax, "conv3x3_planes: w, planes and w_amax must be non-null");
   NPVP_CHECK_ARG(C_in > 0 && C_out > 0 && C_in % 64 == 0 && C_out % 64 == 0, "conv3x3_planes: C_in and C_out must be multiples of 64");
   NPVP_CHECK_ARG(((uintptr_t)w % 16) == 0 && ((uintptr_t)planes % 16) == 0, "conv3x3_planes: w and planes must be 16-byte aligned");
+  return conv3x3_planes_launch(w, C_in, C_out, planes, w_amax, stream);
+}
+
+static int conv3x3_planes_launch(const float* w, int C_in, int C_out, void* planes, float* w_amax, hipStream_t stream) {
   NPVP_LAUNCH(conv3x3_zero_slot_kernel, dim3(1), dim3(256), 0, stream, w_amax);          // (a kernel, not a memset node: see gemm_f16.hip)
   NPVP_CHECK_LAUNCH();
   const int rc = npvp_amax(w, C_out, 9ll * C_in, 9ll * C_in, w_amax, stream);
@@ -276,6 +316,50 @@ extern "C" int npvp_conv3x3_f16(const float* x, const void* planes, const float*
   p.plan = conv3x3_plan(p.M, C_out);
   if (p.plan.variant == 1) NPVP_LAUNCH((conv3x3_f16_kernel<2>), dim3((unsigned)p.plan.grid), dim3(256), 0, stream, p);
   else NPVP_LAUNCH((conv3x3_f16_kernel<1>), dim3((unsigned)p.plan.grid), dim3(256), 0, stream, p);
+  NPVP_CHECK_LAUNCH();
+  return NPVP_OK;
+}
+
+// ---- stride 2, zero padding 1
+extern "C" int npvp_conv3x3s2_route(int F, int H, int W, int C_in, int C_out, int* out8) {
+  NPVP_CHECK_ARG(out8 && conv3x3s2_shape_ok(F, H, W, C_in, C_out), CONV3X3S2_SHAPE_MSG);
+  const int Ho = conv3x3s2_out(H), Wo = conv3x3s2_out(W);
+  const Conv3x3Plan p = conv3x3_plan((long long)F * Ho * Wo, C_out);
+  out8[0] = p.variant; out8[1] = p.bm; out8[2] = p.bn; out8[3] = p.tiles_m; out8[4] = p.tiles_n; out8[5] = p.grid;
+  out8[6] = Ho; out8[7] = Wo;
+  return NPVP_OK;
+}
+
+extern "C" int npvp_conv3x3s2_tile(int F, int H, int W, int C_in, int C_out, int block, int* out4) {
+  NPVP_CHECK_ARG(out4 && conv3x3s2_shape_ok(F, H, W, C_in, C_out), CONV3X3S2_SHAPE_MSG);
+  const long long M = (long long)F * conv3x3s2_out(H) * conv3x3s2_out(W);
+  const Conv3x3Plan p = conv3x3_plan(M, C_out);
+  NPVP_CHECK_ARG(block >= 0 && block < p.grid, "conv3x3s2_tile: block outside the plan's grid");
+  conv3x3_tile(p, block, M, out4[0], out4[1], out4[2], out4[3]);
+  return NPVP_OK;
+}
+
+extern "C" int npvp_conv3x3s2_src(int o, int tap, int extent) {
+  if (tap < 0 || tap > 2 || extent < 1 || o < 0 || o >= conv3x3s2_out(extent)) return -2;
+  return conv3x3s2_src(o, tap, extent);
+}
+
+extern "C" int npvp_conv3x3s2_f16(const float* x, const void* planes, const float* bias, const float* residual, float* y, int F, int H,
+                                  int W, int C_in, int C_out, int act, const float* x_amax, const float* w_amax, float* y_amax,
+                                  void* workspace, long long ws_bytes, hipStream_t stream) {
+  (void)workspace; (void)ws_bytes;
+  NPVP_CHECK_ARG(x && planes && bias && y && x_amax && w_amax, "conv3x3s2: x, planes, bias, y, x_amax and w_amax must be non-null");
+  NPVP_CHECK_ARG(conv3x3s2_shape_ok(F, H, W, C_in, C_out), CONV3X3S2_SHAPE_MSG);
+  NPVP_CHECK_ARG(act >= 0 && act <= 3, "conv3x3s2: act in 0..3");
+  NPVP_CHECK_ARG(((uintptr_t)x % 16) == 0 && ((uintptr_t)planes % 16) == 0 && ((uintptr_t)y % 16) == 0 && ((uintptr_t)residual % 16) == 0,
+                 "conv3x3s2: x, planes, y and residual must be 16-byte aligned");
+  Conv3x3Params p;
+  p.x = x; p.planes = (const _Float16*)planes; p.bias = bias; p.res = residual; p.y = y;
+  p.H = H; p.W = W; p.Cin = C_in; p.Cout = C_out; p.M = (long long)F * conv3x3s2_out(H) * conv3x3s2_out(W); p.pad_mode = 0; p.act = act;
+  p.x_amax = x_amax; p.w_amax = w_amax; p.y_amax = y_amax;
+  p.plan = conv3x3_plan(p.M, C_out);
+  if (p.plan.variant == 1) NPVP_LAUNCH((conv3x3_f16_kernel<2, 2>), dim3((unsigned)p.plan.grid), dim3(256), 0, stream, p);
+  else NPVP_LAUNCH((conv3x3_f16_kernel<1, 2>), dim3((unsigned)p.plan.grid), dim3(256), 0, stream, p);
   NPVP_CHECK_LAUNCH();
   return NPVP_OK;
 }

@@ -1,5 +1,5 @@
 // Index math of the 3 x 3 implicit-GEMM convolution (conv3x3.hip), as __host__ __device__ functions: the kernel and the launcher call
-// them, and the C ABI exports them unchanged (npvp_conv3x3_src, npvp_conv3x3_route, npvp_conv3x3_tile), so the part of the kernel that
+// them, and the C ABI exports them unchanged (npvp_conv3x3_src, npvp_conv3x3_route, npvp_conv3x3_tile, npvp_conv3x3s2_*), so the part of the kernel that
 // can go wrong silently - which pixel a tap reads, which outputs a workgroup owns - is tested on the host.
 #pragma once
 
@@ -21,8 +21,18 @@ NPVP_HD int conv3x3_src(int c, int tap, int extent, int pad_mode) {
   return s < 0 ? -s : 2 * extent - 2 - s;
 }
 
-// The plan of a launch: output tiles of bm rows (pixels, M = F H W of them) x bn columns (output channels), one workgroup per tile,
-// block b -> tile (b / tiles_n, b % tiles_n): the tiles of one row block are neighbours in launch order and share their A rows in L2.
+// Stride 2, zero padding 1 (the downsampling convolutions).  Outputs of an axis of `extent` pixels: floor((extent + 2 - 3) / 2) + 1.
+NPVP_HD int conv3x3s2_out(int extent) { return (extent + 1) / 2; }
+
+// Source coordinate of tap `tap` at OUTPUT coordinate o of that axis: 2 o + tap - 1, or -1 (the tap contributes 0) outside the axis -
+// tap 0 of the first output, and on an odd extent tap 2 of the last output as well.
+NPVP_HD int conv3x3s2_src(int o, int tap, int extent) {
+  const int s = 2 * o + tap - 1;
+  return s >= 0 && s < extent ? s : -1;
+}
+
+// The plan of a launch: output tiles of bm rows (output pixels, M = F H W of them, F Ho Wo at stride 2) x bn columns (output channels),
+// one workgroup per tile, block b -> tile (b / tiles_n, b % tiles_n): the tiles of one row block are neighbours in launch order and share their A rows in L2.
 //   variant 1: 128 x 128 tiles (C_out % 128 == 0), variant 2: 128 x 64 tiles (C_out % 64 == 0 only); 256 threads either way.
 struct Conv3x3Plan { int variant, bm, bn, tiles_m, tiles_n, grid; };
 

@@ -17,6 +17,10 @@ checkpoints load.  `learn_3d=True` adds the temporal half of every Factorized3DC
            (every spatial_conv, both convolutions of every ResnetBlock) through ONE f16x3 implicit-GEMM launch each
            (`ops.conv3x3_packed`, csrc/conv3x3.hip: padding as index math, bias + activation + skip in its epilogue); the default
            `"stock"` leaves them on MIOpen + `npvp_bias_act`.
+           `down3x3="hip"` (opt-in, inference only, independent of the other two switches) sends the encoder's 3 x 3 stride-2
+           downsampling convolutions (`block1`, every `block{i}_conv`; C_in a multiple of 32, C_out of 64) through the stride-2 form
+           of the same kernel (`ops.conv3x3s2_packed`); their output carries its amax slot, so the routed `spatial_conv` behind it
+           runs no `npvp_amax` pass.  The default `"stock"` leaves them on MIOpen + `npvp_bias_act`.
 """
 import functools
 import types
@@ -60,6 +64,7 @@ class FoldedConvAct(nn.Module):
         self.act = 0 if act is None else _ACT_CODE[type(act)]
         self.pad = pad
         self.conv3x3_pad = None          # "zero" / "reflect" once routed to the 3 x 3 kernel (fuse_frozen_autoencoder(conv3x3="hip"))
+        self.down3x3 = False             # True once routed to its stride-2 form (fuse_frozen_autoencoder(down3x3="hip"))
 
     def route_conv3x3(self, pad):
         """send this convolution through ops.conv3x3_packed with the padding rule `pad`; the weight planes and the weight's amax slot
@@ -78,10 +83,27 @@ class FoldedConvAct(nn.Module):
             self._npvp_planes, self._npvp_w_amax = ops.conv3x3_planes(self.weight.to(x.device))
         return ops.conv3x3_packed(x, self._npvp_planes, self._npvp_w_amax, self.bias, self.conv3x3_pad, self.act, residual)
 
+    def route_down3x3(self):
+        """send this stride-2 convolution through ops.conv3x3s2_packed; planes and amax slot as route_conv3x3 keeps them"""
+        self.down3x3 = True
+        planes, w_amax = ops.conv3x3s2_planes(self.weight) if self.weight.is_cuda else (None, None)
+        self.register_buffer("_npvp_planes", planes, persistent=False)
+        self.register_buffer("_npvp_w_amax", w_amax, persistent=False)
+
+    def _down3x3(self, x, residual):
+        if torch.is_grad_enabled() and (x.requires_grad or (residual is not None and residual.requires_grad)):
+            raise NotImplementedError('down3x3="hip" (to_device_layout / fuse_frozen_autoencoder) is inference-only: the input of this '
+                                      'convolution requires grad; fuse the pair with down3x3="stock" to differentiate through it')
+        if self._npvp_planes is None or self._npvp_planes.device != x.device:
+            self._npvp_planes, self._npvp_w_amax = ops.conv3x3s2_planes(self.weight.to(x.device))
+        return ops.conv3x3s2_packed(x, self._npvp_planes, self._npvp_w_amax, self.bias, self.act, residual)
+
     def forward(self, x, residual=None):
         # routed: channels-last frames only (anything else keeps the stock forward below: no silent copy)
         if self.conv3x3_pad is not None and _channels_last_only(x) and (residual is None or _channels_last_only(residual)):
             return self._conv3x3(x, residual)
+        if self.down3x3 and _channels_last_only(x) and (residual is None or _channels_last_only(residual)):
+            return self._down3x3(x, residual)
         if self.pad is not None:
             x = self.pad(x)
         if self.transposed:
@@ -153,6 +175,34 @@ def _route_conv3x3(folded):
             m.route_conv3x3(pad)
 
 
+DOWN3X3_ROUTES = ("stock", "hip")
+
+
+def _check_down3x3(down3x3):
+    if down3x3 not in DOWN3X3_ROUTES:
+        raise ValueError(f"down3x3={down3x3!r}: the route of the frozen encoder's stride-2 3 x 3 convolutions is one of {DOWN3X3_ROUTES}")
+
+
+def _down3x3_takes_hip(m):
+    """whether the stride-2 form of the 3 x 3 kernel runs this FoldedConvAct: a 3 x 3, stride-(2, 2), undilated, not transposed
+    convolution, zero-padded by 1 with no pad module, C_in a multiple of 32 and C_out of 64"""
+    if m.transposed or tuple(m.weight.shape[2:]) != (3, 3) or tuple(m.stride) != (2, 2) or tuple(m.dilation) != (1, 1):
+        return False
+    if m.pad is not None or tuple(m.padding) != (1, 1):
+        return False
+    # every (C_in, C_out) of the rule stays on the kernel: at the seven (C_in -> C_out, grid) pairs of the c1- and c4-size encoders
+    # (64 -> 128 at 64 x 64 ... 256 -> 512 at 16 x 16; 32 -> 64 at 128 x 128 ... 256 -> 512 at 16 x 16) both hip timings, each with its
+    # npvp_amax pass over the input, beat both MIOpen + npvp_bias_act timings (the "conv" lines of profiles/frozen_down3x3_bench.txt);
+    # a pair that loses there would be named and excluded here
+    return ops.conv3x3s2_takes(m.weight.shape[1], m.weight.shape[0])
+
+
+def _route_down3x3(folded):
+    for m in folded:
+        if _down3x3_takes_hip(m):
+            m.route_down3x3()
+
+
 def _zero_or_bias(lin):
     return lin.bias if lin.bias is not None else torch.zeros(lin.out_features, dtype=lin.weight.dtype, device=lin.weight.device)
 
@@ -173,7 +223,7 @@ def _attn2d_takes_hip(a):
             and a.out_proj.bias is not None)
 
 
-def fuse_frozen_autoencoder(enc, dec, attn2d="stock", conv3x3="stock"):
+def fuse_frozen_autoencoder(enc, dec, attn2d="stock", conv3x3="stock", down3x3="stock"):
     """In-place module surgery on an eval-mode pair that already holds its final weights; freezes its parameters (do it after load_state_dict:
     the folded modules no longer carry the reference's state-dict keys).  Returns (enc, dec).
     attn2d: "stock" (default) leaves every NonLocalAttenion2D of the encoder on its own forward (PyTorch: the (frames, H*W, H*W/4) scores
@@ -182,9 +232,13 @@ def fuse_frozen_autoencoder(enc, dec, attn2d="stock", conv3x3="stock"):
     conv3x3: "stock" (default) leaves every convolution on MIOpen + npvp_bias_act; "hip" sends the ENCODER's FoldedConvActs that
     `_conv3x3_takes_hip` accepts - every spatial_conv and ResnetBlock convolution with 64-multiple channels - through
     ops.conv3x3_packed (inference only).  The 7 x 7 and stride-2 convolutions, ReplicationPad2d blocks and the decoder stay stock.
-    Any other value is refused."""
+    Any other value is refused.
+    down3x3: "stock" (default) leaves the stride-2 convolutions on MIOpen + npvp_bias_act; "hip" sends the ENCODER's FoldedConvActs
+    that `_down3x3_takes_hip` accepts - block1 and every block{i}_conv - through ops.conv3x3s2_packed (inference only).  The decoder's
+    transposed convolutions stay stock.  Any other value is refused.  The three switches are independent."""
     _check_attn2d(attn2d)
     _check_conv3x3(conv3x3)
+    _check_down3x3(down3x3)
     for m in (enc, dec):
         assert not m.training, "fuse_frozen_autoencoder: eval mode only (BatchNorm must use its running statistics)"
         for q in m.parameters():
@@ -218,6 +272,8 @@ def fuse_frozen_autoencoder(enc, dec, attn2d="stock", conv3x3="stock"):
                 mod.conv_block = _fold_sequential(mod.conv_block)
         if conv3x3 == "hip":
             _route_conv3x3([m for m in enc.modules() if isinstance(m, FoldedConvAct)])
+        if down3x3 == "hip":
+            _route_down3x3([m for m in enc.modules() if isinstance(m, FoldedConvAct)])
         dec.model = _fold_sequential(dec.model)
     return enc, dec
 
@@ -526,11 +582,12 @@ def build_frozen_autoencoder(AE, img_channels):
     return enc, dec
 
 
-def to_device_layout(enc, dec, device, attn2d="stock", conv3x3="stock"):
+def to_device_layout(enc, dec, device, attn2d="stock", conv3x3="stock", down3x3="stock"):
     """Move the frozen pair to an MI355X.  The ENCODER runs in torch.channels_last (MIOpen's NHWC kernels: 27.5 -> 24.8 ms
     for 640 frames of 64x64, and its (N*T,H,W,C) output is the predictor's canonical layout, so the layout transpose at
     the predictor's entry disappears); the decoder stays NCHW (NHWC measured slower: 9.0 -> 11.2 ms fwd + input-grad)."""
     _check_attn2d(attn2d)
     _check_conv3x3(conv3x3)
+    _check_down3x3(down3x3)
     enc, dec = enc.to(device).to(memory_format=torch.channels_last), dec.to(device)
-    return fuse_frozen_autoencoder(enc.eval(), dec.eval(), attn2d=attn2d, conv3x3=conv3x3)
+    return fuse_frozen_autoencoder(enc.eval(), dec.eval(), attn2d=attn2d, conv3x3=conv3x3, down3x3=down3x3)

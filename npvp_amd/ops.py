@@ -2470,6 +2470,57 @@ def conv3x3_packed(x, planes, w_amax, bias, pad="zero", act=0, residual=None, wa
     return tag_amax(y.permute(0, 3, 1, 2), y_slot)
 
 
+def conv3x3s2_takes(C_in, C_out):
+    """channel counts the stride-2 form of the kernel is built for (C_in = 32: block1 of the ngf = 32 encoders)"""
+    return C_in > 0 and C_out > 0 and C_in % 32 == 0 and C_out % 64 == 0
+
+
+def conv3x3s2_planes(w):
+    """conv3x3_planes under the stride-2 channel rule (conv3x3s2_takes): (planes, w_amax) of a frozen weight w [C_out][C_in][3][3] in
+    the same layout, for conv3x3s2_packed"""
+    _chk(w)
+    if w.dim() != 4 or tuple(w.shape[2:]) != (3, 3) or not conv3x3s2_takes(w.shape[1], w.shape[0]):
+        raise RuntimeError("conv3x3s2_planes: w must be [C_out][C_in][3][3] with C_in a multiple of 32 and C_out a multiple of 64")
+    w = w.detach().contiguous()
+    C_out, C_in = w.shape[:2]
+    planes = torch.empty(lib().npvp_conv3x3s2_planes_bytes(C_in, C_out) // 2, dtype=torch.float16, device=w.device)
+    slot = torch.zeros(AmaxSlot.FLOATS, device=w.device)
+    check(lib().npvp_conv3x3s2_planes(_ptr(w), C_in, C_out, _ptr(planes), _ptr(slot), _stream()), "npvp_conv3x3s2_planes")
+    return planes, slot
+
+
+def conv3x3s2_packed(x, planes, w_amax, bias, act=0, residual=None, want_amax=True):
+    """y = act(conv3x3(x, stride 2, zero padding 1) + bias[c]) (+ residual) of a frozen downsampling convolution on channels-last frames
+    x (F, C_in, H, W) -> (F, C_out, (H + 1) // 2, (W + 1) // 2), one npvp_conv3x3s2_f16 launch (the stride-2 form of conv3x3_packed's
+    kernel).  planes / w_amax: conv3x3s2_planes of the folded weight.  The amax slot of x is its producer's or one npvp_amax pass
+    (amax_of); want_amax attaches the slot of y to the result and to its NCHW view, so a following conv3x3_packed needs no pass.
+    Forward only: an input that requires grad is refused.  x and residual must be channels-last (no silent copy)."""
+    ts = [t for t in (x, bias, residual) if t is not None]
+    if torch.is_grad_enabled() and any(t.requires_grad for t in ts):
+        raise NotImplementedError("conv3x3s2_packed: forward only (the frozen encoder's convolutions); an input requires grad")
+    _chk(x, w_amax, bias, residual)
+    if x.dim() != 4:
+        raise RuntimeError("conv3x3s2_packed: x must be (F, C_in, H, W)")
+    Fr, C_in, H, W = x.shape
+    C_out = bias.shape[0]
+    Ho, Wo = (H + 1) // 2, (W + 1) // 2
+    if planes.numel() != 2 * 9 * C_in * C_out or not planes.is_cuda or planes.dtype != torch.float16:
+        raise RuntimeError("conv3x3s2_packed: planes do not belong to a [C_out][C_in][3][3] weight of these channel counts")
+    x2 = x.permute(0, 2, 3, 1)
+    if not x2.is_contiguous():
+        raise RuntimeError("conv3x3s2_packed: x must be channels-last")
+    y = torch.empty((Fr, Ho, Wo, C_out), device=x.device, dtype=torch.float32)
+    if residual is not None:
+        if residual.shape != (Fr, C_out, Ho, Wo) or not residual.permute(0, 2, 3, 1).is_contiguous():
+            raise RuntimeError("conv3x3s2_packed: residual must be channels-last frames of the output's shape")
+    x_slot = amax_of(x2.reshape(Fr * H * W, C_in))                  # (a view of x: finds the slot its producer attached to x)
+    y_slot = AmaxSlot.new(x.device) if want_amax else None
+    check(lib().npvp_conv3x3s2_f16(_ptr(x), _ptr(planes), _ptr(_c(bias)), _ptr(residual), _ptr(y), Fr, H, W, C_in, C_out, act, _ptr(x_slot),
+                                   _ptr(w_amax), _ptr(y_slot), None, 0, _stream()), "npvp_conv3x3s2_f16")
+    tag_amax(y, y_slot)
+    return tag_amax(y.permute(0, 3, 1, 2), y_slot)
+
+
 # --------------------------------------------------------------------------- Stage-1 autoencoder training (csrc/ae_train.hip)
 class _BnActTrain(_Function):
     """BatchNorm2d (batch statistics in training, running statistics in eval) -> act (0 none, 1 ReLU) [-> + residual] as one
