@@ -653,6 +653,44 @@ int npvp_conv3x3s2_tile(int F, int H, int W, int C_in, int C_out, int block, int
  * input pixels, or -1 for a tap that contributes 0 - the __host__ __device__ function the kernel calls.  -2: bad argument. */
 int npvp_conv3x3s2_src(int o, int tap, int extent);
 
+/* ---- The transposed 3 x 3 convolutions of the frozen decoder (opt-in, to_device_layout(..., up3x3="hip")): every
+ * ConvTranspose2d(kernel 3, stride 2, padding 1, output_padding 1), BatchNorm folded, ReLU (ref/models/ResNetAutoEncoder.py:148-204),
+ * a third form of the same kernel (arithmetic, tiles, LDS stages and epilogue of npvp_conv3x3_f16), forward:
+ *   y[f,oh,ow,co] = act( sum_{ci, (s, k): oh = 2 sh - 1 + kh, ow = 2 sw - 1 + kw} x[f,sh,sw,ci] * w[ci,co,kh,kw] + bias[co] )
+ * x [F][H][W][C_in] -> y [F][2H][2W][C_out], fp32, channels-last; no residual.  The output splits by parity: pixel (2 i + a, 2 j + b)
+ * belongs to class (a, b) and input-grid position (i, j); per axis parity 0 has one tap (kernel index 1, source i), parity 1 two
+ * (kernel index 2 at source i; kernel index 0 at source i + 1, nothing at the far edge) - 1, 2, 2 and 4 taps per class, 9 per 4 outputs,
+ * no multiplication by an inserted zero.  ONE launch: a workgroup owns a 128-row x 128- or 64-column tile of M = F H W input-grid rows
+ * of ONE class, K = taps * C_in; the 4-tap class's workgroups come first in launch order.  C_in % 32 == 0, C_out % 64 == 0;
+ * F, H, W >= 1; F * 2H * 2W < 2^31.  Every output element is written exactly once (no split-K, no atomics on y, no memset); two runs
+ * give the same bits.  The input gradient of this convolution is npvp_conv3x3s2_f16 on the same weight memory read as a Conv2d
+ * weight [out = C_in][in = C_out][3][3] (planes from npvp_conv3x3s2_planes(w, C_out, C_in, ...)). */
+/* taps of an axis at output parity 0 / 1 (1 / 2); -2: bad argument */
+int npvp_convt3x3s2_ntaps(int parity);
+/* kernel index (0, 1, 2) of tap t (0 <= t < ntaps) at that parity; -2: bad argument */
+int npvp_convt3x3s2_tap(int parity, int t);
+/* source coordinate of tap t at input-grid position i (0 <= i < extent) and that parity, or -1 for a tap that contributes 0 - the
+ * __host__ __device__ functions the kernel calls (csrc/conv3x3_index.h).  -2: bad argument. */
+int npvp_convt3x3s2_src(int i, int parity, int t, int extent);
+/* bytes of the weight planes, or -1 for channel counts outside the rule above */
+long long npvp_convt3x3s2_planes_bytes(int C_in, int C_out);
+/* w [C_in][C_out][3][3] (the ConvTranspose2d layout, contiguous) -> planes[2 terms][9 C_in / 8][C_out][8 over k],
+ * k = (kh * 3 + kw) * C_in + ci (kernel index unflipped): npvp_conv3x3_planes' layout and arithmetic; a class reads the K-steps of its
+ * taps.  w_amax is zeroed and recomputed here.  Once per frozen weight. */
+int npvp_convt3x3s2_planes(const float* w, int C_in, int C_out, void* planes, float* w_amax, npvp_stream_t stream);
+/* The convolution.  H, W: the INPUT grid.  planes / w_amax: from npvp_convt3x3s2_planes; x_amax: the slot that bounds |x|; y_amax
+ * (nullable): receives the bound of the values stored to y.  act as npvp_bias_act.  workspace / ws_bytes: reserved (NULL, 0).
+ * x, y and planes 16-byte aligned; y must not overlap x. */
+int npvp_convt3x3s2_f16(const float* x, const void* planes, const float* bias, float* y, int F, int H, int W, int C_in, int C_out,
+                        int act, const float* x_amax, const float* w_amax, float* y_amax, void* workspace, long long ws_bytes,
+                        npvp_stream_t stream);
+/* The plan npvp_convt3x3s2_f16 launches: out8 = {tile variant, rows per tile, columns per tile, row tiles per class, column tiles,
+ * workgroups of the launch (4 classes x row tiles x column tiles), 2H, 2W}.  Returns 0, or -1 for a refused shape.  Pure function. */
+int npvp_convt3x3s2_route(int F, int H, int W, int C_in, int C_out, int* out8);
+/* out6 = {a, b, m0, m1, n0, n1}: the class (row parity a, column parity b), the rows [m0, m1) of [F H W] input-grid positions and
+ * the columns [n0, n1) of C_out that workgroup `block` stores - the function the kernel itself calls.  Pure function. */
+int npvp_convt3x3s2_tile(int F, int H, int W, int C_in, int C_out, int block, int* out6);
+
 /* ---- Stage-1 autoencoder training (csrc/ae_train.hip): LitAE.training_step / shared_step (ref/models/ResNetAutoEncoder.py:13-49)
  * through ResnetEncoder / ResnetDecoder (ref :51-204) and NonLocalAttenion2D (ref/models/submodules.py:98-176); the convolutions
  * stay MIOpen's.  Every entry point is deterministic (fixed-order sums, no atomics) and needs no zero-filled buffer.

@@ -1,5 +1,5 @@
 // Index math of the 3 x 3 implicit-GEMM convolution (conv3x3.hip), as __host__ __device__ functions: the kernel and the launcher call
-// them, and the C ABI exports them unchanged (npvp_conv3x3_src, npvp_conv3x3_route, npvp_conv3x3_tile, npvp_conv3x3s2_*), so the part of the kernel that
+// them, and the C ABI exports them unchanged (npvp_conv3x3_src, npvp_conv3x3_route, npvp_conv3x3_tile, npvp_conv3x3s2_*, npvp_convt3x3s2_*), so the part of the kernel that
 // can go wrong silently - which pixel a tap reads, which outputs a workgroup owns - is tested on the host.
 #pragma once
 
@@ -54,6 +54,30 @@ NPVP_HD void conv3x3_tile(const Conv3x3Plan& p, int block, long long M, int& m0,
   m1 = (long long)m0 + p.bm < M ? m0 + p.bm : (int)M;
   n0 = tn * p.bn;
   n1 = n0 + p.bn;
+}
+
+// ---- The transposed 3 x 3 convolution with stride 2, padding 1, output_padding 1 (the decoder's upsampling): H x W -> 2H x 2W.
+// Per axis o = 2 s - 1 + k (s the source coordinate, k the kernel index, unflipped), so the output splits by parity: output coordinate
+// 2 i + parity belongs to input-grid position i, and
+//   parity 0 has one tap:  kernel index 1, source i;
+//   parity 1 has two taps: t = 0: kernel index 2, source i;  t = 1: kernel index 0, source i + 1, or -1 (contributes 0) at the far edge.
+// A pixel class (a, b) = (row parity, column parity) has ntaps(a) * ntaps(b) = 1, 2, 2 or 4 taps: 9 taps per 4 outputs.
+NPVP_HD int convt3x3s2_ntaps(int parity) { return parity ? 2 : 1; }
+NPVP_HD int convt3x3s2_tap(int parity, int t) { return parity ? (t ? 0 : 2) : 1; }
+NPVP_HD int convt3x3s2_src(int i, int parity, int t, int extent) {
+  if (parity && t) return i + 1 < extent ? i + 1 : -1;
+  return i;
+}
+
+// The plan of ONE launch per transposed convolution: conv3x3_plan's tiles over M = F H W input-grid rows, once per pixel class; block b
+// -> class 3 - b / p.grid (the 4-tap class (1, 1) first: the longest workgroups start first, the 1-tap class last), tile b % p.grid of
+// that class.  4 * p.grid workgroups.  cls = 2 a + b.
+NPVP_HD int convt3x3s2_grid(const Conv3x3Plan& p) { return 4 * p.grid; }
+
+NPVP_HD void convt3x3s2_tile(const Conv3x3Plan& p, int block, long long M, int& cls, int& m0, int& m1, int& n0, int& n1) {
+  const int q = block / p.grid;
+  cls = 3 - q;
+  conv3x3_tile(p, block - q * p.grid, M, m0, m1, n0, n1);
 }
 
 }  // namespace npvp

@@ -21,6 +21,11 @@ checkpoints load.  `learn_3d=True` adds the temporal half of every Factorized3DC
            downsampling convolutions (`block1`, every `block{i}_conv`; C_in a multiple of 32, C_out of 64) through the stride-2 form
            of the same kernel (`ops.conv3x3s2_packed`); their output carries its amax slot, so the routed `spatial_conv` behind it
            runs no `npvp_amax` pass.  The default `"stock"` leaves them on MIOpen + `npvp_bias_act`.
+           `up3x3="hip"` (opt-in, independent of the other three switches, DIFFERENTIABLE w.r.t. its input: the decoder sits inside
+           autograd in Stage 2) sends the decoder's ConvTranspose2d(3, stride 2, padding 1, output_padding 1) groups with 64-multiple
+           channels through the transposed form of the same kernel (`ops.convt3x3s2_packed`: one launch per convolution, 9 taps per
+           4 outputs; its input gradient is the stride-2 kernel of `down3x3`).  The routed decoder copies its NCHW input frames to
+           channels-last once, and copies back to NCHW once in front of its stock remainder (`UP3X3_TAIL`).
 """
 import functools
 import types
@@ -65,6 +70,7 @@ class FoldedConvAct(nn.Module):
         self.pad = pad
         self.conv3x3_pad = None          # "zero" / "reflect" once routed to the 3 x 3 kernel (fuse_frozen_autoencoder(conv3x3="hip"))
         self.down3x3 = False             # True once routed to its stride-2 form (fuse_frozen_autoencoder(down3x3="hip"))
+        self.up3x3 = False               # True once routed to its transposed form (fuse_frozen_autoencoder(up3x3="hip"))
 
     def route_conv3x3(self, pad):
         """send this convolution through ops.conv3x3_packed with the padding rule `pad`; the weight planes and the weight's amax slot
@@ -98,8 +104,28 @@ class FoldedConvAct(nn.Module):
             self._npvp_planes, self._npvp_w_amax = ops.conv3x3s2_planes(self.weight.to(x.device))
         return ops.conv3x3s2_packed(x, self._npvp_planes, self._npvp_w_amax, self.bias, self.act, residual)
 
+    _UP3X3_BUFFERS = ("_npvp_planes", "_npvp_w_amax", "_npvp_bwd_planes", "_npvp_bwd_w_amax", "_npvp_zero_bias")
+
+    def route_up3x3(self):
+        """send this transposed convolution through ops.convt3x3s2_packed (differentiable w.r.t. its input); the forward planes, the
+        input gradient's planes, their amax slots and the gradient launch's zero bias are non-persistent buffers, built as
+        route_conv3x3 builds its own"""
+        self.up3x3 = True
+        planes = ops.convt3x3s2_planes(self.weight) if self.weight.is_cuda else (None,) * len(self._UP3X3_BUFFERS)
+        for name, t in zip(self._UP3X3_BUFFERS, planes):
+            self.register_buffer(name, t, persistent=False)
+
+    def _up3x3(self, x):
+        if self._npvp_planes is None or self._npvp_planes.device != x.device:
+            for name, t in zip(self._UP3X3_BUFFERS, ops.convt3x3s2_planes(self.weight.to(x.device))):
+                setattr(self, name, t)
+        planes = ops.ConvT3x3Planes(*(getattr(self, name) for name in self._UP3X3_BUFFERS))
+        return ops.convt3x3s2_packed(x, planes, self.bias, self.act)
+
     def forward(self, x, residual=None):
         # routed: channels-last frames only (anything else keeps the stock forward below: no silent copy)
+        if self.up3x3 and residual is None and _channels_last_only(x):
+            return self._up3x3(x)
         if self.conv3x3_pad is not None and _channels_last_only(x) and (residual is None or _channels_last_only(residual)):
             return self._conv3x3(x, residual)
         if self.down3x3 and _channels_last_only(x) and (residual is None or _channels_last_only(residual)):
@@ -203,6 +229,39 @@ def _route_down3x3(folded):
             m.route_down3x3()
 
 
+UP3X3_ROUTES = ("stock", "hip")
+# where the stock remainder of a routed decoder runs (the 7 x 7 tail, and in front of it the 64 -> 32 transposed convolution of an
+# ngf = 32 decoder): on the channels-last tensor the routed convolutions hand over ("nhwc"), or with NCHW weights behind one copy back to
+# NCHW ("nchw"); whichever measured faster for decoder forward + input gradient (profiles/frozen_up3x3_bench.txt).  Read at fuse time.
+UP3X3_TAIL = "nchw"
+
+
+def _check_up3x3(up3x3):
+    if up3x3 not in UP3X3_ROUTES:
+        raise ValueError(f"up3x3={up3x3!r}: the route of the frozen decoder's transposed 3 x 3 convolutions is one of {UP3X3_ROUTES}")
+
+
+def _up3x3_takes_hip(m):
+    """whether the transposed form of the 3 x 3 kernel runs this FoldedConvAct: a transposed 3 x 3 convolution, stride (2, 2), padding
+    (1, 1), output_padding (1, 1), undilated, no pad module, C_in and C_out multiples of 64 (the forward needs C_out, its input
+    gradient - the stride-2 kernel with the channels exchanged - C_in)"""
+    if not m.transposed or tuple(m.weight.shape[2:]) != (3, 3) or tuple(m.stride) != (2, 2) or tuple(m.dilation) != (1, 1):
+        return False
+    if m.pad is not None or tuple(m.padding) != (1, 1) or tuple(m.output_padding) != (1, 1):
+        return False
+    # every (C_in, C_out) of the rule stays on the kernel: at the three (C_in -> C_out, grid) pairs of the decoders - 512 -> 256 at 8 x 8,
+    # 256 -> 128 at 16 x 16, 128 -> 64 at 32 x 32, at 320, 1792 and 128 frames - both hip timings beat both MIOpen + npvp_bias_act timings,
+    # forward and forward + input gradient, each hip call with an npvp_amax pass over its input (the "conv" lines of
+    # profiles/frozen_up3x3_bench.txt); a pair that loses there would be named and excluded here
+    return ops.convt3x3s2_takes(m.weight.shape[0], m.weight.shape[1])
+
+
+def _route_up3x3(folded):
+    for m in folded:
+        if _up3x3_takes_hip(m):
+            m.route_up3x3()
+
+
 def _zero_or_bias(lin):
     return lin.bias if lin.bias is not None else torch.zeros(lin.out_features, dtype=lin.weight.dtype, device=lin.weight.device)
 
@@ -223,7 +282,7 @@ def _attn2d_takes_hip(a):
             and a.out_proj.bias is not None)
 
 
-def fuse_frozen_autoencoder(enc, dec, attn2d="stock", conv3x3="stock", down3x3="stock"):
+def fuse_frozen_autoencoder(enc, dec, attn2d="stock", conv3x3="stock", down3x3="stock", up3x3="stock"):
     """In-place module surgery on an eval-mode pair that already holds its final weights; freezes its parameters (do it after load_state_dict:
     the folded modules no longer carry the reference's state-dict keys).  Returns (enc, dec).
     attn2d: "stock" (default) leaves every NonLocalAttenion2D of the encoder on its own forward (PyTorch: the (frames, H*W, H*W/4) scores
@@ -235,10 +294,17 @@ def fuse_frozen_autoencoder(enc, dec, attn2d="stock", conv3x3="stock", down3x3="
     Any other value is refused.
     down3x3: "stock" (default) leaves the stride-2 convolutions on MIOpen + npvp_bias_act; "hip" sends the ENCODER's FoldedConvActs
     that `_down3x3_takes_hip` accepts - block1 and every block{i}_conv - through ops.conv3x3s2_packed (inference only).  The decoder's
-    transposed convolutions stay stock.  Any other value is refused.  The three switches are independent."""
+    transposed convolutions stay stock.  Any other value is refused.
+    up3x3: "stock" (default) leaves the DECODER's transposed convolutions on MIOpen + npvp_bias_act; "hip" sends those
+    `_up3x3_takes_hip` accepts - ConvTranspose2d(3, stride 2, padding 1, output_padding 1) with 64-multiple channels: all of an
+    ngf = 64 decoder, all but the last (64 -> 32) of an ngf = 32 one - through ops.convt3x3s2_packed, which is differentiable w.r.t.
+    its input (the decoder sits inside autograd in Stage 2), and makes the decoder convert its input frames to channels-last at its
+    entry.  The 7 x 7 tail stays stock, with NCHW weights behind one copy back to NCHW (`UP3X3_TAIL`).  Any other value is refused.
+    The four switches are independent."""
     _check_attn2d(attn2d)
     _check_conv3x3(conv3x3)
     _check_down3x3(down3x3)
+    _check_up3x3(up3x3)
     for m in (enc, dec):
         assert not m.training, "fuse_frozen_autoencoder: eval mode only (BatchNorm must use its running statistics)"
         for q in m.parameters():
@@ -275,6 +341,13 @@ def fuse_frozen_autoencoder(enc, dec, attn2d="stock", conv3x3="stock", down3x3="
         if down3x3 == "hip":
             _route_down3x3([m for m in enc.modules() if isinstance(m, FoldedConvAct)])
         dec.model = _fold_sequential(dec.model)
+        if up3x3 == "hip":
+            _route_up3x3(list(dec.model))
+            if UP3X3_TAIL == "nchw":
+                for m in dec.model:
+                    if not m.up3x3:
+                        m.weight = m.weight.contiguous()
+            dec.up3x3 = True
     return enc, dec
 
 
@@ -562,9 +635,20 @@ class ResnetDecoder(nn.Module):
             raise ValueError("Unsupported output layer")
         self.model = nn.Sequential(*model)
 
+    up3x3 = False          # True on a fused decoder whose transposed convolutions are routed (fuse_frozen_autoencoder(up3x3="hip"))
+
     def forward(self, x):
         N, T = x.shape[:2]
-        y = self.model(x.flatten(0, 1))
+        y = x.flatten(0, 1)
+        if self.up3x3:
+            # the routed kernels are channels-last and the predictor hands out NCHW: ONE explicit, differentiable copy at the entry
+            y = y.contiguous(memory_format=torch.channels_last)
+            for m in self.model:
+                if not m.up3x3 and m.weight.is_contiguous() and not y.is_contiguous():
+                    y = y.contiguous()                   # the stock remainder runs in its weights' layout (UP3X3_TAIL): one copy back to NCHW
+                y = m(y)
+        else:
+            y = self.model(y)
         return y.reshape(N, T, *y.shape[1:])
 
 
@@ -582,12 +666,17 @@ def build_frozen_autoencoder(AE, img_channels):
     return enc, dec
 
 
-def to_device_layout(enc, dec, device, attn2d="stock", conv3x3="stock", down3x3="stock"):
+def to_device_layout(enc, dec, device, attn2d="stock", conv3x3="stock", down3x3="stock", up3x3="stock"):
     """Move the frozen pair to an MI355X.  The ENCODER runs in torch.channels_last (MIOpen's NHWC kernels: 27.5 -> 24.8 ms
     for 640 frames of 64x64, and its (N*T,H,W,C) output is the predictor's canonical layout, so the layout transpose at
-    the predictor's entry disappears); the decoder stays NCHW (NHWC measured slower: 9.0 -> 11.2 ms fwd + input-grad)."""
+    the predictor's entry disappears); the decoder stays NCHW (NHWC measured slower: 9.0 -> 11.2 ms fwd + input-grad on MIOpen)
+    unless up3x3="hip" routes its transposed convolutions to the channels-last kernel: then it is moved to torch.channels_last too,
+    and fuse_frozen_autoencoder gives the stock remainder (the 7 x 7 tail) its NCHW weights back (`UP3X3_TAIL`: measured faster)."""
     _check_attn2d(attn2d)
     _check_conv3x3(conv3x3)
     _check_down3x3(down3x3)
+    _check_up3x3(up3x3)
     enc, dec = enc.to(device).to(memory_format=torch.channels_last), dec.to(device)
-    return fuse_frozen_autoencoder(enc.eval(), dec.eval(), attn2d=attn2d, conv3x3=conv3x3, down3x3=down3x3)
+    if up3x3 == "hip":
+        dec = dec.to(memory_format=torch.channels_last)
+    return fuse_frozen_autoencoder(enc.eval(), dec.eval(), attn2d=attn2d, conv3x3=conv3x3, down3x3=down3x3, up3x3=up3x3)

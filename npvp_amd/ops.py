@@ -2521,6 +2521,97 @@ def conv3x3s2_packed(x, planes, w_amax, bias, act=0, residual=None, want_amax=Tr
     return tag_amax(y.permute(0, 3, 1, 2), y_slot)
 
 
+# --------------------------------------------------------------------------- frozen decoder: transposed 3 x 3 convolutions (csrc/conv3x3.hip)
+def convt3x3s2_takes(C_in, C_out):
+    """channel counts of a ConvTranspose2d(3, stride 2, padding 1, output_padding 1) the route runs: the forward kernel needs
+    C_out % 64 == 0, the input gradient is npvp_conv3x3s2_f16 with in = C_out, out = C_in and needs C_in % 64 == 0"""
+    return C_in > 0 and C_out > 0 and C_in % 64 == 0 and C_out % 64 == 0
+
+
+ConvT3x3Planes = namedtuple("ConvT3x3Planes", "fwd w_amax bwd bwd_w_amax zero_bias")
+
+
+def convt3x3s2_planes(w):
+    """the planes of a frozen ConvTranspose2d weight w [C_in][C_out][3][3] for convt3x3s2_packed: (fwd, w_amax) for the forward kernel
+    (npvp_convt3x3s2_planes), (bwd, bwd_w_amax) for the input gradient - npvp_conv3x3s2_planes on the SAME weight memory read as a
+    Conv2d weight [out = C_in][in = C_out][3][3] - and the zero bias of C_in floats that launch takes"""
+    _chk(w)
+    if w.dim() != 4 or tuple(w.shape[2:]) != (3, 3) or not convt3x3s2_takes(w.shape[0], w.shape[1]):
+        raise RuntimeError("convt3x3s2_planes: w must be [C_in][C_out][3][3] with channel counts that are multiples of 64")
+    w = w.detach().contiguous()
+    C_in, C_out = w.shape[:2]
+    L = lib()
+    fwd = torch.empty(L.npvp_convt3x3s2_planes_bytes(C_in, C_out) // 2, dtype=torch.float16, device=w.device)
+    slot = torch.zeros(AmaxSlot.FLOATS, device=w.device)
+    check(L.npvp_convt3x3s2_planes(_ptr(w), C_in, C_out, _ptr(fwd), _ptr(slot), _stream()), "npvp_convt3x3s2_planes")
+    bwd = torch.empty(L.npvp_conv3x3s2_planes_bytes(C_out, C_in) // 2, dtype=torch.float16, device=w.device)
+    bslot = torch.zeros(AmaxSlot.FLOATS, device=w.device)
+    check(L.npvp_conv3x3s2_planes(_ptr(w), C_out, C_in, _ptr(bwd), _ptr(bslot), _stream()), "npvp_conv3x3s2_planes")
+    return ConvT3x3Planes(fwd, slot, bwd, bslot, torch.zeros(C_in, device=w.device))
+
+
+class _ConvT3x3S2(_Function):
+    """y = act(conv_transpose3x3(x, stride 2, padding 1, output_padding 1) + bias[c]) of a frozen weight, channels-last.  Gradient
+    w.r.t. x only (the decoder's input-gradient path): dx = conv3x3(act'(y) g, stride 2, padding 1) with the weight read as a Conv2d
+    weight - npvp_act_bwd through the saved OUTPUT, one npvp_amax pass, the existing npvp_conv3x3s2_f16."""
+
+    @staticmethod
+    def forward(ctx, x, bias, act, fwd, w_amax, bwd, bwd_w_amax, zero_bias):
+        remember(ctx)
+        Fr, C_in, H, W = x.shape
+        C_out = bias.shape[0]
+        x2 = x.permute(0, 2, 3, 1)
+        y = torch.empty((Fr, 2 * H, 2 * W, C_out), device=x.device, dtype=torch.float32)
+        x_slot = amax_of(x2.reshape(Fr * H * W, C_in))                  # (a view of x: finds the slot its producer attached to x)
+        y_slot = AmaxSlot.new(x.device)
+        check(lib().npvp_convt3x3s2_f16(_ptr(x), _ptr(fwd), _ptr(bias), _ptr(y), Fr, H, W, C_in, C_out, act, _ptr(x_slot), _ptr(w_amax),
+                                        _ptr(y_slot), None, 0, _stream()), "npvp_convt3x3s2_f16")
+        tag_amax(y, y_slot)                                             # (amax_of looks at a view's base)
+        out = tag_amax(y.permute(0, 3, 1, 2), y_slot)
+        ctx.act, ctx.dims = act, (Fr, C_in, H, W, C_out)
+        if ctx.needs_input_grad[0]:
+            ctx.save_for_backward(out, bwd, bwd_w_amax, zero_bias)
+        return out
+
+    @scoped
+    def backward(ctx, g):
+        y, bwd, bwd_w_amax, zero_bias = ctx.saved_tensors
+        Fr, C_in, H, W, C_out = ctx.dims
+        g = g.contiguous(memory_format=torch.channels_last)
+        if ctx.act != 0:
+            dz = torch.empty_like(g)
+            check(lib().npvp_act_bwd(_ptr(g), _ptr(y), _ptr(dz), y.numel(), ctx.act, _stream()), "npvp_act_bwd")
+            g = dz
+        s = AmaxSlot.new(g.device)
+        check(lib().npvp_amax(_ptr(g), Fr * 4 * H * W, C_out, C_out, _ptr(s), _stream()), "npvp_amax")
+        dx = torch.empty((Fr, H, W, C_in), device=g.device, dtype=torch.float32)
+        check(lib().npvp_conv3x3s2_f16(_ptr(g), _ptr(bwd), _ptr(zero_bias), None, _ptr(dx), Fr, 2 * H, 2 * W, C_out, C_in, 0, _ptr(s),
+                                       _ptr(bwd_w_amax), None, None, 0, _stream()), "npvp_conv3x3s2_f16")
+        return dx.permute(0, 3, 1, 2), None, None, None, None, None, None, None
+
+
+def convt3x3s2_packed(x, planes, bias, act=0):
+    """y = act(conv_transpose2d(x, w, stride 2, padding 1, output_padding 1) + bias[c]) of a frozen upsampling convolution on
+    channels-last frames x (F, C_in, H, W) -> (F, C_out, 2H, 2W), one npvp_convt3x3s2_f16 launch (the transposed form of
+    conv3x3_packed's kernel).  planes: convt3x3s2_planes of the folded weight.  The amax slot of x is its producer's or one npvp_amax
+    pass (amax_of); the slot of y is attached to the result and to its NCHW view, so a following convt3x3s2_packed needs no pass.
+    Differentiable w.r.t. x (act_bwd, amax, one npvp_conv3x3s2_f16).  x must be channels-last (no silent copy)."""
+    _chk(x, bias, planes.w_amax, planes.bwd_w_amax, planes.zero_bias)
+    if x.dim() != 4 or bias.dim() != 1:
+        raise RuntimeError("convt3x3s2_packed: x must be (F, C_in, H, W) and bias (C_out,)")
+    C_in, C_out = x.shape[1], bias.shape[0]
+    if not convt3x3s2_takes(C_in, C_out):
+        raise RuntimeError("convt3x3s2_packed: C_in and C_out must be multiples of 64")
+    for p in (planes.fwd, planes.bwd):
+        if p.numel() != 2 * 9 * C_in * C_out or not p.is_cuda or p.dtype != torch.float16:
+            raise RuntimeError("convt3x3s2_packed: planes do not belong to a [C_in][C_out][3][3] weight of these channel counts")
+    if planes.zero_bias.numel() != C_in:
+        raise RuntimeError("convt3x3s2_packed: planes do not belong to a [C_in][C_out][3][3] weight of these channel counts")
+    if not x.permute(0, 2, 3, 1).is_contiguous():
+        raise RuntimeError("convt3x3s2_packed: x must be channels-last")
+    return _ConvT3x3S2.apply(x, _c(bias), act, *planes)
+
+
 # --------------------------------------------------------------------------- Stage-1 autoencoder training (csrc/ae_train.hip)
 class _BnActTrain(_Function):
     """BatchNorm2d (batch statistics in training, running statistics in eval) -> act (0 none, 1 ReLU) [-> + residual] as one
