@@ -691,6 +691,51 @@ int npvp_convt3x3s2_route(int F, int H, int W, int C_in, int C_out, int* out8);
  * the columns [n0, n1) of C_out that workgroup `block` stores - the function the kernel itself calls.  Pure function. */
 int npvp_convt3x3s2_tile(int F, int H, int W, int C_in, int C_out, int block, int* out6);
 
+/* ---- The 7 x 7 tail of the frozen decoder (opt-in, to_device_layout(..., tail7x7="hip"); csrc/conv7x7.hip): ReflectionPad2d(3) ->
+ * Conv2d(C_in, C_out, 7) -> Tanh / Sigmoid (ref/models/ResNetAutoEncoder.py:148-204), forward and input gradient:
+ *   y[f,co,h,w] = act( bias[co] + sum_{ci,kh,kw} x[f, refl_H(h + kh - 3), refl_W(w + kw - 3), ci] * w[co,ci,kh,kw] )
+ * x [F][H][W][C_in] fp32 channels-last -> y [F][C_out][H][W] fp32 NCHW (the layout the decoder returns); no padded copy of x.
+ * The kernel's column index is folded into N: Z[(f,h,w')][(kw,co)] = sum_{kh,ci} x[f, refl_H(h+kh-3), w', ci] w[co,ci,kh,kw] is a
+ * GEMM with M = F H W, N = 7 * 4 = 32 (co padded to 4), K = 7 C_in ordered (kh, ci), and y = act(bias + sum_kw Z[(f,h,refl_W(w+kw-3))][(kw,co)])
+ * is summed inside the workgroup, which owns whole image rows (W <= 128: 128 / W rows of the F * H rows) or one row's segment of 122
+ * columns with a halo of 3 Z columns per side (W > 128).  f16x3 arithmetic as npvp_conv3x3_f16.  C_in % 32 == 0 (up to 4096),
+ * 1 <= C_out <= 4, H, W >= 4, F * H * W < 2^31.  Every element of y is written exactly once (no atomics, no memset); two runs give
+ * the same bits.  The 7 x 7 stem of the ENCODER is not routed. */
+/* source coordinate of tap (0..6) at output coordinate c (0 <= c < extent, extent >= 4) of an axis behind ReflectionPad2d(3) - the
+ * __host__ __device__ function the kernel calls (csrc/conv7x7_index.h).  -2: bad argument. */
+int npvp_tail7x7_src(int c, int tap, int extent);
+/* the adjoint: the output coordinate o with npvp_tail7x7_src(o, tap, extent) == s; which 0: the straight one (o = s + 3 - tap),
+ * which 1: the one mirror image (low edge for tap <= 2, high edge for tap >= 4).  The coordinate, -1 when there is none, -2: bad
+ * argument. */
+int npvp_tail7x7_adj_src(int s, int tap, int extent, int which);
+/* bytes of the weight planes (the forward's and the input gradient's have the same size), or -1 for channel counts outside the rule */
+long long npvp_tail7x7_planes_bytes(int C_in, int C_out);
+/* w [C_out][C_in][7][7] (contiguous) -> forward planes [2 terms][7 C_in / 8][32][8 over k], k = kh * C_in + ci, column kw * 4 + co
+ * (zero columns for co >= C_out and kw = 7).  w_amax is zeroed and recomputed here.  Once per frozen weight. */
+int npvp_tail7x7_planes(const float* w, int C_in, int C_out, void* planes, float* w_amax, npvp_stream_t stream);
+/* the same weight -> the input gradient's planes [2 terms][28][C_in][8 over k], k = kh * 32 + kw * 4 + co, column ci, at the scale
+ * of the SAME slot w_amax (read, not written: call npvp_tail7x7_planes first). */
+int npvp_tail7x7_dgrad_planes(const float* w, int C_in, int C_out, void* planes, const float* w_amax, npvp_stream_t stream);
+/* The forward.  act: 0 none, 2 tanh, 3 sigmoid.  workspace / ws_bytes: reserved (NULL, 0).  x, y and planes 16-byte aligned. */
+int npvp_tail7x7_f16(const float* x, const void* planes, const float* bias, float* y, int F, int H, int W, int C_in, int C_out, int act,
+                     const float* x_amax, const float* w_amax, void* workspace, long long ws_bytes, npvp_stream_t stream);
+/* The plan npvp_tail7x7_f16 launches: out8 = {image rows per tile, column segments per row, output columns per segment, row tiles,
+ * workgroups, Z rows per tile (128), Z columns (32), K-steps}.  Returns 0, or -1 for a refused shape.  Pure function. */
+int npvp_tail7x7_route(int F, int H, int W, int C_in, int C_out, int* out8);
+/* out6 = {r0, r1, w0, w1, z0, z1}: the image rows [r0, r1) of the F * H rows, the output columns [w0, w1) and the Z window [z0, z1)
+ * of workgroup `block` - the function the kernel itself calls.  Pure function. */
+int npvp_tail7x7_tile(int F, int H, int W, int C_in, int C_out, int block, int* out6);
+/* The input gradient: dz [F][C_out][H][W] (g * act'(y), npvp_act_bwd on the planar tensors) -> dx [F][H][W][C_in] channels-last,
+ *   dx[(f,s,t)][ci] = sum_kh sum_{(kw,co)} A[(f,s,t)][kh][(kw,co)] w[co,ci,kh,kw],  A = the sum of dz over npvp_tail7x7_adj_src's
+ * at most 2 x 2 output pixels, taken in fp32 before the fp16 split.  M = F H W rows in tiles of 128, C_in in tiles of 64 (32 when
+ * C_in % 64 != 0), K = 7 steps of 32.  dz_amax: the slot that bounds |dz|.  Written exactly once, no atomics. */
+int npvp_tail7x7_dgrad_f16(const float* dz, const void* planes, float* dx, int F, int H, int W, int C_in, int C_out, const float* dz_amax,
+                           const float* w_amax, void* workspace, long long ws_bytes, npvp_stream_t stream);
+/* out6 = {tile variant (1: 64 columns, 2: 32), rows per tile, columns per tile, row tiles, column tiles, workgroups} */
+int npvp_tail7x7_dgrad_route(int F, int H, int W, int C_in, int C_out, int* out6);
+/* out4 = {m0, m1, n0, n1}: the rows of [F H W] and the columns of C_in that workgroup `block` of the input gradient stores */
+int npvp_tail7x7_dgrad_tile(int F, int H, int W, int C_in, int C_out, int block, int* out4);
+
 /* ---- Stage-1 autoencoder training (csrc/ae_train.hip): LitAE.training_step / shared_step (ref/models/ResNetAutoEncoder.py:13-49)
  * through ResnetEncoder / ResnetDecoder (ref :51-204) and NonLocalAttenion2D (ref/models/submodules.py:98-176); the convolutions
  * stay MIOpen's.  Every entry point is deterministic (fixed-order sums, no atomics) and needs no zero-filled buffer.

@@ -26,6 +26,10 @@ checkpoints load.  `learn_3d=True` adds the temporal half of every Factorized3DC
            channels through the transposed form of the same kernel (`ops.convt3x3s2_packed`: one launch per convolution, 9 taps per
            4 outputs; its input gradient is the stride-2 kernel of `down3x3`).  The routed decoder copies its NCHW input frames to
            channels-last once, and copies back to NCHW once in front of its stock remainder (`UP3X3_TAIL`).
+           `tail7x7="hip"` (opt-in, independent of the other four switches, differentiable w.r.t. its input) sends the decoder's tail -
+           ReflectionPad2d(3), Conv2d(ngf, output_nc, 7), Tanh / Sigmoid - through `ops.tail7x7_packed` (csrc/conv7x7.hip: one launch,
+           padding as index math, bias and activation in the epilogue, channels-last frames in, NCHW frames out; the input gradient is
+           act_bwd, amax and one launch).  Behind `up3x3="hip"` no copy back to NCHW remains.  The encoder's 7 x 7 stem stays stock.
 """
 import functools
 import types
@@ -71,6 +75,7 @@ class FoldedConvAct(nn.Module):
         self.conv3x3_pad = None          # "zero" / "reflect" once routed to the 3 x 3 kernel (fuse_frozen_autoencoder(conv3x3="hip"))
         self.down3x3 = False             # True once routed to its stride-2 form (fuse_frozen_autoencoder(down3x3="hip"))
         self.up3x3 = False               # True once routed to its transposed form (fuse_frozen_autoencoder(up3x3="hip"))
+        self.tail7x7 = False             # True once routed to the 7 x 7 tail kernels (fuse_frozen_autoencoder(tail7x7="hip"))
 
     def route_conv3x3(self, pad):
         """send this convolution through ops.conv3x3_packed with the padding rule `pad`; the weight planes and the weight's amax slot
@@ -122,8 +127,28 @@ class FoldedConvAct(nn.Module):
         planes = ops.ConvT3x3Planes(*(getattr(self, name) for name in self._UP3X3_BUFFERS))
         return ops.convt3x3s2_packed(x, planes, self.bias, self.act)
 
+    _TAIL7X7_BUFFERS = ("_npvp_planes", "_npvp_w_amax", "_npvp_bwd_planes")
+
+    def route_tail7x7(self):
+        """send this ReflectionPad2d(3) -> 7 x 7 convolution -> activation through ops.tail7x7_packed (differentiable w.r.t. its input,
+        NCHW out); the forward planes, the weight's amax slot and the input gradient's planes are non-persistent buffers, built as
+        route_up3x3 builds its own"""
+        self.tail7x7 = True
+        planes = ops.tail7x7_planes(self.weight) if self.weight.is_cuda else (None,) * len(self._TAIL7X7_BUFFERS)
+        for name, t in zip(self._TAIL7X7_BUFFERS, planes):
+            self.register_buffer(name, t, persistent=False)
+
+    def _tail7x7(self, x):
+        if self._npvp_planes is None or self._npvp_planes.device != x.device:
+            for name, t in zip(self._TAIL7X7_BUFFERS, ops.tail7x7_planes(self.weight.to(x.device))):
+                setattr(self, name, t)
+        planes = ops.Tail7x7Planes(*(getattr(self, name) for name in self._TAIL7X7_BUFFERS))
+        return ops.tail7x7_packed(x, planes, self.bias, self.act)
+
     def forward(self, x, residual=None):
         # routed: channels-last frames only (anything else keeps the stock forward below: no silent copy)
+        if self.tail7x7 and residual is None and _channels_last_only(x):
+            return self._tail7x7(x)
         if self.up3x3 and residual is None and _channels_last_only(x):
             return self._up3x3(x)
         if self.conv3x3_pad is not None and _channels_last_only(x) and (residual is None or _channels_last_only(residual)):
@@ -233,6 +258,8 @@ UP3X3_ROUTES = ("stock", "hip")
 # where the stock remainder of a routed decoder runs (the 7 x 7 tail, and in front of it the 64 -> 32 transposed convolution of an
 # ngf = 32 decoder): on the channels-last tensor the routed convolutions hand over ("nhwc"), or with NCHW weights behind one copy back to
 # NCHW ("nchw"); whichever measured faster for decoder forward + input gradient (profiles/frozen_up3x3_bench.txt).  Read at fuse time.
+# It decides for a STOCK tail: where tail7x7="hip" routes the tail, which reads channels-last frames, whatever stays stock in front of
+# it keeps its channels-last weights and no copy back to NCHW is made.
 UP3X3_TAIL = "nchw"
 
 
@@ -262,6 +289,35 @@ def _route_up3x3(folded):
             m.route_up3x3()
 
 
+TAIL7X7_ROUTES = ("stock", "hip")
+
+
+def _check_tail7x7(tail7x7):
+    if tail7x7 not in TAIL7X7_ROUTES:
+        raise ValueError(f"tail7x7={tail7x7!r}: the route of the frozen decoder's 7 x 7 output convolution is one of {TAIL7X7_ROUTES}")
+
+
+def _tail7x7_takes_hip(m):
+    """whether the 7 x 7 tail kernels run this FoldedConvAct: a 7 x 7, stride-1, undilated, not transposed convolution with conv padding
+    0 behind ReflectionPad2d(3), C_in a multiple of 32, 1 <= C_out <= 4, activation none, Tanh or Sigmoid.  (The encoder's 7 x 7 stem
+    has C_in = 1 or 3 and wide C_out: another kernel shape, not built.)"""
+    if m.transposed or tuple(m.weight.shape[2:]) != (7, 7) or tuple(m.stride) != (1, 1) or tuple(m.dilation) != (1, 1):
+        return False
+    if type(m.pad) is not nn.ReflectionPad2d or tuple(m.pad.padding) != (3, 3, 3, 3) or tuple(m.padding) != (0, 0):
+        return False
+    if m.act not in ops.TAIL7X7_ACTS:
+        return False
+    # every (C_in, size) pair of the rule stays on the kernels: C_in = 64 at 64 x 64 x 1 and 64 x 64 x 3 frames, C_in = 32 at
+    # 128 x 128 x 3 - the "tail" lines of profiles/frozen_tail7x7_bench.txt; a pair that loses there would be named and excluded here
+    return ops.tail7x7_takes(m.weight.shape[1], m.weight.shape[0])
+
+
+def _route_tail7x7(folded):
+    for m in folded:
+        if _tail7x7_takes_hip(m):
+            m.route_tail7x7()
+
+
 def _zero_or_bias(lin):
     return lin.bias if lin.bias is not None else torch.zeros(lin.out_features, dtype=lin.weight.dtype, device=lin.weight.device)
 
@@ -282,7 +338,7 @@ def _attn2d_takes_hip(a):
             and a.out_proj.bias is not None)
 
 
-def fuse_frozen_autoencoder(enc, dec, attn2d="stock", conv3x3="stock", down3x3="stock", up3x3="stock"):
+def fuse_frozen_autoencoder(enc, dec, attn2d="stock", conv3x3="stock", down3x3="stock", up3x3="stock", tail7x7="stock"):
     """In-place module surgery on an eval-mode pair that already holds its final weights; freezes its parameters (do it after load_state_dict:
     the folded modules no longer carry the reference's state-dict keys).  Returns (enc, dec).
     attn2d: "stock" (default) leaves every NonLocalAttenion2D of the encoder on its own forward (PyTorch: the (frames, H*W, H*W/4) scores
@@ -300,11 +356,18 @@ def fuse_frozen_autoencoder(enc, dec, attn2d="stock", conv3x3="stock", down3x3="
     ngf = 64 decoder, all but the last (64 -> 32) of an ngf = 32 one - through ops.convt3x3s2_packed, which is differentiable w.r.t.
     its input (the decoder sits inside autograd in Stage 2), and makes the decoder convert its input frames to channels-last at its
     entry.  The 7 x 7 tail stays stock, with NCHW weights behind one copy back to NCHW (`UP3X3_TAIL`).  Any other value is refused.
-    The four switches are independent."""
+    tail7x7: "stock" (default) leaves the decoder's tail - ReflectionPad2d(3), Conv2d(ngf, output_nc, 7), Tanh / Sigmoid - on a padded
+    copy, MIOpen and npvp_bias_act; "hip" sends the FoldedConvAct of the DECODER that `_tail7x7_takes_hip` accepts through
+    ops.tail7x7_packed (one launch, padding as index math, bias and activation in the epilogue, NCHW out; differentiable w.r.t. its
+    input: act_bwd, amax, one input-gradient launch).  The routed tail reads channels-last frames: behind up3x3="hip" it takes them as
+    they come (and whatever stays stock between the routed convolutions keeps its channels-last weights: no copy back to NCHW), behind
+    up3x3="stock" the decoder makes one explicit copy to channels-last in front of it.  The encoder's 7 x 7 stem stays stock.  Any
+    other value is refused.  The five switches are independent."""
     _check_attn2d(attn2d)
     _check_conv3x3(conv3x3)
     _check_down3x3(down3x3)
     _check_up3x3(up3x3)
+    _check_tail7x7(tail7x7)
     for m in (enc, dec):
         assert not m.training, "fuse_frozen_autoencoder: eval mode only (BatchNorm must use its running statistics)"
         for q in m.parameters():
@@ -341,9 +404,12 @@ def fuse_frozen_autoencoder(enc, dec, attn2d="stock", conv3x3="stock", down3x3="
         if down3x3 == "hip":
             _route_down3x3([m for m in enc.modules() if isinstance(m, FoldedConvAct)])
         dec.model = _fold_sequential(dec.model)
+        if tail7x7 == "hip":
+            _route_tail7x7(list(dec.model))
+            dec.tail7x7 = any(m.tail7x7 for m in dec.model)
         if up3x3 == "hip":
             _route_up3x3(list(dec.model))
-            if UP3X3_TAIL == "nchw":
+            if UP3X3_TAIL == "nchw" and not dec.tail7x7:         # (a routed tail reads channels-last: the stock remainder stays there)
                 for m in dec.model:
                     if not m.up3x3:
                         m.weight = m.weight.contiguous()
@@ -636,15 +702,20 @@ class ResnetDecoder(nn.Module):
         self.model = nn.Sequential(*model)
 
     up3x3 = False          # True on a fused decoder whose transposed convolutions are routed (fuse_frozen_autoencoder(up3x3="hip"))
+    tail7x7 = False        # True on a fused decoder whose 7 x 7 tail is routed (fuse_frozen_autoencoder(tail7x7="hip"))
 
     def forward(self, x):
         N, T = x.shape[:2]
         y = x.flatten(0, 1)
-        if self.up3x3:
-            # the routed kernels are channels-last and the predictor hands out NCHW: ONE explicit, differentiable copy at the entry
-            y = y.contiguous(memory_format=torch.channels_last)
+        if self.up3x3 or self.tail7x7:
+            if self.up3x3:
+                # the routed kernels are channels-last and the predictor hands out NCHW: ONE explicit, differentiable copy at the entry
+                y = y.contiguous(memory_format=torch.channels_last)
             for m in self.model:
-                if not m.up3x3 and m.weight.is_contiguous() and not y.is_contiguous():
+                if m.tail7x7:
+                    if not _channels_last_only(y):
+                        y = y.contiguous(memory_format=torch.channels_last)      # (up3x3="stock": ONE explicit, differentiable copy)
+                elif not m.up3x3 and m.weight.is_contiguous() and not y.is_contiguous():
                     y = y.contiguous()                   # the stock remainder runs in its weights' layout (UP3X3_TAIL): one copy back to NCHW
                 y = m(y)
         else:
@@ -666,17 +737,20 @@ def build_frozen_autoencoder(AE, img_channels):
     return enc, dec
 
 
-def to_device_layout(enc, dec, device, attn2d="stock", conv3x3="stock", down3x3="stock", up3x3="stock"):
+def to_device_layout(enc, dec, device, attn2d="stock", conv3x3="stock", down3x3="stock", up3x3="stock", tail7x7="stock"):
     """Move the frozen pair to an MI355X.  The ENCODER runs in torch.channels_last (MIOpen's NHWC kernels: 27.5 -> 24.8 ms
     for 640 frames of 64x64, and its (N*T,H,W,C) output is the predictor's canonical layout, so the layout transpose at
     the predictor's entry disappears); the decoder stays NCHW (NHWC measured slower: 9.0 -> 11.2 ms fwd + input-grad on MIOpen)
     unless up3x3="hip" routes its transposed convolutions to the channels-last kernel: then it is moved to torch.channels_last too,
-    and fuse_frozen_autoencoder gives the stock remainder (the 7 x 7 tail) its NCHW weights back (`UP3X3_TAIL`: measured faster)."""
+    and fuse_frozen_autoencoder gives the stock remainder (the 7 x 7 tail) its NCHW weights back (`UP3X3_TAIL`: measured faster).
+    tail7x7="hip" routes that tail to the kernels of csrc/conv7x7.hip, which read channels-last frames and write NCHW ones."""
     _check_attn2d(attn2d)
     _check_conv3x3(conv3x3)
     _check_down3x3(down3x3)
     _check_up3x3(up3x3)
+    _check_tail7x7(tail7x7)
     enc, dec = enc.to(device).to(memory_format=torch.channels_last), dec.to(device)
     if up3x3 == "hip":
         dec = dec.to(memory_format=torch.channels_last)
-    return fuse_frozen_autoencoder(enc.eval(), dec.eval(), attn2d=attn2d, conv3x3=conv3x3, down3x3=down3x3, up3x3=up3x3)
+    return fuse_frozen_autoencoder(enc.eval(), dec.eval(), attn2d=attn2d, conv3x3=conv3x3, down3x3=down3x3, up3x3=up3x3,
+                                   tail7x7=tail7x7)

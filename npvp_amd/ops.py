@@ -2612,6 +2612,106 @@ def convt3x3s2_packed(x, planes, bias, act=0):
     return _ConvT3x3S2.apply(x, _c(bias), act, *planes)
 
 
+# --------------------------------------------------------------------------- frozen decoder: the 7 x 7 tail (csrc/conv7x7.hip)
+TAIL7X7_ACTS = (0, 2, 3)         # none, Tanh, Sigmoid
+
+
+def tail7x7_takes(C_in, C_out):
+    """channel counts of a ReflectionPad2d(3) -> Conv2d(C_in, C_out, 7) the route runs: a K-step of 32 inside one kernel row, the
+    output channels padded to 4 inside the 32 GEMM columns"""
+    return C_in > 0 and C_in % 32 == 0 and C_in <= 4096 and 1 <= C_out <= 4
+
+
+Tail7x7Planes = namedtuple("Tail7x7Planes", "fwd w_amax bwd")
+
+
+def tail7x7_planes(w):
+    """the planes of a frozen Conv2d weight w [C_out][C_in][7][7] for tail7x7_packed: fwd (npvp_tail7x7_planes, K ordered (kh, ci),
+    columns (kw, co)), the weight's amax slot, and bwd, the input gradient's planes at the scale of the same slot
+    (npvp_tail7x7_dgrad_planes)"""
+    _chk(w)
+    if w.dim() != 4 or tuple(w.shape[2:]) != (7, 7) or not tail7x7_takes(w.shape[1], w.shape[0]):
+        raise RuntimeError("tail7x7_planes: w must be [C_out][C_in][7][7] with C_in a multiple of 32 and 1 <= C_out <= 4")
+    w = w.detach().contiguous()
+    C_out, C_in = w.shape[:2]
+    L = lib()
+    halves = L.npvp_tail7x7_planes_bytes(C_in, C_out) // 2
+    fwd = torch.empty(halves, dtype=torch.float16, device=w.device)
+    bwd = torch.empty(halves, dtype=torch.float16, device=w.device)
+    slot = torch.zeros(AmaxSlot.FLOATS, device=w.device)
+    check(L.npvp_tail7x7_planes(_ptr(w), C_in, C_out, _ptr(fwd), _ptr(slot), _stream()), "npvp_tail7x7_planes")
+    check(L.npvp_tail7x7_dgrad_planes(_ptr(w), C_in, C_out, _ptr(bwd), _ptr(slot), _stream()), "npvp_tail7x7_dgrad_planes")
+    return Tail7x7Planes(fwd, slot, bwd)
+
+
+class _Tail7x7(_Function):
+    """y = act(conv2d(reflection_pad(x, 3), w) + bias[c]) of a frozen 7 x 7 weight with C_out <= 4: channels-last x in, contiguous
+    NCHW y out.  Gradient w.r.t. x only: npvp_act_bwd through the saved OUTPUT (planar), one npvp_amax pass, one
+    npvp_tail7x7_dgrad_f16 launch; dx is channels-last."""
+
+    @staticmethod
+    def forward(ctx, x, bias, act, fwd, w_amax, bwd):
+        remember(ctx)
+        Fr, C_in, H, W = x.shape
+        C_out = bias.shape[0]
+        x_slot = amax_of(x.permute(0, 2, 3, 1).reshape(Fr * H * W, C_in))            # (a view of x: finds the slot its producer attached)
+        y = torch.empty((Fr, C_out, H, W), device=x.device, dtype=torch.float32)
+        check(lib().npvp_tail7x7_f16(_ptr(x), _ptr(fwd), _ptr(bias), _ptr(y), Fr, H, W, C_in, C_out, act, _ptr(x_slot), _ptr(w_amax),
+                                     None, 0, _stream()), "npvp_tail7x7_f16")
+        ctx.act, ctx.dims = act, (Fr, C_in, H, W, C_out)
+        if ctx.needs_input_grad[0]:
+            ctx.save_for_backward(y, bwd, w_amax)
+        return y
+
+    @scoped
+    def backward(ctx, g):
+        y, bwd, w_amax = ctx.saved_tensors
+        Fr, C_in, H, W, C_out = ctx.dims
+        n = y.numel()
+        npad = (n + 3) // 4 * 4                          # npvp_amax reads float4s: a zero tail behind dz where n is no multiple of 4
+        g = _c(g)
+        if ctx.act != 0 or npad != n:
+            dz = torch.empty(npad, device=g.device, dtype=torch.float32)
+            if npad != n:
+                dz[n:].zero_()
+            if ctx.act != 0:
+                check(lib().npvp_act_bwd(_ptr(g), _ptr(y), _ptr(dz), n, ctx.act, _stream()), "npvp_act_bwd")
+            else:
+                dz[:n].copy_(g.view(-1))
+        else:
+            dz = g
+        s = AmaxSlot.new(g.device)
+        check(lib().npvp_amax(_ptr(dz), 1, npad, npad, _ptr(s), _stream()), "npvp_amax")
+        dx = torch.empty((Fr, H, W, C_in), device=g.device, dtype=torch.float32)
+        check(lib().npvp_tail7x7_dgrad_f16(_ptr(dz), _ptr(bwd), _ptr(dx), Fr, H, W, C_in, C_out, _ptr(s), _ptr(w_amax), None, 0, _stream()),
+              "npvp_tail7x7_dgrad_f16")
+        return dx.permute(0, 3, 1, 2), None, None, None, None, None
+
+
+def tail7x7_packed(x, planes, bias, act=0):
+    """y = act(conv2d(reflection_pad2d(x, 3), w) + bias[c]) of the frozen decoder's 7 x 7 output convolution on channels-last frames
+    x (F, C_in, H, W) -> contiguous NCHW (F, C_out, H, W), one npvp_tail7x7_f16 launch: the padding is index math, bias and activation
+    are the epilogue.  planes: tail7x7_planes of the folded weight.  act: 0 none, 2 Tanh, 3 Sigmoid.  The amax slot of x is its
+    producer's or one npvp_amax pass (amax_of).  Differentiable w.r.t. x (act_bwd, amax, one npvp_tail7x7_dgrad_f16; dx is
+    channels-last).  x must be channels-last (no silent copy); H, W >= 4, as reflection by 3 needs."""
+    _chk(x, bias, planes.w_amax)
+    if x.dim() != 4 or bias.dim() != 1:
+        raise RuntimeError("tail7x7_packed: x must be (F, C_in, H, W) and bias (C_out,)")
+    C_in, C_out = x.shape[1], bias.shape[0]
+    if not tail7x7_takes(C_in, C_out):
+        raise RuntimeError("tail7x7_packed: C_in must be a multiple of 32 and 1 <= C_out <= 4")
+    if act not in TAIL7X7_ACTS:
+        raise RuntimeError("tail7x7_packed: act is 0 (none), 2 (Tanh) or 3 (Sigmoid)")
+    if x.shape[2] < 4 or x.shape[3] < 4:
+        raise RuntimeError("tail7x7_packed: H and W must be at least 4 (ReflectionPad2d(3))")
+    for p in (planes.fwd, planes.bwd):
+        if p.numel() != 2 * 7 * C_in * 32 or not p.is_cuda or p.dtype != torch.float16:
+            raise RuntimeError("tail7x7_packed: planes do not belong to a [C_out][C_in][7][7] weight of this C_in")
+    if not x.permute(0, 2, 3, 1).is_contiguous():
+        raise RuntimeError("tail7x7_packed: x must be channels-last")
+    return _Tail7x7.apply(x, _c(bias), act, *planes)
+
+
 # --------------------------------------------------------------------------- Stage-1 autoencoder training (csrc/ae_train.hip)
 class _BnActTrain(_Function):
     """BatchNorm2d (batch statistics in training, running statistics in eval) -> act (0 none, 1 ReLU) [-> + residual] as one
