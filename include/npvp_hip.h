@@ -736,6 +736,35 @@ int npvp_tail7x7_dgrad_route(int F, int H, int W, int C_in, int C_out, int* out6
 /* out4 = {m0, m1, n0, n1}: the rows of [F H W] and the columns of C_in that workgroup `block` of the input gradient stores */
 int npvp_tail7x7_dgrad_tile(int F, int H, int W, int C_in, int C_out, int block, int* out4);
 
+/* ---- The 7 x 7 stem of the frozen encoder (opt-in, to_device_layout(..., stem7x7="hip"); csrc/conv7x7.hip): ReflectionPad2d(3) ->
+ * Conv2d(C_in, C_out, 7) -> BatchNorm (folded) -> ReLU (ref/models/ResNetAutoEncoder.py:51-146), forward only (the encoder runs under
+ * no_grad in Stage 2):
+ *   y[f,h,w,co] = act( bias[co] + sum_{kh,kw,ci} x[f, ci, refl_H(h + kh - 3), refl_W(w + kw - 3)] * w[co,ci,kh,kw] )
+ * x [F][C_in][H][W] fp32 PLANAR (NCHW, the layout the data path hands the encoder; for C_in = 1 also the channels-last memory) ->
+ * y [F][H][W][C_out] fp32 channels-last; refl is npvp_tail7x7_src; no padded copy of x.  An implicit GEMM with M = F H W in tiles of
+ * 128, N = C_out in tiles of 64 (32 when C_out % 64 != 0) and the dense K order k = (kh * 7 + kw) * C_in + ci, zero-padded from
+ * 49 C_in to a multiple of 32 (2 / 4 / 5 / 7 K-steps for C_in = 1 / 2 / 3 / 4).  f16x3 arithmetic as npvp_conv3x3_f16.
+ * 1 <= C_in <= 4, C_out a positive multiple of 32 up to 4096, F >= 1, H, W >= 4, F * H * W < 2^31; y and planes 16-byte aligned.
+ * Every element of y is written exactly once (no atomics on y, no memset); two runs give the same bits. */
+/* out3 = {kh, kw, ci} of K index k - the __host__ __device__ function the gather and the planes kernel call (csrc/conv7x7_index.h).
+ * Returns 0; 1 for an index of the zero padding (49 C_in <= k < K_pad; out3 = {-1, -1, -1}); -2: bad argument (out3 untouched). */
+int npvp_stem7x7_k(int C_in, int k, int* out3);
+/* bytes of the weight planes, or -1 for channel counts outside the rule */
+long long npvp_stem7x7_planes_bytes(int C_in, int C_out);
+/* w [C_out][C_in][7][7] (contiguous) -> planes [2 terms][K_pad / 8][C_out][8 over k] (zero for the padding of K).  w_amax is zeroed
+ * (by a kernel, not a memset node) and recomputed here.  Once per frozen weight. */
+int npvp_stem7x7_planes(const float* w, int C_in, int C_out, void* planes, float* w_amax, npvp_stream_t stream);
+/* The forward.  act: 0 none, 1 ReLU.  y_amax: the slot that receives the bound of the stored values, or NULL.  workspace / ws_bytes:
+ * reserved (NULL, 0). */
+int npvp_stem7x7_f16(const float* x, const void* planes, const float* bias, float* y, int F, int H, int W, int C_in, int C_out, int act,
+                     const float* x_amax, const float* w_amax, float* y_amax, void* workspace, long long ws_bytes, npvp_stream_t stream);
+/* The plan npvp_stem7x7_f16 launches: out7 = {tile variant (1: 64 columns, 2: 32), rows per tile, columns per tile, row tiles, column
+ * tiles, workgroups, K-steps}.  Returns 0, or -1 for a refused shape (out7 untouched).  Pure function. */
+int npvp_stem7x7_route(int F, int H, int W, int C_in, int C_out, int* out7);
+/* out4 = {m0, m1, n0, n1}: the rows of [F H W] and the columns of C_out that workgroup `block` stores - the function the kernel itself
+ * calls.  Pure function. */
+int npvp_stem7x7_tile(int F, int H, int W, int C_in, int C_out, int block, int* out4);
+
 /* ---- Stage-1 autoencoder training (csrc/ae_train.hip): LitAE.training_step / shared_step (ref/models/ResNetAutoEncoder.py:13-49)
  * through ResnetEncoder / ResnetDecoder (ref :51-204) and NonLocalAttenion2D (ref/models/submodules.py:98-176); the convolutions
  * stay MIOpen's.  Every entry point is deterministic (fixed-order sums, no atomics) and needs no zero-filled buffer.

@@ -1,7 +1,9 @@
-// Index math of the frozen decoder's 7 x 7 tail (conv7x7.hip: ReflectionPad2d(3) -> Conv2d(C_in, C_out <= 4, 7) -> activation), as
+// Index math of the frozen decoder's 7 x 7 tail (conv7x7.hip: ReflectionPad2d(3) -> Conv2d(C_in, C_out <= 4, 7) -> activation) and of
+// the frozen encoder's 7 x 7 stem (the same file: ReflectionPad2d(3) -> Conv2d(C_in <= 4, C_out, 7) -> activation), as
 // __host__ __device__ functions: the kernels and the launchers call them, and the C ABI exports them unchanged (npvp_tail7x7_src,
-// npvp_tail7x7_adj_src, npvp_tail7x7_route, npvp_tail7x7_tile, npvp_tail7x7_dgrad_route, npvp_tail7x7_dgrad_tile), so which pixel a
-// tap reads, which outputs a workgroup owns and which Z columns it holds are tested on the host.
+// npvp_tail7x7_adj_src, npvp_tail7x7_route, npvp_tail7x7_tile, npvp_tail7x7_dgrad_route, npvp_tail7x7_dgrad_tile, npvp_stem7x7_k,
+// npvp_stem7x7_route, npvp_stem7x7_tile), so which pixel a tap reads, which outputs a workgroup owns and which Z columns it holds are
+// tested on the host.
 #pragma once
 
 #include "conv3x3_index.h"
@@ -71,6 +73,21 @@ NPVP_HD Conv3x3Plan tail7x7_dgrad_plan(long long M, int C_in) {
   p.tiles_n = C_in / p.bn;
   p.grid = p.tiles_m * p.tiles_n;
   return p;
+}
+
+// ---- The encoder's stem: C[M = F H W][N = C_out] = A[M][K] B[K][N] with the dense K order k = (kh * 7 + kw) * C_in + ci, zero-padded
+// from 49 C_in to a multiple of 32 (C_in = 1, 2, 3, 4: 64, 128, 160, 224 - 2, 4, 5, 7 K-steps).  The tiles are tail7x7_dgrad_plan's over
+// (M, C_out): 128 rows x 64 columns (C_out % 64 == 0) or x 32, rows and columns by conv3x3_tile.
+NPVP_HD int stem7x7_kpad(int C_in) { return (49 * C_in + 31) / 32 * 32; }
+
+// K index k (0 <= k < stem7x7_kpad(C_in)) -> kernel row kh, kernel column kw, input channel ci; false for an index of the zero padding
+// (kh comes out as 7 or more there).  The gather of stem7x7_f16_kernel and stem7x7_planes_kernel both call it.
+NPVP_HD bool stem7x7_k(int C_in, int k, int& kh, int& kw, int& ci) {
+  const int tap = k / C_in;
+  ci = k - tap * C_in;
+  kh = tap / 7;
+  kw = tap - kh * 7;
+  return tap < 49;
 }
 
 }  // namespace npvp

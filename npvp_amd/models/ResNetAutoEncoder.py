@@ -29,7 +29,11 @@ checkpoints load.  `learn_3d=True` adds the temporal half of every Factorized3DC
            `tail7x7="hip"` (opt-in, independent of the other four switches, differentiable w.r.t. its input) sends the decoder's tail -
            ReflectionPad2d(3), Conv2d(ngf, output_nc, 7), Tanh / Sigmoid - through `ops.tail7x7_packed` (csrc/conv7x7.hip: one launch,
            padding as index math, bias and activation in the epilogue, channels-last frames in, NCHW frames out; the input gradient is
-           act_bwd, amax and one launch).  Behind `up3x3="hip"` no copy back to NCHW remains.  The encoder's 7 x 7 stem stays stock.
+           act_bwd, amax and one launch).  Behind `up3x3="hip"` no copy back to NCHW remains.
+           `stem7x7="hip"` (opt-in, inference only, independent of the other five switches) sends the encoder's stem `block0` -
+           ReflectionPad2d(3), Conv2d(input_nc, ngf, 7), BatchNorm (folded), ReLU - through `ops.stem7x7_packed` (csrc/conv7x7.hip: one
+           launch, planar NCHW frames in, channels-last frames out with their amax slot, so a routed `block1` runs no `npvp_amax` pass).
+           With it every convolution of an ngf = 64, `learn_3d=False` pair has a hand-written route.
 """
 import functools
 import types
@@ -76,6 +80,7 @@ class FoldedConvAct(nn.Module):
         self.down3x3 = False             # True once routed to its stride-2 form (fuse_frozen_autoencoder(down3x3="hip"))
         self.up3x3 = False               # True once routed to its transposed form (fuse_frozen_autoencoder(up3x3="hip"))
         self.tail7x7 = False             # True once routed to the 7 x 7 tail kernels (fuse_frozen_autoencoder(tail7x7="hip"))
+        self.stem7x7 = False             # True once routed to the 7 x 7 stem kernel (fuse_frozen_autoencoder(stem7x7="hip"))
 
     def route_conv3x3(self, pad):
         """send this convolution through ops.conv3x3_packed with the padding rule `pad`; the weight planes and the weight's amax slot
@@ -145,7 +150,26 @@ class FoldedConvAct(nn.Module):
         planes = ops.Tail7x7Planes(*(getattr(self, name) for name in self._TAIL7X7_BUFFERS))
         return ops.tail7x7_packed(x, planes, self.bias, self.act)
 
+    def route_stem7x7(self):
+        """send this ReflectionPad2d(3) -> 7 x 7 convolution -> activation through ops.stem7x7_packed (inference only; planar frames in,
+        channels-last frames out); planes and amax slot as route_conv3x3 keeps them"""
+        self.stem7x7 = True
+        planes, w_amax = ops.stem7x7_planes(self.weight) if self.weight.is_cuda else (None, None)
+        self.register_buffer("_npvp_planes", planes, persistent=False)
+        self.register_buffer("_npvp_w_amax", w_amax, persistent=False)
+
+    def _stem7x7(self, x):
+        if torch.is_grad_enabled() and x.requires_grad:
+            raise NotImplementedError('stem7x7="hip" (to_device_layout / fuse_frozen_autoencoder) is inference-only: the input of this '
+                                      'convolution requires grad; fuse the pair with stem7x7="stock" to differentiate through it')
+        if self._npvp_planes is None or self._npvp_planes.device != x.device:
+            self._npvp_planes, self._npvp_w_amax = ops.stem7x7_planes(self.weight.to(x.device))
+        return ops.stem7x7_packed(x, self._npvp_planes, self._npvp_w_amax, self.bias, self.act)
+
     def forward(self, x, residual=None):
+        # the routed stem: planar (contiguous NCHW) frames of at least 4 x 4 pixels only - what ops.stem7x7_packed accepts
+        if self.stem7x7 and residual is None and x.dim() == 4 and x.is_contiguous() and x.shape[2] >= 4 and x.shape[3] >= 4:
+            return self._stem7x7(x)
         # routed: channels-last frames only (anything else keeps the stock forward below: no silent copy)
         if self.tail7x7 and residual is None and _channels_last_only(x):
             return self._tail7x7(x)
@@ -300,7 +324,7 @@ def _check_tail7x7(tail7x7):
 def _tail7x7_takes_hip(m):
     """whether the 7 x 7 tail kernels run this FoldedConvAct: a 7 x 7, stride-1, undilated, not transposed convolution with conv padding
     0 behind ReflectionPad2d(3), C_in a multiple of 32, 1 <= C_out <= 4, activation none, Tanh or Sigmoid.  (The encoder's 7 x 7 stem
-    has C_in = 1 or 3 and wide C_out: another kernel shape, not built.)"""
+    has C_in = 1 or 3 and wide C_out: another kernel, `_stem7x7_takes_hip`.)"""
     if m.transposed or tuple(m.weight.shape[2:]) != (7, 7) or tuple(m.stride) != (1, 1) or tuple(m.dilation) != (1, 1):
         return False
     if type(m.pad) is not nn.ReflectionPad2d or tuple(m.pad.padding) != (3, 3, 3, 3) or tuple(m.padding) != (0, 0):
@@ -316,6 +340,36 @@ def _route_tail7x7(folded):
     for m in folded:
         if _tail7x7_takes_hip(m):
             m.route_tail7x7()
+
+
+STEM7X7_ROUTES = ("stock", "hip")
+
+
+def _check_stem7x7(stem7x7):
+    if stem7x7 not in STEM7X7_ROUTES:
+        raise ValueError(f"stem7x7={stem7x7!r}: the route of the frozen encoder's 7 x 7 input convolution is one of {STEM7X7_ROUTES}")
+
+
+def _stem7x7_takes_hip(m):
+    """whether the 7 x 7 stem kernel runs this FoldedConvAct: a 7 x 7, stride-1, undilated, not transposed convolution with conv padding
+    0 behind ReflectionPad2d(3), 1 <= C_in <= 4, C_out a multiple of 32, activation none or ReLU.  (The decoder's 7 x 7 tail has wide
+    C_in and C_out <= 4: `_tail7x7_takes_hip`.)"""
+    if m.transposed or tuple(m.weight.shape[2:]) != (7, 7) or tuple(m.stride) != (1, 1) or tuple(m.dilation) != (1, 1):
+        return False
+    if type(m.pad) is not nn.ReflectionPad2d or tuple(m.pad.padding) != (3, 3, 3, 3) or tuple(m.padding) != (0, 0):
+        return False
+    if m.act not in ops.STEM7X7_ACTS:
+        return False
+    # every (C_in -> C_out, size) of the rule stays on the kernel: 1 -> 64 at 640 frames of 64 x 64, 3 -> 64 at 1920 frames of 64 x 64 and
+    # 3 -> 32 at 160 frames of 128 x 128 - both hip timings, each with its npvp_amax pass over the frames, beat both padded copy + MIOpen +
+    # npvp_bias_act timings (the "stem" lines of profiles/frozen_stem7x7_bench.txt); a pair that loses there would be named and excluded here
+    return ops.stem7x7_takes(m.weight.shape[1], m.weight.shape[0])
+
+
+def _route_stem7x7(folded):
+    for m in folded:
+        if _stem7x7_takes_hip(m):
+            m.route_stem7x7()
 
 
 def _zero_or_bias(lin):
@@ -338,7 +392,8 @@ def _attn2d_takes_hip(a):
             and a.out_proj.bias is not None)
 
 
-def fuse_frozen_autoencoder(enc, dec, attn2d="stock", conv3x3="stock", down3x3="stock", up3x3="stock", tail7x7="stock"):
+def fuse_frozen_autoencoder(enc, dec, attn2d="stock", conv3x3="stock", down3x3="stock", up3x3="stock", tail7x7="stock",
+                            stem7x7="stock"):
     """In-place module surgery on an eval-mode pair that already holds its final weights; freezes its parameters (do it after load_state_dict:
     the folded modules no longer carry the reference's state-dict keys).  Returns (enc, dec).
     attn2d: "stock" (default) leaves every NonLocalAttenion2D of the encoder on its own forward (PyTorch: the (frames, H*W, H*W/4) scores
@@ -361,13 +416,19 @@ def fuse_frozen_autoencoder(enc, dec, attn2d="stock", conv3x3="stock", down3x3="
     ops.tail7x7_packed (one launch, padding as index math, bias and activation in the epilogue, NCHW out; differentiable w.r.t. its
     input: act_bwd, amax, one input-gradient launch).  The routed tail reads channels-last frames: behind up3x3="hip" it takes them as
     they come (and whatever stays stock between the routed convolutions keeps its channels-last weights: no copy back to NCHW), behind
-    up3x3="stock" the decoder makes one explicit copy to channels-last in front of it.  The encoder's 7 x 7 stem stays stock.  Any
-    other value is refused.  The five switches are independent."""
+    up3x3="stock" the decoder makes one explicit copy to channels-last in front of it.  Any other value is refused.
+    stem7x7: "stock" (default) leaves the encoder's stem - block0: ReflectionPad2d(3), Conv2d(input_nc, ngf, 7), BatchNorm, ReLU - on a
+    padded copy, MIOpen and npvp_bias_act; "hip" sends the FoldedConvActs of the ENCODER that `_stem7x7_takes_hip` accepts (block0[0])
+    through ops.stem7x7_packed (inference only: one launch on the planar frames the data path hands over, padding as index math, bias
+    and ReLU in the epilogue, channels-last out with its amax slot).  A frame tensor in another layout keeps the stock forward.  Any
+    other value is refused, before anything is changed.  The six switches are independent, and the state dict is the same under
+    every combination."""
     _check_attn2d(attn2d)
     _check_conv3x3(conv3x3)
     _check_down3x3(down3x3)
     _check_up3x3(up3x3)
     _check_tail7x7(tail7x7)
+    _check_stem7x7(stem7x7)
     for m in (enc, dec):
         assert not m.training, "fuse_frozen_autoencoder: eval mode only (BatchNorm must use its running statistics)"
         for q in m.parameters():
@@ -403,6 +464,8 @@ def fuse_frozen_autoencoder(enc, dec, attn2d="stock", conv3x3="stock", down3x3="
             _route_conv3x3([m for m in enc.modules() if isinstance(m, FoldedConvAct)])
         if down3x3 == "hip":
             _route_down3x3([m for m in enc.modules() if isinstance(m, FoldedConvAct)])
+        if stem7x7 == "hip":
+            _route_stem7x7([m for m in enc.modules() if isinstance(m, FoldedConvAct)])
         dec.model = _fold_sequential(dec.model)
         if tail7x7 == "hip":
             _route_tail7x7(list(dec.model))
@@ -737,20 +800,24 @@ def build_frozen_autoencoder(AE, img_channels):
     return enc, dec
 
 
-def to_device_layout(enc, dec, device, attn2d="stock", conv3x3="stock", down3x3="stock", up3x3="stock", tail7x7="stock"):
+def to_device_layout(enc, dec, device, attn2d="stock", conv3x3="stock", down3x3="stock", up3x3="stock", tail7x7="stock",
+                     stem7x7="stock"):
     """Move the frozen pair to an MI355X.  The ENCODER runs in torch.channels_last (MIOpen's NHWC kernels: 27.5 -> 24.8 ms
     for 640 frames of 64x64, and its (N*T,H,W,C) output is the predictor's canonical layout, so the layout transpose at
     the predictor's entry disappears); the decoder stays NCHW (NHWC measured slower: 9.0 -> 11.2 ms fwd + input-grad on MIOpen)
     unless up3x3="hip" routes its transposed convolutions to the channels-last kernel: then it is moved to torch.channels_last too,
     and fuse_frozen_autoencoder gives the stock remainder (the 7 x 7 tail) its NCHW weights back (`UP3X3_TAIL`: measured faster).
-    tail7x7="hip" routes that tail to the kernels of csrc/conv7x7.hip, which read channels-last frames and write NCHW ones."""
+    tail7x7="hip" routes that tail to the kernels of csrc/conv7x7.hip, which read channels-last frames and write NCHW ones.
+    stem7x7="hip" routes the encoder's 7 x 7 stem to the stem kernel of the same file, which reads the planar frames as they come and
+    writes channels-last ones."""
     _check_attn2d(attn2d)
     _check_conv3x3(conv3x3)
     _check_down3x3(down3x3)
     _check_up3x3(up3x3)
     _check_tail7x7(tail7x7)
+    _check_stem7x7(stem7x7)
     enc, dec = enc.to(device).to(memory_format=torch.channels_last), dec.to(device)
     if up3x3 == "hip":
         dec = dec.to(memory_format=torch.channels_last)
     return fuse_frozen_autoencoder(enc.eval(), dec.eval(), attn2d=attn2d, conv3x3=conv3x3, down3x3=down3x3, up3x3=up3x3,
-                                   tail7x7=tail7x7)
+                                   tail7x7=tail7x7, stem7x7=stem7x7)

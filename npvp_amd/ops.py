@@ -2712,6 +2712,87 @@ def tail7x7_packed(x, planes, bias, act=0):
     return _Tail7x7.apply(x, _c(bias), act, *planes)
 
 
+# --------------------------------------------------------------------------- frozen encoder: the 7 x 7 stem (csrc/conv7x7.hip)
+STEM7X7_ACTS = (0, 1)            # none, ReLU
+
+
+def stem7x7_takes(C_in, C_out):
+    """channel counts of a ReflectionPad2d(3) -> Conv2d(C_in, C_out, 7) the stem kernel runs: thin K (the image's channels), C_out in
+    32-column tiles"""
+    return 1 <= C_in <= 4 and C_out > 0 and C_out % 32 == 0 and C_out <= 4096
+
+
+def stem7x7_planes(w):
+    """(planes, w_amax) of a frozen weight w [C_out][C_in][7][7] for stem7x7_packed: the scaled two-term fp16 planes npvp_stem7x7_f16
+    reads, K ordered (kh, kw, ci) and zero-padded to a multiple of 32, and the weight's amax slot as a 512-float tensor"""
+    _chk(w)
+    if w.dim() != 4 or tuple(w.shape[2:]) != (7, 7) or not stem7x7_takes(w.shape[1], w.shape[0]):
+        raise RuntimeError("stem7x7_planes: w must be [C_out][C_in][7][7] with 1 <= C_in <= 4 and C_out a multiple of 32")
+    w = w.detach().contiguous()
+    C_out, C_in = w.shape[:2]
+    planes = torch.empty(lib().npvp_stem7x7_planes_bytes(C_in, C_out) // 2, dtype=torch.float16, device=w.device)
+    slot = torch.zeros(AmaxSlot.FLOATS, device=w.device)
+    check(lib().npvp_stem7x7_planes(_ptr(w), C_in, C_out, _ptr(planes), _ptr(slot), _stream()), "npvp_stem7x7_planes")
+    return planes, slot
+
+
+def _planar_amax(x):
+    """the amax slot of planar frames x (F, C, H, W), contiguous: its producer's, or one npvp_amax pass over the memory viewed as one
+    row (npvp_amax reads float4s: where the element count is no multiple of 4 - no frame size of the configs - the last 1..3 elements go
+    through a second pass over a zero-padded copy of those few floats)"""
+    for cand in (x, x._base):                            # as amax_of: a view is bounded by the slot of the tensor it is a view of
+        tag = getattr(cand, "_npvp_amax", None) if cand is not None else None
+        if tag is not None and tag[1] == cand._version:
+            return tag[0]
+    if x.data_ptr() % 16:
+        raise RuntimeError("stem7x7_packed: x carries no amax slot and does not start at a 16-byte boundary (npvp_amax reads float4s)")
+    flat = x.reshape(-1)                                 # a view: x is contiguous
+    n = flat.numel()
+    s, n4 = AmaxSlot.new(x.device), n - n % 4
+    if n4:
+        check(lib().npvp_amax(_ptr(flat), 1, n4, n4, _ptr(s), _stream()), "npvp_amax")
+    if n4 != n:
+        rest = torch.zeros(4, device=x.device)
+        rest[:n - n4] = flat[n4:]
+        check(lib().npvp_amax(_ptr(rest), 1, 4, 4, _ptr(s), _stream()), "npvp_amax")
+    return s
+
+
+def stem7x7_packed(x, planes, w_amax, bias, act=1, want_amax=True):
+    """y = act(conv2d(reflection_pad2d(x, 3), w) + bias[c]) of the frozen encoder's 7 x 7 input convolution on PLANAR frames
+    x (F, C_in, H, W) (contiguous NCHW, as the data path hands them over; with C_in = 1 that is the channels-last memory as well) ->
+    channels-last (F, C_out, H, W), one npvp_stem7x7_f16 launch: the padding is index math, bias and activation are the epilogue.
+    planes / w_amax: stem7x7_planes of the folded weight.  act: 0 none, 1 ReLU.  The amax slot of x is its producer's or one npvp_amax
+    pass over the planar memory; want_amax attaches the slot of y to the result and to its NCHW view, so a following conv3x3s2_packed
+    needs no pass.  Forward only: an input that requires grad is refused.  x in any other layout is refused (no silent copy); H, W >= 4,
+    as reflection by 3 needs."""
+    ts = [t for t in (x, bias) if t is not None]
+    if torch.is_grad_enabled() and any(t.requires_grad for t in ts):
+        raise NotImplementedError("stem7x7_packed: forward only (the frozen encoder's input convolution); an input requires grad")
+    _chk(x, w_amax, bias)
+    if x.dim() != 4 or bias.dim() != 1:
+        raise RuntimeError("stem7x7_packed: x must be (F, C_in, H, W) and bias (C_out,)")
+    Fr, C_in, H, W = x.shape
+    C_out = bias.shape[0]
+    if not stem7x7_takes(C_in, C_out):
+        raise RuntimeError("stem7x7_packed: 1 <= C_in <= 4 and C_out must be a multiple of 32")
+    if act not in STEM7X7_ACTS:
+        raise RuntimeError("stem7x7_packed: act is 0 (none) or 1 (ReLU)")
+    if H < 4 or W < 4:
+        raise RuntimeError("stem7x7_packed: H and W must be at least 4 (ReflectionPad2d(3))")
+    if planes.numel() != 2 * ((49 * C_in + 31) // 32 * 32) * C_out or not planes.is_cuda or planes.dtype != torch.float16:
+        raise RuntimeError("stem7x7_packed: planes do not belong to a [C_out][C_in][7][7] weight of these channel counts")
+    if not x.is_contiguous():
+        raise RuntimeError("stem7x7_packed: x must be planar (contiguous NCHW) frames")
+    x_slot = _planar_amax(x)
+    y = torch.empty((Fr, H, W, C_out), device=x.device, dtype=torch.float32)
+    y_slot = AmaxSlot.new(x.device) if want_amax else None
+    check(lib().npvp_stem7x7_f16(_ptr(x), _ptr(planes), _ptr(_c(bias)), _ptr(y), Fr, H, W, C_in, C_out, act, _ptr(x_slot), _ptr(w_amax),
+                                 _ptr(y_slot), None, 0, _stream()), "npvp_stem7x7_f16")
+    tag_amax(y, y_slot)                                             # (amax_of looks at a view's base)
+    return tag_amax(y.permute(0, 3, 1, 2), y_slot)
+
+
 # --------------------------------------------------------------------------- Stage-1 autoencoder training (csrc/ae_train.hip)
 class _BnActTrain(_Function):
     """BatchNorm2d (batch statistics in training, running statistics in eval) -> act (0 none, 1 ReLU) [-> + residual] as one
